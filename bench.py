@@ -37,6 +37,14 @@ native router rate times N — when that is below the job's rate. A simulated
 host-routed world also runs ``spread_drift``: the spread hot set refreshed incrementally
 (parallel/hotspread.py refresh_hot) under a drifting popularity order.
 
+A plain run does only what the headline needs: it sets up, fills the headline's cache (the
+--warmup steps are the last of the fill steps), times the K steps and prints the result
+line. ``--full`` adds every secondary block named above and below (the other cache states,
+the uncoalesced steps, GPU-event passes, request hit ratio and whole-lap timing, the drift
+blocks, the platform smoke checks). ``--dump-outputs DIR`` writes the GET response of the
+last timed step as ``DIR/<name>.npy`` (``capture_outputs``); the request stream is seeded,
+so two builds run with the same arguments can be compared output for output.
+
 Metric: whole-job cache operations per second (GET+SET requests served).
 The reference (kmacrow/Shellac) publishes no numbers, so vs_baseline is null.
 Secondary (outside the timed region): the BASELINE.json platform smoke checks
@@ -217,6 +225,17 @@ def parse():
                          "beside the previous step's SET chain, its reinsertions indexed as "
                          "moves (early), or at the head of the SET chain (inline)")
     ap.add_argument("--check", action="store_true", help="verify a sample of GET values")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other cache states "
+                         "(log_fresh, log_wrapped, log_pressured_cycled, log_overfull), the "
+                         "uncoalesced steps, the GPU-event passes, the request hit ratio and "
+                         "whole-lap timing of the full-cache blocks, the drift blocks and the "
+                         "platform smoke checks. Without it a run sets up, warms up, times the "
+                         "--steps headline steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to "
+                         "its caller (rank 0's GET response) as DIR/<name>.npy: see "
+                         "capture_outputs()")
     return ap.parse_args()
 
 
@@ -236,6 +255,65 @@ def router_bound(out: dict, router_req_per_s: float, world: int) -> dict:
         value = round(cap_, 1)
     hr_["value_bounded_by_router"] = not hr_["router_feeds_job"]
     return {"value": value, "ms_per_step": ms, "host_routing": hr_}
+
+
+DUMP_REQUESTS = 1 << 20   # per-request arrays: every request up to this many, else a sample
+DUMP_RECORDS = 1024       # whole records dumped byte for byte ...
+DUMP_RECORD_BYTES = 16 << 20   # ... in at most this much float32
+
+
+def capture_outputs(res, max_val: int) -> dict:
+    """--dump-outputs: what a serving step returned to its caller (a GetResult: ``data``,
+    ``off``, ``size``), as host arrays of at most 64 MB in all, name -> numpy array:
+
+      * ``size`` (float32 [n]): the record bytes of request i (0 = miss);
+      * ``record_bytesum`` (float64 [n]): the sum of the bytes of request i's record
+        (header, value and padding), so every byte of ``data`` a request points at counts;
+      * ``request_index`` (float64 [n]): which requests the two arrays above hold, every
+        one of them up to 2^20 requests, a fixed seeded sample beyond;
+      * ``records`` (float32 [k, 32 + max value padded to 16]): the records of a fixed seeded
+        sample of k requests byte for byte, zero beyond the record, and ``records_index``
+        (float64 [k]): the requests they belong to.
+
+    Records are dumped by content, not by ``off``: where a record lands in ``data`` is the
+    kernels' choice and differs from run to run of one build (nearly every offset, on the
+    default N=1 run), while the size and the bytes each request receives do not.
+    Call it before a later step reuses the response buffer."""
+    res.wait()
+    wd = res.data.device   # (pinned host memory under --edge host)
+    size = res.size.to(wd).long()
+    hit = size > 0
+    off = torch.where(hit, res.off.to(wd).long(), torch.zeros_like(size))
+    n = int(size.numel())
+    end = int((off + size).max()) if n else 0
+    cs = torch.zeros(end + 1, dtype=torch.int64, device=wd)
+    torch.cumsum(res.data[:end], 0, dtype=torch.int64, out=cs[1:])
+    g = torch.Generator(device="cpu").manual_seed(4711)
+    perm = torch.randperm(n, generator=g)
+    req = (torch.arange(n) if n <= DUMP_REQUESTS else perm[:DUMP_REQUESTS].sort()[0]).to(wd)
+    o, s = off.index_select(0, req), size.index_select(0, req)
+    width = 32 + ((max_val + 15) & ~15)
+    k = min(n, DUMP_RECORDS, max(1, DUMP_RECORD_BYTES // (4 * width)))
+    rows = perm[:k].sort()[0].to(wd)
+    ro, rs = off.index_select(0, rows), size.index_select(0, rows).clamp_(max=width)
+    col = torch.arange(width, device=wd)
+    inside = col[None, :] < rs[:, None]
+    at = torch.where(inside, ro[:, None] + col[None, :], torch.zeros_like(inside, dtype=torch.int64))
+    rec = torch.where(inside, res.data.index_select(0, at.flatten()).view(k, width),
+                      torch.zeros((), dtype=torch.uint8, device=wd))
+    return {"size": s.float().cpu().numpy(),
+            "record_bytesum": (cs.index_select(0, o + s) - cs.index_select(0, o)).double().cpu().numpy(),
+            "request_index": req.double().cpu().numpy(),
+            "records": rec.float().cpu().numpy(),
+            "records_index": rows.double().cpu().numpy()}
+
+
+def write_outputs(directory: str, arrays: dict) -> None:
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -627,10 +705,33 @@ def main():
                     cache.set(wl.set_batch(rep_ids[s0: s0 + chunk]))
         sync()
 
-    populate(sc)
+    host_edge = args.edge == "host"
+    steady_ok = not host_edge and dev.type == "cuda" and not args.no_wrapped
+    # the shard's working set: one record of every key it holds (its owner share, plus the
+    # replicas of spread hot objects), as the log stores it (header + 16-B aligned value)
+    held = (torch.arange(lo, hi, device=dev) if fill_ids is None else
+            fill_ids if rep_ids is None else torch.cat([fill_ids, rep_ids]))
+    ws_bytes = int((32 + ((wl.vlen.index_select(0, held).long() + 15) & ~15)).sum())
+    del held
+    p_gb = args.pressured_gb
+    if p_gb is None:
+        p_gb = ws_bytes / max(args.pressured_fill, 0.1) / (1 << 30)
+    do_pressured = p_gb > 0 and steady_ok and not msim
+    headline = args.headline if steady_ok else "fresh"
+    if headline == "pressured" and not do_pressured:
+        headline = "wrapped"
+    full = args.full
+    # A plain run of the full-cache headline needs nothing of the 16 GiB shard `sc` (the
+    # fresh and wrapped states): the headline block populates and fills a shard of its own.
+    # (The replica tier and the routed engine are set up through `sc`: then it is served.)
+    lean = not full and headline == "pressured" and replica is None and not sc.routed
+
+    if not lean:
+        populate(sc)
     if real_world > 1:
         dist.barrier()
-    log(rank, f"[bench] populated {total_keys} keys in {time.perf_counter() - t_setup:.1f}s")
+    log(rank, f"[bench] populated {0 if lean else total_keys} keys in "
+              f"{time.perf_counter() - t_setup:.1f}s")
 
     # pre-generated request batches (the "data loader"), cycled through the steps: 16
     # distinct pairs by default, so the GET digests alone (16 x 16 MiB) outgrow the 256 MB
@@ -673,7 +774,6 @@ def main():
         del seen
         log(rank, f"[bench] replicated {nrep} hot objects on every rank")
     shard.reserve(max(args.sets * 2, chunk))
-    host_edge = args.edge == "host"
     if host_edge:
         if real_world > 1 or sim or dev.type != "cuda":
             raise SystemExit("--edge host runs one GPU rank")
@@ -932,27 +1032,25 @@ def main():
                 "replica_dropped": st.get("replica_dropped", 0),
                 "replica_fetched_gib": round(st.get("replica_fetched_bytes", 0) / (1 << 30), 3)}
 
-    steady_ok = not host_edge and dev.type == "cuda" and not args.no_wrapped
-    # the shard's working set: one record of every key it holds (its owner share, plus the
-    # replicas of spread hot objects), as the log stores it (header + 16-B aligned value)
-    held = (torch.arange(lo, hi, device=dev) if fill_ids is None else
-            fill_ids if rep_ids is None else torch.cat([fill_ids, rep_ids]))
-    ws_bytes = int((32 + ((wl.vlen.index_select(0, held).long() + 15) & ~15)).sum())
-    del held
-    p_gb = args.pressured_gb
-    if p_gb is None:
-        p_gb = ws_bytes / max(args.pressured_fill, 0.1) / (1 << 30)
-    do_pressured = p_gb > 0 and steady_ok and not msim
-    headline = args.headline if steady_ok else "fresh"
-    if headline == "pressured" and not do_pressured:
-        headline = "wrapped"
-    for i in range(args.warmup):
-        step(i)
-    sync()
-    # the log not yet wrapped (the first K steps after the warmup)
-    fresh = window(sc, shard, args.warmup)
-    if args.check and headline == "fresh":
-        check(fresh)
+    dumped = {}
+
+    def headline_window(w):
+        """The headline's K timed steps are done: verify (--check) and keep (--dump-outputs)
+        their last response, before any later step can reuse its buffer."""
+        if args.check:
+            check(w)
+        if args.dump_outputs and rank == 0:
+            dumped.update(capture_outputs(w["res"], args.max_val))
+
+    fresh = None
+    if not lean:
+        for i in range(args.warmup):
+            step(i)
+        sync()
+        # the log not yet wrapped (the first K steps after the warmup)
+        fresh = window(sc, shard, args.warmup)
+        if headline == "fresh":
+            headline_window(fresh)
     diag = None
     if sc._engine is not None:
         # the routed step's SET exchange: early appends (look-ahead), carried rows
@@ -975,29 +1073,38 @@ def main():
             # a SET row that neither fit its slot nor the carry leaves the owner's older
             # value in place (a stale hit, not a miss): a checked run must not have any
             raise SystemExit(f"[bench] check: {clost} routed SET rows were lost (carry full)")
-    fresh_iv = timed(args.steps, args.warmup + args.steps, events=True)[1] if use_events else []
+    fresh_iv = (timed(args.steps, args.warmup + args.steps, events=True)[1]
+                if use_events and full else [])
     # secondary: the same steps with every GET probed and copied (no in-batch request
     # collapsing)
     unco = None
-    if sc.coalesce and not args.no_uncoalesced:
+    if full and sc.coalesce and not args.no_uncoalesced:
         sc.coalesce = False
         step(0)
         unco_el, _, _ = timed(args.steps, args.warmup)
         sc.coalesce = True
         unco = (args.batch + args.sets) * world * args.steps / unco_el
-    per_step = max((fresh["head1"] - fresh["head0"]) / max(args.steps, 1), 1.0)
+    if fresh is not None:
+        per_step = max((fresh["head1"] - fresh["head0"]) / max(args.steps, 1), 1.0)
+    else:
+        # what the fresh window's steps would have appended: one record of every distinct
+        # key of their SET batches (no reinsertions before the first wrap)
+        appended = sum(
+            int((32 + ((wl.vlen.index_select(0, torch.unique(set_ids[i % P])).long() + 15) & ~15)).sum())
+            for i in range(args.warmup, args.warmup + args.steps))
+        per_step = max(appended / max(args.steps, 1), 1.0)
 
     # the 16 GiB log wrapped: every SET batch runs the eviction hand, but the working set
     # fills only ~1/4 of the log, so nothing live is evicted or re-appended
     wrapped = wrapped_iv = nfill = None
-    if steady_ok:
+    if steady_ok and (full or headline == "wrapped"):
         base = args.warmup + 3 * args.steps
         nfill = fill_to_wrap(sc, shard, log_bytes, base, per_step)
         if nfill is not None:
             wrapped = window(sc, shard, base + nfill)
-            if args.check and headline == "wrapped":
-                check(wrapped)
-            if use_events:
+            if headline == "wrapped":
+                headline_window(wrapped)
+            if use_events and full:
                 wrapped_iv = timed(args.steps, base + nfill + args.steps, events=True)[1]
     if headline == "wrapped" and wrapped is None:
         raise SystemExit("[bench] the value log could not be wrapped for the headline; "
@@ -1005,11 +1112,15 @@ def main():
     # the full cache (the headline): a shard whose working set fills --pressured-fill of its
     # log, wrapped, so the CLOCK hand re-appends the objects the steps read (reinsertions)
     # and evicts the rest: the state a serving cache runs in (memcached evicts under load)
-    def full_cache(gb, check_it, min_fill=0, walk=None):
+    def full_cache(gb, is_headline, min_fill=0, walk=None):
         """A shard of `gb` GiB populated with this rank's keys, wrapped (fill steps, at least
-        `min_fill`), then the headline protocol (K timed steps), a GPU-event pass and one
-        whole lap timed: (summary, window, event intervals, fill steps). `walk`: the
-        (GET digests, GET ids, SET batches) the steps cycle instead of the default ones."""
+        `min_fill`), then the headline protocol (K timed steps) and, with --full, a GPU-event
+        pass, the request hit ratio and one whole lap timed: (summary, window, event
+        intervals, fill steps). `walk`: the (GET digests, GET ids, SET batches) the steps
+        cycle instead of the default ones. A plain run's --warmup steps are the last of the
+        fill steps (at least that many run)."""
+        if not full:
+            min_fill = max(min_fill, args.warmup)
         if walk is not None:
             cyc["gets"], cyc["get_ids"], cyc["sets"] = walk
         f_log = int(gb * (1 << 30)) // 16 * 16
@@ -1064,11 +1175,12 @@ def main():
         if ffill is not None:
             fw = window(f_sc, f_shard, fbase + ffill)
             debug_hot("after window")
-            if check_it:
-                check(fw)
+            if is_headline:
+                headline_window(fw)
             fiv = timed(args.steps, fbase + ffill + args.steps, events=True,
-                        cache=f_sc)[1] if use_events else []
+                        cache=f_sc)[1] if use_events and full else []
             out_ = summary(fw, fiv, f_log, ffill)
+        if out_ is not None and full:
             # what a client sees: the share of GET requests (duplicates included) answered
             # with a record, over K more steps (untimed: a reduction per step)
             hit_n = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -1139,18 +1251,21 @@ def main():
     pressured = pw = piv = pfill = None
     pressured_cycled = None
     wb = None  # the walk: built once, shared by the headline and log_overfull
-    if do_pressured and (args.set_walk or (args.overfull_fill > 0 and args.pressured_gb is None)):
+    # (a plain run: the full cache only as the headline, and no secondary block)
+    do_pressured = do_pressured and (full or headline == "pressured")
+    do_overfull = do_pressured and full and args.overfull_fill > 0 and args.pressured_gb is None
+    if do_pressured and (args.set_walk or do_overfull):
         wb = walk_batches()
     if do_pressured:
         walk = wb if args.set_walk else None
         pressured, pw, piv, pfill = full_cache(
-            p_gb, args.check and headline == "pressured",
+            p_gb, headline == "pressured",
             min_fill=2 * len(walk[2]) if walk else 0, walk=walk)
         if pressured is not None:
             pressured["stream"] = "walk" if walk else "cycled"
             pressured["set_batches_cycled"] = len(walk[2]) if walk else len(cyc["sets"])
             pressured["get_batches_cycled"] = len(walk[0]) if walk else len(cyc["gets"])
-        if walk is not None and not args.no_cycled and world == 1:
+        if full and walk is not None and not args.no_cycled and world == 1:
             # secondary (N = 1): the same full cache on the 16 cycled batches (round 5's
             # headline); skipped with more ranks, where each block repopulates every shard
             pressured_cycled = full_cache(p_gb, False)[0]
@@ -1159,7 +1274,7 @@ def main():
     # secondary: a working set larger than the log (--overfull-fill x the log): the hit ratio
     # when the cache cannot hold every key
     overfull = None
-    if do_pressured and args.overfull_fill > 0 and args.pressured_gb is None:
+    if do_overfull:
         # An evicted key comes back only when it is SET again (the default steps cycle 16
         # SET batches, 1M of the 4M keys), and 16 cycled GET batches read only ~1/3 of the
         # keys: walk_batches() (every key re-SET in turn, 256 fresh GET batches). The
@@ -1274,19 +1389,20 @@ def main():
     sdrift = None
     # (simulated worlds only: the real N-rank job's collectives in refresh_hot are covered by
     # the gloo test, and a secondary block must not put the driver's scaling run at risk)
-    if (host_route and sim and args.spread and args.drift_epochs > 0
+    if (full and host_route and sim and args.spread and args.drift_epochs > 0
             and args.spread_drift_steps > 0 and steady_ok):
         sdrift = spread_drift()
 
     # secondary: a drifting hot set (hot objects replaced every epoch) with the replica tier
     # maintained incrementally between epochs (refresh under a byte budget, no flush)
     drift = None
-    if (args.drift_epochs > 0 and replica is not None and dev.type == "cuda" and not bounce
-            and sc._hot is not None):
+    if (full and args.drift_epochs > 0 and replica is not None and dev.type == "cuda"
+            and not bounce and sc._hot is not None):
         drift = hot_drift()
 
     t_sm = time.perf_counter()
-    sm = {} if (args.no_smoke or dev.type != "cuda" or sim or bounce) else smoke(rank, world, dev)
+    sm = ({} if (not full or args.no_smoke or dev.type != "cuda" or sim or bounce) else
+          smoke(rank, world, dev))
     if sm:
         # BASELINE.json's headline: wall clock of the platform smoke checks
         sm["smoke_wallclock_s"] = round(time.perf_counter() - t_sm, 3)
@@ -1350,7 +1466,10 @@ def main():
         # live is evicted), "log_fresh" = before the first wrap
         "headline_phase": "log_" + headline,
         "working_set_over_capacity": round(ws_bytes / (hw_log * (1 << 30) if hw_log else log_bytes), 4),
-        "warmup_detail": (f"{args.warmup} warmup steps, {args.steps} pre-wrap steps (log_fresh), "
+        "warmup_detail": (f"a {hw_log:.2f} GiB shard populated and {hw_fill} fill steps to wrap "
+                          f"it, the --warmup steps the last of them; then the {args.steps} "
+                          f"timed steps") if headline == "pressured" and not full else
+                         (f"{args.warmup} warmup steps, {args.steps} pre-wrap steps (log_fresh), "
                           f"{2 * args.steps} more, {nfill} fill steps to wrap the 16 GiB log, 2 x "
                           f"{args.steps} steps there (log_wrapped); a {hw_log:.2f} GiB shard "
                           f"populated and {hw_fill} fill steps to wrap it; then the {args.steps} "
@@ -1377,7 +1496,7 @@ def main():
         "edge": args.edge,
         "routed_diag": diag,
         # the step before the value log first wraps (no eviction work)
-        "log_fresh": summary(fresh, fresh_iv),
+        "log_fresh": summary(fresh, fresh_iv) if fresh else None,
         # the 16 GiB log wrapped (the hand in every SET batch; ~1/4 of it live)
         "log_wrapped": summary(wrapped, wrapped_iv, fill=nfill) if wrapped else None,
         # the full cache (the default headline): reinsertions and evictions every step
@@ -1429,6 +1548,8 @@ def main():
                         "of the key space; profiling only, not a scaling result"))
         out["n_gpus"] = 1
         out["simulated_world"] = sim
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dumped)
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if real_world > 1:

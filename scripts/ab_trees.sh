@@ -13,7 +13,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for d in "$@"; do
     tag=$(basename "$(cd "$d" && pwd)")
     [ "$d" = "." ] && tag=main
-    (cd "$d" && timeout -k 10 300 python -u bench.py --no-uncoalesced --no-smoke $AB_ARGS \
+    (cd "$d" && timeout -k 10 300 python -u bench.py --full --no-uncoalesced --no-smoke $AB_ARGS \
        > "$R/${tag}_$r.json" 2> "$R/${tag}_$r.err") \
       || { echo "$tag round $r failed"; tail -20 "$R/${tag}_$r.err"; exit 1; }
     python3 -c "import json; d=json.load(open('$R/${tag}_$r.json')); f=d.get('log_fresh') or {}; p=d.get('log_pressured') or {}; print('$tag', $r, 'wrapped', d['ms_per_step'], 'fresh', f.get('ms_per_step'), 'pressured', p.get('ms_per_step'))"

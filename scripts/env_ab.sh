@@ -7,7 +7,7 @@ O=gpurun_out/${1:-env_ab}; shift; mkdir -p "$O"
 k=0
 for e in "$@"; do
   k=$((k + 1))
-  env $e timeout -k 10 300 python -u bench.py --no-uncoalesced --no-smoke --check $EXTRA > "$O/v$k.json" 2> "$O/v$k.err" \
+  env $e timeout -k 10 300 python -u bench.py --full --no-uncoalesced --no-smoke --check $EXTRA > "$O/v$k.json" 2> "$O/v$k.err" \
     || { echo "variant $k ($e) failed"; tail -5 "$O/v$k.err"; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/v$k.json')); p=d.get('log_pressured') or {}; w=d.get('log_wrapped') or {}

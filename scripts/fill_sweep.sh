@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-fill_sweep}
 shift
 mkdir -p "$OUT"
 for f in "$@"; do
-  timeout -k 10 400 python -u bench.py --pressured-fill "$f" --no-cycled --overfull-fill 0 \
+  timeout -k 10 400 python -u bench.py --full --pressured-fill "$f" --no-cycled --overfull-fill 0 \
     --no-uncoalesced > "$OUT/fill_$f.json" 2> "$OUT/fill_$f.err" \
     || { echo "fill $f failed"; tail -20 "$OUT/fill_$f.err"; exit 1; }
   python - "$OUT/fill_$f.json" "$f" <<'PY'

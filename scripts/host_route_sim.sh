@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for n in ${2:-"2 4 8"}; do
   for k in ${3:-"0 1024"}; do
     tag=sim${n}_spread${k}
-    timeout -k 10 400 python -u bench.py --no-uncoalesced --no-smoke --check --simulate-world "$n" \
+    timeout -k 10 400 python -u bench.py --full --no-uncoalesced --no-smoke --check --simulate-world "$n" \
       --route host --spread "$k" $SIM_ARGS > "$OUT/$tag.json" 2> "$OUT/$tag.err" \
       || { echo "$tag failed"; tail -20 "$OUT/$tag.err"; exit 1; }
     python3 -c "

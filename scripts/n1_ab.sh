@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 k=0
 for a in "$@"; do
   k=$((k + 1))
-  timeout -k 10 300 python -u bench.py --no-uncoalesced --no-smoke $a > "$OUT/v$k.json" 2> "$OUT/v$k.err" \
+  timeout -k 10 300 python -u bench.py --full --no-uncoalesced --no-smoke $a > "$OUT/v$k.json" 2> "$OUT/v$k.err" \
     || { echo "variant $k ($a) failed"; tail -20 "$OUT/v$k.err"; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$OUT/v$k.json')); f=d.get('log_fresh') or {}; p=d.get('log_pressured') or {}; print('v$k', repr('$a'), 'wrapped', d['ms_per_step'], 'fresh', f.get('ms_per_step'), 'pressured', p.get('ms_per_step'), 'probes/req', d['get_probes_per_request'])"
 done

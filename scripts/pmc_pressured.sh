@@ -8,7 +8,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 P=gpurun_out/${1:-pmc_pressured}; shift
 mkdir -p "$P"
-ARGS="--steps 40 --warmup 2 --no-uncoalesced --no-smoke --pressured-gb 0 --log-gb 4.92 $*"
+ARGS="--full --steps 40 --warmup 2 --no-uncoalesced --no-smoke --pressured-gb 0 --log-gb 4.92 $*"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $P/$c -o run -- python3 bench.py $ARGS > $P/$c.log 2>&1 || { tail -5 $P/$c.log; exit 1; }
 done

@@ -5,7 +5,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 P=${PMC_OUT:-gpurun_out/pmc}
 mkdir -p "$P"
-ARGS="--steps 6 --warmup 2 --no-uncoalesced --no-smoke $*"
+ARGS="--full --steps 6 --warmup 2 --no-uncoalesced --no-smoke $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $P/trace -o run -- python3 bench.py $ARGS > $P/trace.log 2>&1 || exit 1
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/fetch -o run -- python3 bench.py $ARGS > $P/fetch.log 2>&1 || exit 1
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $P/write -o run -- python3 bench.py $ARGS > $P/write.log 2>&1 || exit 1

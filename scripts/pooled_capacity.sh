@@ -16,7 +16,7 @@ LOG_GB=${LOG_GB:-8}
 for n in ${2:-"1 2 4 8"}; do
   tag=cap_n${n}
   if [ "$n" = 1 ]; then sim=""; else sim="--simulate-world $n --route host"; fi
-  timeout -k 10 600 python -u bench.py --no-uncoalesced --no-smoke --keys-total "$KEYS" \
+  timeout -k 10 600 python -u bench.py --full --no-uncoalesced --no-smoke --keys-total "$KEYS" \
     --pressured-gb "$LOG_GB" --log-gb 2 --set-walk $sim $CAP_ARGS \
     > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { echo "$tag failed"; tail -20 "$OUT/$tag.err"; exit 1; }
   python3 -c "

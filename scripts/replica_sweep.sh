@@ -11,7 +11,7 @@ export PYTHONUNBUFFERED=1
 for w in $WORLDS; do
   for r in $REPS; do
     f="$OUT/sim${w}_rep${r}.json"
-    timeout -k 10 240 python -u bench.py --steps 20 --warmup 5 --no-uncoalesced --no-wrapped \
+    timeout -k 10 240 python -u bench.py --full --steps 20 --warmup 5 --no-uncoalesced --no-wrapped \
       --no-smoke --simulate-world "$w" --replicate "$r" "$@" > "$f" 2> "$OUT/sim${w}_rep${r}.err" \
       || { echo "sim $w rep $r failed"; tail -20 "$OUT/sim${w}_rep${r}.err"; exit 1; }
     python3 -c "import json; d=json.load(open('$f')); print('sim$w rep $r', d['ms_per_step'], d.get('ms_per_step_median_gpu_events'), 'replica_hit', d['replica_hit_fraction'])"

@@ -9,7 +9,7 @@ export PYTHONUNBUFFERED=1
 for v in "$@"; do
   for args in "--simulate-world 8" "--simulate-world 2" "--routed"; do
     name=$(echo "x$args$v" | tr -d ' -')
-    timeout -k 10 240 python -u bench.py --steps 20 --warmup 5 --no-uncoalesced --no-wrapped \
+    timeout -k 10 240 python -u bench.py --full --steps 20 --warmup 5 --no-uncoalesced --no-wrapped \
       --no-smoke $args $v > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
       || { echo "bench $args $v failed"; tail -30 "$OUT/bench_$name.err"; exit 1; }
     echo "== $args $v: $(python3 -c "import json,sys; d=json.load(open('$OUT/bench_$name.json')); print(d['ms_per_step'], d.get('ms_per_step_median_gpu_events'))")"

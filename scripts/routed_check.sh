@@ -14,7 +14,7 @@ timeout -k 10 500 python -u -m pytest -x -v --timeout 150 --timeout-method threa
 tail -3 "$OUT/tests.log"
 for args in "--simulate-world 8" "--simulate-world 2" "--routed" ""; do
   name=$(echo "x$args" | tr -d ' -')
-  timeout -k 10 240 python -u bench.py --steps 20 --warmup 5 --check --no-uncoalesced \
+  timeout -k 10 240 python -u bench.py --full --steps 20 --warmup 5 --check --no-uncoalesced \
     --no-wrapped "$@" $args > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
     || { echo "bench $args failed"; tail -30 "$OUT/bench_$name.err"; exit 1; }
   echo "== $args"; grep check "$OUT/bench_$name.err"; cut -c1-300 "$OUT/bench_$name.json"

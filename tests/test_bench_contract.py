@@ -127,20 +127,65 @@ def test_bench_more_gpus_than_devices_exits_nonzero():
     assert "GPUs on this node" in p.stderr
 
 
-def test_bench_simulated_host_routed_world_cpu():
+def test_bench_simulated_host_routed_world_cpu(tmp_path):
     """--simulate-world 4 --route host: rank 0's owner share of the Zipf stream over its
-    1/4 of a 4x key space (one process, no mirrored collectives)."""
+    1/4 of a 4x key space (one process, no mirrored collectives). --dump-outputs writes the
+    last timed step's GET response as float arrays that agree with each other."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2",
                         "--warmup", "1", "--device", "cpu", "--batch", "2048", "--sets", "256",
                         "--keys-per-gpu", "8192", "--log-gb", "0.125", "--batches", "2",
                         "--no-uncoalesced", "--simulate-world", "4", "--route", "host",
-                        "--check"], capture_output=True, text=True, timeout=600, cwd="/tmp")
+                        "--check", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert out["config"]["routing"] == "host" and out["simulated_world"] == 4
     assert out["config"]["keys_total"] == 4 * 8192
     assert out["get_hit_ratio"] == 1.0
     assert "0 mismatches" in p.stderr
+    arrays = {f.stem: np.load(f) for f in dump.iterdir()}
+    assert sorted(arrays) == ["record_bytesum", "records", "records_index", "request_index",
+                              "size"]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+    n = arrays["size"].shape[0]
+    assert n > 0 and np.array_equal(arrays["request_index"], np.arange(n))
+    assert (arrays["size"] > 0).all()           # every key is held: no miss
+    rows = arrays["records_index"].astype(np.int64)
+    assert np.array_equal(arrays["records"].sum(axis=1), arrays["record_bytesum"][rows])
+    # a record is [32-byte header | value | pad to 16]: word 4 of the header is the length
+    vlen = arrays["records"][:, 16] + 256 * arrays["records"][:, 17]
+    assert np.array_equal(32 + (vlen.astype(np.int64) + 15) // 16 * 16, arrays["size"][rows])
+
+
+def test_capture_outputs_reads_each_request_record():
+    """capture_outputs() on a hand-made response: sizes, byte sums and sampled
+    records follow (off, size) of each request, a miss counts as nothing, and the sample
+    is the same from call to call."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from shellac_amd.models.sharded_cache import GetResult
+
+    data = (torch.arange(4096, dtype=torch.int64) % 251).to(torch.uint8)
+    off = torch.tensor([48, 999999, 0, 1024], dtype=torch.int64)   # request 1: a miss
+    size = torch.tensor([48, 0, 32, 112], dtype=torch.int64)
+    a = bench.capture_outputs(GetResult(data, off, size), max_val=80)
+    assert a["size"].tolist() == [48, 0, 32, 112]
+    assert set(a) == {"size", "record_bytesum", "request_index", "records", "records_index"}
+    want = [float(data[o: o + s].sum()) for o, s in ((48, 48), (0, 0), (0, 32), (1024, 112))]
+    assert a["record_bytesum"].tolist() == want
+    assert a["records"].shape == (4, 32 + 80) and sorted(a["records_index"].tolist()) == [0, 1, 2, 3]
+    for row, i in zip(a["records"], a["records_index"].astype(int)):
+        o, s = int(off[i]) if size[i] else 0, int(size[i])
+        assert np.array_equal(row[:s], data[o: o + s].numpy()) and not row[s:].any()
+    b = bench.capture_outputs(GetResult(data, off, size), max_val=80)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 @pytest.mark.gpu
@@ -151,7 +196,7 @@ def test_bench_host_routed_ranks_on_one_gpu():
     rank's cache routed over the default group.)"""
     p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--bounce", "--route", "host", "--check", "--steps", "3", "--warmup",
-                        "1", "--no-uncoalesced"],
+                        "1", "--no-uncoalesced", "--full"],
                        capture_output=True, text=True, timeout=300, cwd="/tmp",
                        env={**os.environ, "SHELLAC_BENCH_STACKS": "60"})
     assert p.returncode == 0, p.stderr[-3000:]
@@ -180,7 +225,7 @@ def test_bench_pooled_capacity_mode_on_one_gpu():
                         "--simulate-world", "2", "--route", "host", "--keys-total", str(16 << 20),
                         "--pressured-gb", "4", "--log-gb", "2", "--set-walk",
                         "--walk-get-batches", "32", "--overfull-fill", "0", "--check",
-                        "--steps", "3", "--warmup", "1", "--no-uncoalesced", "--no-smoke"],
+                        "--steps", "3", "--warmup", "1", "--no-uncoalesced", "--no-smoke", "--full"],
                        capture_output=True, text=True, timeout=300, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -195,6 +240,45 @@ def test_bench_pooled_capacity_mode_on_one_gpu():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_times_only_the_headline(tmp_path):
+    """Without --full a run fills the headline's full cache, times the K steps there and
+    stops: no secondary block, no smoke check; the result line keeps its headline fields,
+    --check is clean and --dump-outputs holds the last timed step's response."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--steps", "3", "--warmup", "1", "--keys-per-gpu", str(1 << 20),
+                        "--batch", str(1 << 18), "--sets", str(1 << 14),
+                        "--walk-get-batches", "16", "--check", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=300, cwd="/tmp")
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["metric"] == "cache_ops_per_s" and out["unit"] == "requests/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "uint8"
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(((1 << 18) + (1 << 14)) / out["ms_per_step"] * 1e3,
+                                         rel=1e-3)
+    assert out["headline_phase"] == "log_pressured"
+    pr = out["log_pressured"]
+    assert pr["ms_per_step"] == out["ms_per_step"] and pr["stream"] == "walk"
+    assert pr["fill_steps"] >= 2 * pr["set_batches_cycled"] == 128
+    assert "request_hit_ratio" not in pr and "lap_steps" not in pr
+    for k in ("log_fresh", "log_wrapped", "log_pressured_cycled", "log_overfull",
+              "uncoalesced_ops_per_s", "hot_drift", "spread_drift"):
+        assert out[k] is None, k
+    assert out["smoke"] == {} and "ms_per_step_median_gpu_events" not in out
+    assert "check: 0 mismatches in 200 sampled GETs" in p.stderr
+    size = np.load(dump / "size.npy")
+    assert size.shape == (1 << 18,) and 0.8 < (size > 0).mean() <= 1.0
+    rows = np.load(dump / "records_index.npy").astype(np.int64)
+    rec = np.load(dump / "records.npy")
+    assert np.array_equal(rec.sum(axis=1), np.load(dump / "record_bytesum.npy")[rows])
+
+
+@pytest.mark.gpu
 def test_bench_spread_drift_block_on_one_gpu():
     """The spread_drift block (simulated host-routed world): each epoch drifts the
     popularity order, refreshes the spread hot set incrementally (hotspread.refresh_hot) and
@@ -203,7 +287,7 @@ def test_bench_spread_drift_block_on_one_gpu():
     p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"),
                         "--simulate-world", "2", "--route", "host", "--keys-per-gpu", str(1 << 20),
                         "--drift-epochs", "2", "--spread-drift-steps", "4", "--overfull-fill", "0",
-                        "--steps", "3", "--warmup", "1", "--no-uncoalesced", "--no-smoke"],
+                        "--steps", "3", "--warmup", "1", "--no-uncoalesced", "--no-smoke", "--full"],
                        capture_output=True, text=True, timeout=300, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
