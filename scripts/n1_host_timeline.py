@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-side timeline of the N=1 serve step (bench.py's default config): wraps the
-shard calls ShardedCache.serve makes and reports, per step, how long the host spends
+shard calls ShardedCache.serve (models/local_step.py LocalStep.serve) makes and reports, per step, how long the host spends
 before the lookup launch, in each launch call, spinning on the lookup total, and from
 the end of that spin to the next step's lookup launch (the part that can starve the GPU
 when it exceeds the gather)."""
@@ -11,7 +11,6 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
-import shellac_amd.models.sharded_cache as scm  # noqa: E402
 from shellac_amd.bench.workload import Workload  # noqa: E402
 from shellac_amd.models.sharded_cache import ShardedCache  # noqa: E402
 from shellac_amd.ops.cache import CacheShard, reserve_step_streams  # noqa: E402
@@ -45,7 +44,6 @@ def main():
 
     for nm in ("lookup_coalesced", "store", "gather", "host_total"):
         wrap(shard, nm, nm)
-    wrap(scm, "expand_out", "expand_out")
     ready = torch.cuda.Event()
     ready.record()
     for i in range(30):
@@ -74,8 +72,7 @@ def main():
             last_spin_end = t
         if tag == "serve>":
             for a, b in (("serve<", "lookup_coalesced<"), ("lookup_coalesced<", "lookup_coalesced>"),
-                         ("store<", "store>"), ("expand_out<", "expand_out>"),
-                         ("gather<", "gather>"), ("host_total<", "host_total>"),
+                         ("store<", "store>"), ("gather<", "gather>"), ("host_total<", "host_total>"),
                          ("host_total>", "serve>"), ("serve<", "serve>")):
                 if a in cur and b in cur:
                     per.setdefault(f"{a[:-1]}..{b[:-1]}", []).append(cur[b] - cur[a])

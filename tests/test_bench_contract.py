@@ -188,6 +188,58 @@ def test_capture_outputs_reads_each_request_record():
     assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
+def test_sharded_cache_surface_bench_reads():
+    """The ShardedCache surface bench.py and the tests drive, on a CPU shard at world 1:
+    the names bench.py reads with their values before any step, every knob's default, and
+    one serve and one get that return what a set stored."""
+    import torch
+
+    from shellac_amd.models.sharded_cache import SetBatch, ShardedCache
+    from shellac_amd.ops.cache import CacheShard, digest_strings, pack_values, unpack_records
+
+    env = {k: os.environ.pop(k, None) for k in ("SHELLAC_STOP_EVENTS", "SHELLAC_STOP_FENCE")}
+    try:
+        sc = ShardedCache(CacheShard(1 << 22, 1 << 12, 1 << 14, "cpu"))
+    finally:
+        os.environ.update({k: v for k, v in env.items() if v is not None})
+    assert sc._hot is None and sc._engine is None
+    assert getattr(sc, "_calibrations", 0) == 0
+    assert sc.gathered_bytes == 0 and sc.routed is False and sc.world == 1
+    assert sc.stats == dict.fromkeys(
+        ("get_requests", "set_requests", "remote_gets", "replica_hits", "replica_refreshes",
+         "coalesced_gets", "slot_overflow_rows", "reply_dropped_rows"), 0)
+    sc.stats["replica_added"] = 1          # refresh_replica adds keys to the same dict
+    assert sc.stats.pop("replica_added") == 1
+    b = torch.tensor([[-5, 1], [0, 2], [7, 3]], dtype=torch.int64)   # sorted by lo
+    a = torch.tensor([[0, 2], [7, 4], [9, 9]], dtype=torch.int64)    # same row, hi differs, absent
+    assert ShardedCache._member(a, b).tolist() == [True, False, False]
+    assert ShardedCache._member(a, b[:0]).tolist() == [False] * 3
+    knobs = {"coalesce": True, "overlap_store": True, "event_fence": "none",
+             "stop_events": True, "stop_fence": "none", "gather_after_append": False,
+             "hand": "early", "host_edge": False, "host_edge_dma": True, "fused": True,
+             "comm_mode": "channels", "hot_decay": 0.5, "probe_of": None}
+    assert {k: vars(sc)[k] for k in knobs} == knobs   # plain attributes of the cache itself
+
+    keys = [f"/k{i}".encode() for i in range(300)]
+    v1 = [f"v1:{i}".encode() * (1 + i % 11) for i in range(300)]
+    dg = digest_strings(keys)
+    sc.set(SetBatch(dg, *pack_values(v1)))
+
+    def values(res):
+        return [r[0] if r else None for r in unpack_records(res.data, res.off, res.size)]
+
+    assert values(sc.get(dg)) == v1
+    # a step's GETs see the state before its SETs; the next get sees them
+    v2 = [b"v2:" + k for k in keys[:100]]
+    res = sc.serve(dg, SetBatch(digest_strings(keys[:100]), *pack_values(v2))).wait()
+    assert values(res) == v1
+    sc.sync_sets()
+    assert values(sc.get(dg)) == v2 + v1[100:]
+    assert values(sc.get(digest_strings([b"/absent"]))) == [None]
+    assert sc.stats["get_requests"] == 901 and sc.stats["set_requests"] == 400
+    assert sc._engine is None   # no routed step ran
+
+
 @pytest.mark.gpu
 def test_bench_host_routed_ranks_on_one_gpu():
     """The N>1 default's flow (host-routed ranks, barriers and reductions between steps,
