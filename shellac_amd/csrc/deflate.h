@@ -6,21 +6,31 @@
 // the CPU. This engine moves that compression to the GPU for whole batches of bodies
 // ("batch gzip on GPU for the miss path").
 //
-// Design (deflate.hip, two passes around a host planning step): every input is cut into
-// 32 KiB blocks and every block is one workgroup of ONE wave.
-//  1. k_lz77: the wave keeps the block and a 4096-entry hash head table in LDS and parses
-//     greedily: at each position the 64 lanes compare the candidate match 64 bytes at a
-//     time (one ballot finds the first mismatch) and hash the positions a match covers
-//     in parallel. It writes the block's tokens, its literal/length + distance symbol
-//     histogram and its CRC-32 register (lane slices combined by GF(2) multiplies).
-//  2. host (huffman.cc, a few threads): per block, the cheapest of stored / fixed
-//     Huffman / dynamic Huffman by exact bit count, length-limited canonical codes and
-//     the dynamic header.
-//  3. k_emit: the codes in LDS; each chunk of 64 tokens is placed by a wave prefix sum of
+// Design (deflate.hip, four kernels on one stream, no host step between them): every input
+// is cut into 32 KiB blocks and every block is one workgroup of ONE wave.
+//  1. k_lz77: the wave keeps the block, a 4096-entry hash head table and a per-position
+//     hash chain in LDS. The chains are built 64 positions per step; then every lane parses
+//     its own 1/64 segment of the block: up to 12 chain candidates per position, 4 bytes
+//     compared at a time, lazy matching as zlib's levels 4-9. A match never crosses the
+//     lane's segment, so the lanes' token lists concatenate. It writes the block's tokens,
+//     its literal/length + distance symbol histogram and its CRC-32 register (lane slices
+//     combined by GF(2) multiplies).
+//  2. k_plan: per block, the planner of deflate_plan.h (the same code huffman.cc runs on
+//     the host for tests): the cheapest of stored / fixed Huffman / dynamic Huffman by
+//     exact bit count, length-limited canonical codes and the dynamic header.
+//  3. k_slot_scan: exclusive scan of the planned sizes, the compact output layout.
+//  4. k_emit: the codes in LDS; each chunk of 64 tokens is placed by a wave prefix sum of
 //     their bit lengths and OR-ed into an LDS bit buffer, written out whole.
-// Blocks are independent (the window never crosses a block), so a non-final block ends
-// with an empty stored block (the zlib sync-flush marker 00 00 FF FF) and the blocks of
-// one input concatenate byte-wise. The host folds the blocks' CRC registers per input.
+// Blocks are independent (no match reaches before its block's first byte), so a non-final
+// Huffman block ends with an empty stored block (the zlib sync-flush marker 00 00 FF FF),
+// a stored block is byte-aligned by itself, and the blocks of one input concatenate
+// byte-wise. The host folds the blocks' CRC registers per input.
+//
+// Gunzip (k_inflate): one wave per member. The host parses the gzip framing and declines
+// what it does not check itself (FHCRC, reserved flags); the kernel decodes the DEFLATE
+// stream and reports an error for everything zlib would reject in it, including a stream
+// that does not end exactly where the trailer begins. Accepting no more than zlib does is
+// the contract: whatever this path declines is given to zlib, which reports the error.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

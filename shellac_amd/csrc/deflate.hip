@@ -1,5 +1,8 @@
-// Batch gzip on the GPU: one wave per 32 KiB block, greedy LZ77 over an LDS hash table,
-// fixed-Huffman DEFLATE codes (RFC 1951 §3.2.6). See deflate.h for the design.
+// Batch gzip and gunzip on the GPU. Compression: one wave per 32 KiB block; a lazy LZ77
+// parse over LDS hash chains, one segment of the block per lane (k_lz77); stored / fixed /
+// dynamic Huffman codes chosen per block on the device by the planner of deflate_plan.h
+// (k_plan); a compact output layout (k_slot_scan); lane-parallel emission (k_emit).
+// Decompression: one wave per gzip member (k_inflate). See deflate.h for the design.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -492,18 +495,22 @@ __device__ __forceinline__ int inf_decode(InfState& st, const uint8_t* s_ring, c
   return -1;
 }
 
-// counts + symbols from code lengths (lane 0 writes); false on an over-subscribed code
-__device__ bool inf_construct(InfHuff* h, const uint8_t* len, int n, int lane) {
+// counts + symbols from code lengths (lane 0 writes); false on a code set zlib rejects:
+// an over-subscribed one, or an incomplete one — except, for a literal/length or distance
+// set (`codes` false, not the code-length code), no code at all or a single 1-bit code
+__device__ bool inf_construct(InfHuff* h, const uint8_t* len, int n, bool codes, int lane) {
   bool ok = true;
   if (lane == 0) {
     for (int k = 0; k < 16; ++k) h->count[k] = 0;
     for (int sym = 0; sym < n; ++sym) h->count[len[sym]]++;
-    int left = 1;
+    int left = 1, longest = 0;
     for (int k = 1; k < 16; ++k) {
       left <<= 1;
       left -= h->count[k];
       if (left < 0) ok = false;
+      if (h->count[k]) longest = k;
     }
+    if (left > 0 && (codes || longest > 1)) ok = false;
     uint16_t offs[16];
     offs[1] = 0;
     for (int k = 1; k < 15; ++k) offs[k + 1] = (uint16_t)(offs[k] + h->count[k]);
@@ -605,8 +612,8 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* __restrict__ in,
         for (int sym = 0; sym < 30; ++sym) s_len[288 + sym] = 5;
       }
       __syncthreads();
-      inf_construct(&s_ll, s_len, 288, lane);
-      inf_construct(&s_dd, s_len + 288, 30, lane);
+      inf_construct(&s_ll, s_len, 288, false, lane);
+      inf_construct(&s_dd, s_len + 288, 30, false, lane);  // 30 of 32 codes, by definition
     } else {  // dynamic codes
       const int nlen = (int)inf_bits(st, s_ring, 5) + 257;
       const int ndist = (int)inf_bits(st, s_ring, 5) + 1;
@@ -618,7 +625,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* __restrict__ in,
       if (lane == 0)
         for (int k = 0; k < 19; ++k) s_len[kOrd[k]] = (uint8_t)clv[k];
       __syncthreads();
-      if (!inf_construct(&s_ll, s_len, 19, lane)) { err = 5; break; }
+      if (!inf_construct(&s_ll, s_len, 19, true, lane)) { err = 5; break; }
       int idx = 0;
       uint8_t prevlen = 0;
       uint8_t lens[316];
@@ -653,8 +660,9 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* __restrict__ in,
         for (int k = 0; k < ndist; ++k) s_len[288 + k] = lens[nlen + k];
       }
       __syncthreads();
-      inf_construct(&s_ll, s_len, nlen, lane);
-      inf_construct(&s_dd, s_len + 288, ndist, lane);
+      const bool ll_ok = inf_construct(&s_ll, s_len, nlen, false, lane);
+      const bool dd_ok = inf_construct(&s_dd, s_len + 288, ndist, false, lane);
+      if (!ll_ok || !dd_ok) { err = 15; break; }
     }
     // the block's symbols
     static constexpr uint16_t kLBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27,
@@ -668,6 +676,9 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* __restrict__ in,
     static constexpr uint8_t kDExt[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6,
                                           6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
     for (;;) {
+      // bytes are fetched only when their bits are needed, so a position past the end
+      // means the symbols now come from the ring's zero fill, not from the member
+      if (st.pos > st.in_len) { err = 14; break; }
       maybe_refill();
       if (opos - flushed > kInfWin - 2 * 258 - kInfFlush) flush();
       else if (opos - flushed >= kInfFlush) flush();
@@ -704,6 +715,9 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* __restrict__ in,
       opos += len;
     }
   }
+  // the stream must end in the member's last byte before the trailer (fewer than 8 bits
+  // are ever buffered, so st.pos counts the bytes the stream used)
+  if (!err && st.pos != st.in_len) err = 14;
   if (!err) flush();
   if (lane == 0) {
     res[2 * m] = (uint32_t)min(opos, (int64_t)0x7FFFFFFF) | (err ? 0x80000000u : 0u);
@@ -759,11 +773,14 @@ std::vector<std::string> GpuGzip::deflate(const std::vector<std::string_view>& i
   return out;
 }
 
-// gzip member -> (raw DEFLATE offset, length, ISIZE, CRC) or false (framing, RFC 1952)
+// gzip member -> (raw DEFLATE offset, length, ISIZE, CRC) or false (framing, RFC 1952).
+// Declined, so that zlib judges them: reserved FLG bits (zlib rejects those) and FHCRC (the
+// header checksum is not verified here).
 static bool parse_gzip_member(std::string_view z, size_t* off, size_t* len, uint32_t* isize,
                               uint32_t* crc) {
   if (z.size() < 18 || (uint8_t)z[0] != 0x1f || (uint8_t)z[1] != 0x8b || z[2] != 8) return false;
   const uint8_t flg = (uint8_t)z[3];
+  if (flg & 0xE2) return false;
   size_t p = 10;
   if (flg & 4) {  // FEXTRA
     if (p + 2 > z.size()) return false;
@@ -775,7 +792,6 @@ static bool parse_gzip_member(std::string_view z, size_t* off, size_t* len, uint
       ++p;
     }
   }
-  if (flg & 2) p += 2;  // FHCRC
   if (p + 8 > z.size()) return false;
   auto u32 = [&](size_t q) {
     return (uint32_t)(uint8_t)z[q] | ((uint32_t)(uint8_t)z[q + 1] << 8) |

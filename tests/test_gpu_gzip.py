@@ -2,7 +2,6 @@
 input (gzip framing, CRC-32 and ISIZE checked by zlib), across empty, tiny, multi-block,
 incompressible (stored-block fallback) and highly repetitive inputs."""
 import gzip
-import os
 import random
 import zlib
 
@@ -33,7 +32,8 @@ def test_round_trip_mixed_batch(gz):
     rng = random.Random(5)
     block = 32768
     bodies = [b"", b"a", b"ab", b"abc", b"aaaa" * 100, b"x" * 258, b"x" * 259,
-              os.urandom(1000), os.urandom(block), os.urandom(block + 1),
+              random.Random(1).randbytes(1000), random.Random(2).randbytes(block),
+              random.Random(3).randbytes(block + 1),
               _html(rng, 4096), _html(rng, block), _html(rng, block + 17),
               _html(rng, 3 * block + 5), bytes(range(256)) * 300, b"\x00" * 100000]
     out = gz.compress(bodies)
@@ -58,7 +58,7 @@ def test_raw_deflate_and_ratio(gz):
 
 def test_incompressible_falls_back_to_stored(gz):
     before = gz.stats().stored_blocks
-    bodies = [os.urandom(20000) for _ in range(4)]
+    bodies = [random.Random(n).randbytes(20000) for n in range(4)]
     out = gz.compress(bodies)
     for b, o in zip(bodies, out):
         assert zlib.decompress(o, 31) == b
@@ -143,9 +143,9 @@ def test_gpu_inflate_matches_zlib(gz):
     long runs (distance 1 back-references), plus the GPU's own members; a corrupt member
     is rejected (None), never returned wrong."""
     rng = random.Random(11)
-    bodies = [b"", b"a", b"hello world", b"x" * 100000, os.urandom(70000),
+    bodies = [b"", b"a", b"hello world", b"x" * 100000, random.Random(12).randbytes(70000),
               _html(rng, 4096), _html(rng, 200000), bytes(range(256)) * 500,
-              b"ab" * 40000 + os.urandom(300)]
+              b"ab" * 40000 + random.Random(13).randbytes(300)]
     members = [gzip.compress(b, lvl) for b in bodies for lvl in (1, 6, 9)]
     members += gz.compress(bodies)
     want = [b for b in bodies for _ in (1, 6, 9)] + bodies
