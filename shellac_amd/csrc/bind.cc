@@ -160,16 +160,17 @@ PYBIND11_MODULE(_shellac_core, m) {
       .def("gather", [](HbmCache& c, uintptr_t loc, uintptr_t off, int64_t n, uintptr_t out,
                         uintptr_t s, uint64_t out_cap, uintptr_t first, uintptr_t size,
                         uintptr_t out_size, uintptr_t out_off, uintptr_t table, uintptr_t cslot,
-                        uintptr_t prefix, int shift) {
+                        uintptr_t prefix, int shift, int64_t table_slots) {
         py::gil_scoped_release nogil;
         c.gather(P<const uint64_t>(loc), P<const uint64_t>(off), n, P<uint8_t>(out), S(s),
                  out_cap, P<const uint32_t>(first), P<const uint64_t>(size), P<uint64_t>(out_size),
                  P<uint64_t>(out_off), P<uint32_t>(table), P<const uint32_t>(cslot),
-                 P<const uint64_t>(prefix), shift);
+                 P<const uint64_t>(prefix), shift, table_slots);
       }, py::arg("loc"), py::arg("off"), py::arg("n"), py::arg("out"), py::arg("stream"),
          py::arg("out_cap") = ~0ull, py::arg("first") = 0, py::arg("size") = 0,
          py::arg("out_size") = 0, py::arg("out_off") = 0, py::arg("table") = 0,
-         py::arg("cslot") = 0, py::arg("prefix") = 0, py::arg("shift") = 0)
+         py::arg("cslot") = 0, py::arg("prefix") = 0, py::arg("shift") = 0,
+         py::arg("table_slots") = 0)
       .def("store_graph", [](HbmCache& c, HbmCache::StoreGraph& g, uintptr_t keys,
                              uintptr_t values, uintptr_t val_off, uintptr_t vlen, uintptr_t flags,
                              uintptr_t expire, int64_t n, uint64_t bytes_bound, uint32_t now,

@@ -67,10 +67,12 @@ class HbmCache {
   // `cslot` (optional, u32 [n]): each claiming row's table slot, for
   // expand_coalesced_out to clear; `table_clean`: the caller guarantees a zeroed table
   // (skips the memset).
-  // `prefix` (optional, kMaxGrid + 1 words): block-local offsets — `off` gets each row's
-  // offset within its lookup workgroup's rows and `prefix` the exclusive prefix of the
-  // workgroup totals (one small scan instead of the n-row one); returns the row shift of a
-  // workgroup (its rows are [b << shift, (b + 1) << shift)), for gather(prefix, shift).
+  // `prefix` (optional, kMaxGrid + 1 words): the blocked lookup — `off` gets one packed word
+  // per row, (the row's offset within its lookup workgroup's rows) << 21 | its record bytes
+  // (0 for a miss or a duplicate request), `size` is not written (may be null), `loc` is
+  // written for claiming rows only, and `prefix` gets the exclusive prefix of the workgroup
+  // totals (one small scan instead of the n-row one); returns the row shift of a workgroup
+  // (its rows are [b << shift, (b + 1) << shift)), for gather(prefix, shift).
   // Without `prefix`: `off` is the exclusive scan of `size`; returns -1.
   // `index_done`: completes with the kernel that reads (and reference-marks) the index, as
   // that kernel's own completion signal (no marker packet between it and the next kernel
@@ -164,12 +166,15 @@ class HbmCache {
   // `first` (a coalesced lookup): the gather's workgroups also write every request's
   // (size, off) from its claimer into out_size / out_off and clear the claimers' slots of
   // the coalescing table (expand_coalesced_out's work, no launch of its own).
+  // `prefix`, `shift` (a blocked lookup, lookup_coalesced with a prefix): `off` holds its
+  // packed rows, `size` and `cslot` are unused, and all `table_slots` words of `table` are
+  // zeroed by streaming stores instead of a store per claimer.
   void gather(const uint64_t* loc, const uint64_t* off, int64_t n, uint8_t* out, hipStream_t s,
               uint64_t out_cap = ~0ull, const uint32_t* first = nullptr,
               const uint64_t* size = nullptr, uint64_t* out_size = nullptr,
               uint64_t* out_off = nullptr, uint32_t* table = nullptr,
               const uint32_t* cslot = nullptr, const uint64_t* prefix = nullptr,
-              int shift = 0);
+              int shift = 0, int64_t table_slots = 0);
   // SET a batch. values + val_off[i] holds vlen[i] bytes (val_off 16-byte aligned,
   // the buffer readable 16 bytes past every value). Later duplicates of a key in
   // the same batch win. `bytes_bound` must bound sum(item_bytes(vlen)).

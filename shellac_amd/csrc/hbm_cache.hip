@@ -543,6 +543,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
 // reads the 128-B bucket), so coalescing and lookup are one pass over the batch, and
 // the workgroup's contiguous row range yields the partial sums k_offsets scans.
 constexpr int kCoPer = 4;                   // keys per thread per chunk
+// A blocked lookup's row: block-local byte offset << kPackBits | record bytes. A record is
+// at most item_bytes(max_item) < 2^21 bytes (checked by lookup_coalesced); a lookup
+// workgroup has at most 2^20 rows (n < 2^31 rows over kMaxGrid workgroups of whole
+// power-of-two chunk counts), so its local offsets stay below 2^41.
+constexpr int kPackBits = 21;
+constexpr uint64_t kPackSizeMask = (1ull << kPackBits) - 1;
+__device__ __forceinline__ uint64_t pack_row(uint64_t local_off, uint32_t bytes) {
+  return local_off << kPackBits | bytes;
+}
 constexpr int kCoKeys = kBlock * kCoPer;    // keys per chunk
 constexpr int kCoSlots = 2 * kCoKeys;       // LDS table slots (<= 50 % load)
 
@@ -556,11 +565,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     Entry* __restrict__ index, uint64_t mask, const uint64_t* __restrict__ head_ptr,
     uint64_t reserve, uint64_t cap, uint32_t now, uint64_t* __restrict__ out_loc,
     uint64_t* __restrict__ out_size, CacheCounters* __restrict__ ctr,
-    uint64_t* __restrict__ part, int local_only, uint64_t* __restrict__ woff) {
+    uint64_t* __restrict__ part, int local_only, uint64_t* __restrict__ packed) {
   __shared__ Digest s_k[kCoKeys];       // the chunk's digests (LDS compares, probe input)
-  // woff (PROBE, optional): each row's exclusive offset within this workgroup's rows (the
-  // gather adds the prefix of the workgroup totals, k_block_prefix): the chunk's sizes are
-  // kept in s_tab (free after the local claims) and scanned at the end of the chunk
+  // packed (PROBE, optional; the blocked lookup): one word per row, pack_row(the row's
+  // exclusive offset within this workgroup's rows, its record bytes) — a non-claimer carries
+  // its running offset and 0 bytes. It replaces out_size (not written at all) and the
+  // non-claimers' out_loc (only a claimer's is written: the gather never reads the source of
+  // an empty segment). The gather adds the prefix of the workgroup totals. The chunk's sizes
+  // are kept in s_tab (free after the local claims) and scanned at the end of the chunk
   __shared__ unsigned long long s_wt[kBlock / 64], s_run;
   if (threadIdx.x == 0) s_run = 0;
   __shared__ uint32_t s_tab[kCoSlots];  // local row + 1
@@ -709,8 +721,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
             hv = entry_vlen(hv);
             ++ops;
             out_loc[base + j] = hl ? (hl - 1) % cap : kMissLoc;
-            out_size[base + j] = hl ? item_bytes(hv) : 0;
-            if (woff) s_tab[j] = hl ? (uint32_t)item_bytes(hv) : 0u;
+            if (packed)
+              s_tab[j] = hl ? (uint32_t)item_bytes(hv) : 0u;
+            else
+              out_size[base + j] = hl ? item_bytes(hv) : 0;
             if (hl) {
               ++hits;
               bytes += hv;
@@ -728,14 +742,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
       const uint32_t f = s_rep[lrep[u]];
       first[base + j] = f;
       if (PROBE && f != (uint32_t)(base + j)) {
-        out_loc[base + j] = kMissLoc;
-        out_size[base + j] = 0;
-        if (woff) s_tab[j] = 0u;
+        if (packed) {
+          s_tab[j] = 0u;
+        } else {
+          out_loc[base + j] = kMissLoc;
+          out_size[base + j] = 0;
+        }
         ++dups;
       }
     }
     __syncthreads();  // LDS is reused by the next chunk
-    if (PROBE && woff) {
+    if (PROBE && packed) {
       // the chunk's exclusive offsets from its sizes (kCoPer consecutive rows per thread)
       const int t4 = threadIdx.x * kCoPer;
       uint32_t v[kCoPer];
@@ -762,7 +779,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
       }
 #pragma unroll
       for (int u = 0; u < kCoPer; ++u) {
-        if (t4 + u < cnt) woff[base + t4 + u] = ex;
+        if (t4 + u < cnt) packed[base + t4 + u] = pack_row(ex, v[u]);
         ex += v[u];
       }
       __syncthreads();  // s_run and s_wt read by every thread
@@ -771,7 +788,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
   }
   if (PROBE) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) out_size[n] = 0;
+    if (!packed && blockIdx.x == 0 && threadIdx.x == 0) out_size[n] = 0;
     block_count(ctr, ops, &CacheCounters::get_ops, hits, &CacheCounters::get_hits, bytes,
                 &CacheCounters::get_bytes);
     block_count(ctr, dups, &CacheCounters::get_coalesced);
@@ -882,20 +899,22 @@ __device__ __forceinline__ int64_t seg_search_global(const uint64_t* off, int64_
 }
 
 // Segment offsets of a byte mover: a plain array, or (Blocked) the coalescing lookup's
-// block-local offsets plus the exclusive prefix of its per-workgroup totals — off(j) =
-// prefix[j >> shift] + local[j] for j < n, the total for j >= n (no 1M-row scan between
-// the lookup and the gather: k_block_prefix scans only the workgroup totals).
+// packed rows (pack_row: block-local offset, record bytes) plus the exclusive prefix of its
+// per-workgroup totals — off(j) = prefix[j >> shift] + (packed[j] >> kPackBits) for j < n,
+// the total for j >= n (no 1M-row scan between the lookup and the gather: k_block_prefix
+// scans only the workgroup totals).
 struct PlainOff {
   const uint64_t* __restrict__ p;
   __device__ __forceinline__ uint64_t operator[](int64_t j) const { return p[j]; }
 };
 struct BlockedOff {
-  const uint64_t* __restrict__ local;
+  const uint64_t* __restrict__ packed;
   const uint64_t* __restrict__ prefix;
   int64_t n;
   int shift;
   __device__ __forceinline__ uint64_t operator[](int64_t j) const {
-    return j < n ? prefix[j >> shift] + local[j] : prefix[((n - 1) >> shift) + 1];
+    return j < n ? prefix[j >> shift] + (packed[j] >> kPackBits)
+                 : prefix[((n - 1) >> shift) + 1];
   }
 };
 
@@ -991,6 +1010,11 @@ __device__ __forceinline__ int64_t block_last_le(const Off off, int64_t lo,
 // copies (a grid-stride tail, n = 0: none): row i takes its claimer's (size, off), and
 // every claimer clears its slot of the coalescing table (k_expand_out's work, without a
 // launch or a stream of its own).
+// A blocked lookup (`prefix` set): `off` holds its packed rows and `size` is unused — one
+// random 8-byte read per request (the claimer's row) plus the claimer's block prefix; and
+// the whole table (`tab_words` words, no `cslot`) is zeroed with streaming 16-byte stores
+// spread over the workgroups: 8 MiB written for a 1M batch, where a scattered 4-byte store
+// per claimer cost ~317K partial sectors plus the cslot array written and read back.
 struct ExpandTail {
   const uint32_t* first = nullptr;
   int64_t n = 0;
@@ -1002,13 +1026,57 @@ struct ExpandTail {
   const uint32_t* cslot = nullptr;
   const uint64_t* prefix = nullptr;  // non-null: `off` holds block-local offsets (BlockedOff)
   int shift = 0;
+  int64_t tab_words = 0;             // blocked: words of `tab`, all zeroed
 };
+// The blocked lookup's tail. A thread has a few rows (~2.7 of a 1M batch on 1,536
+// workgroups): the loads of kRows of them are issued together — `first` for all, then the
+// claimers' packed rows and block prefixes for all, then the stores — so the tail costs two
+// memory round trips, not two per row.
+__device__ __forceinline__ void expand_tail_packed(const ExpandTail& ex) {
+  constexpr int kRows = 4;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < ex.n;
+       i0 += kRows * stride) {
+    uint32_t f[kRows];
+    uint64_t p[kRows], pre[kRows];
+#pragma unroll
+    for (int u = 0; u < kRows; ++u) {
+      const int64_t i = i0 + u * stride;
+      f[u] = i < ex.n ? ex.first[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < kRows; ++u) {
+      p[u] = ex.off[f[u]];  // (row 0 past the end: a valid address, the value unused)
+      pre[u] = ex.prefix[f[u] >> ex.shift];
+    }
+#pragma unroll
+    for (int u = 0; u < kRows; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i >= ex.n) continue;
+      ex.out_size[i] = p[u] & kPackSizeMask;
+      ex.out_off[i] = pre[u] + (p[u] >> kPackBits);
+    }
+  }
+  if (ex.tab) {  // (idempotent: the retry gather after an outgrown capacity runs it again)
+    const int64_t n4 = ex.tab_words >> 2;
+    u32x4* __restrict__ t4 = reinterpret_cast<u32x4*>(ex.tab);
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n4; k += stride)
+      t4[k] = u32x4{0u, 0u, 0u, 0u};
+    if (blockIdx.x == 0 && threadIdx.x < (ex.tab_words & 3))
+      ex.tab[(n4 << 2) + threadIdx.x] = 0u;
+  }
+}
+
 __device__ __forceinline__ void expand_tail(const ExpandTail& ex) {
+  if (ex.prefix) {
+    expand_tail_packed(ex);
+    return;
+  }
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ex.n;
        i += (int64_t)gridDim.x * kBlock) {
     const uint32_t f = ex.first[i];
     ex.out_size[i] = ex.size[f];
-    ex.out_off[i] = ex.prefix ? ex.prefix[f >> ex.shift] + ex.off[f] : ex.off[f];
+    ex.out_off[i] = ex.off[f];
     if (f == (uint32_t)i && ex.tab) ex.tab[ex.cslot[i]] = 0u;
   }
 }
@@ -1019,7 +1087,8 @@ __device__ __forceinline__ void expand_tail(const ExpandTail& ex) {
 // the `head_ptr` slot) and is copied only when it ends within `cap`; the bytes between a
 // segment's end and the next segment's start are left untouched (gaps, headers written
 // by someone else), and segments past `cap` are dropped instead of the whole copy.
-// Mode 4: mode 0 with BlockedOff segment offsets (`dst_off` block-local, ex.prefix/shift).
+// Mode 4: mode 0 with BlockedOff segment offsets (`dst_off`: the blocked lookup's packed
+// rows, ex.prefix/shift); src_off is read only for segments that hold bytes.
 // Mode 3: mode 0 with the segment count read from the device word `head_ptr` points at
 // (a plan whose segment list the GPU built: no host read of its length).
 // Mode 1 (SET log write): w < 32 synthesises the ItemHeader, else value bytes from
@@ -1091,8 +1160,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
     }
     const int cnt = (int)min((int64_t)TSC, jb - j0 + 1);
     __syncthreads();  // previous pass done with s_off / s_src (and s_lo read above)
-    for (int k = threadIdx.x; k <= cnt; k += kBlock) s_off[k] = doff[j0 + k];
-    for (int k = threadIdx.x; k < cnt; k += kBlock) s_src[k] = src_off[j0 + k];
+    if constexpr (MODE == 4) {
+      // one read of a segment's packed row gives its offset and whether it holds bytes: the
+      // source of an empty segment (a miss, or a duplicate request) is never read
+      for (int k = threadIdx.x; k <= cnt; k += kBlock) {
+        const int64_t j = j0 + k;
+        if (j < n) {
+          const uint64_t p = dst_off[j];
+          s_off[k] = ex.prefix[j >> ex.shift] + (p >> kPackBits);
+          if (k < cnt) s_src[k] = (p & kPackSizeMask) ? src_off[j] : kSegSkip;
+        } else {
+          s_off[k] = total;
+          if (k < cnt) s_src[k] = kSegSkip;
+        }
+      }
+    } else {
+      for (int k = threadIdx.x; k <= cnt; k += kBlock) s_off[k] = doff[j0 + k];
+      for (int k = threadIdx.x; k < cnt; k += kBlock) s_src[k] = src_off[j0 + k];
+    }
     if (MODE == 2)
       for (int k = threadIdx.x; k < cnt; k += kBlock) {
         const uint64_t st = dst_off[j0 + k], ln = seg_len[j0 + k];
@@ -3581,6 +3666,12 @@ int HbmCache::lookup_coalesced(const Digest* keys, int64_t n, uint32_t* table,
   SH_CHECK(n < (1ll << 31), "coalesce: batch too large");
   SH_CHECK(table_slots >= 2 * n && (table_slots & (table_slots - 1)) == 0,
            "coalesce: table needs a power of two >= 2n slots");
+  // a packed row: the record bytes in kPackBits bits, the rest for the offset within a
+  // lookup workgroup's rows — at most 2^31 / kMaxGrid = 2^20 rows of such records
+  static_assert(kMaxGrid == 2048 && 20 + kPackBits <= 64 - kPackBits,
+                "packed rows: a workgroup's local offsets must fit 64 - kPackBits bits");
+  SH_CHECK(!prefix || item_bytes(cfg_.max_item) <= kPackSizeMask,
+           "blocked lookup: a record of max_item bytes does not fit a packed row");
   std::lock_guard<std::mutex> lk(mu_);
   DeviceGuard g(cfg_.device);
   uint64_t* ht = total_slot >= 0 ? host_slots_ + total_slot : nullptr;
@@ -3791,7 +3882,7 @@ void HbmCache::gather(const uint64_t* loc, const uint64_t* off, int64_t n, uint8
                       hipStream_t s, uint64_t out_cap, const uint32_t* first,
                       const uint64_t* size, uint64_t* out_size, uint64_t* out_off,
                       uint32_t* table, const uint32_t* cslot, const uint64_t* prefix,
-                      int shift) {
+                      int shift, int64_t table_slots) {
   TraceRange tr("hbm.gather");
   DeviceGuard g(cfg_.device);
   if (n <= 0) return;
@@ -3799,6 +3890,11 @@ void HbmCache::gather(const uint64_t* loc, const uint64_t* off, int64_t n, uint8
   if (first) ex = ExpandTail{first, n, size, off, out_size, out_off, table, cslot};
   ex.prefix = prefix;
   ex.shift = shift;
+  if (prefix && first && table) {
+    SH_CHECK(table_slots > 0 && ((uintptr_t)table & 15) == 0,
+             "gather: a blocked lookup's table is cleared whole (16-byte aligned, its slots)");
+    ex.tab_words = table_slots;
+  }
   if (prefix)  // block-local offsets (lookup_coalesced with a prefix)
     launch_segcopy_ex<4>(s, ex, log_, loc, off, n, out, nullptr, nullptr, nullptr, nullptr,
                          nullptr, out_cap);

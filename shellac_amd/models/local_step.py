@@ -303,7 +303,7 @@ class LocalStep:
     # ---- buffers -----------------------------------------------------------------
     def _coalesce_table(self, n: int) -> torch.Tensor:
         """Persistent, zeroed GET-coalescing table (every serve step leaves it zeroed: the
-        gather's expand tail clears the slots its batch claimed). Coalescing the next batch
+        gather's expand tail zeroes it whole with streaming stores). Coalescing the next batch
         under this step's gather on a third stream (two tables, ping-pong) was measured
         slower, 0.35 vs 0.30 ms/step: both passes compete for the same memory system."""
         slots = int(_core().coalesce_table_slots(n))

@@ -234,13 +234,16 @@ def _stop_handle(ev) -> int:
 @dataclass
 class Lookup:
     loc: torch.Tensor   # int64 [n]  physical log offset (MISS_LOC as -1 on miss)
-    size: torch.Tensor  # int64 [n+1] response bytes per key (0 = miss); size[n] = 0
+    # int64 [n+1] response bytes per key (0 = miss); size[n] = 0. None for a blocked lookup
+    size: Optional[torch.Tensor]
     # the offsets buffer as the lookup wrote it: the exclusive scan of size (off_raw[n] =
-    # total bytes), or, for a blocked lookup (lookup_coalesced(blocked=True)), row i's
-    # offset within its lookup workgroup's rows [b << shift, (b + 1) << shift) with
-    # off_raw[n] unwritten, `prefix[b]` the bytes of the workgroups before b (prefix[last +
-    # 1] = the total). Read it through `off`, which refuses a blocked lookup: only gather()
-    # (with its expand tail, which writes the per-request offsets) reads those.
+    # total bytes), or, for a blocked lookup (lookup_coalesced(blocked=True)), one packed
+    # word per row: (row i's offset within its lookup workgroup's rows [b << shift, (b + 1)
+    # << shift)) << 21 | its record bytes, 0 bytes for a miss or a duplicate request, with
+    # off_raw[n] unwritten and `loc` written for claiming rows only; `prefix[b]` is the bytes
+    # of the workgroups before b (prefix[last + 1] = the total). Read it through `off`, which
+    # refuses a blocked lookup: only gather() (with its expand tail, which writes the
+    # per-request sizes and offsets) reads those.
     off_raw: torch.Tensor
     prefix: Optional[torch.Tensor] = None
     shift: int = 0
@@ -382,10 +385,12 @@ class CacheShard:
         cslot); duplicate rows have size 0 until ``expand(first, lk.size, lk.off)`` runs
         after the gather. ``table``: a caller-owned, zeroed coalescing table (int32,
         >= ``coalesce_table_slots(n)`` power-of-two slots) — then ``cslot`` holds each
-        claimer's slot and ``expand_out`` must run to clean the table again; otherwise
+        claimer's slot and ``expand_out`` must run to clean the table again (blocked:
+        ``cslot`` is None and the gather's expand tail zeroes the whole table); otherwise
         a temporary table is zeroed here and ``cslot`` is None. ``blocked`` (GPU): the
-        Lookup holds block-local offsets (``Lookup.prefix``), which only ``gather`` with an
-        ``expand`` tail reads — no n-row offsets scan between the lookup and the gather.
+        Lookup holds packed rows of block-local offsets and sizes (``Lookup.prefix``, no
+        ``size``), which only ``gather`` with an ``expand`` tail reads — no n-row offsets
+        scan between the lookup and the gather.
         ``index_done`` (GPU, a ``StreamEvent``): completes with the kernel that reads the
         index, as that kernel's own completion signal (a SET's ``index_after``).
         CPU shards: a plain lookup, ``first = cslot = None``."""
@@ -395,6 +400,7 @@ class CacheShard:
         c = core()
         n = keys.shape[0]
         cslot = None
+        table_clean = False
         if table is None:
             slots = int(c.coalesce_table_slots(n))
             table = torch.empty(slots, dtype=torch.int32, device=self.device)
@@ -402,20 +408,24 @@ class CacheShard:
             slots = table.numel()
             if slots < int(c.coalesce_table_slots(n)) or slots & (slots - 1):
                 raise ValueError("coalescing table too small or not a power of two")
-            cslot = torch.empty(n, dtype=torch.int32, device=self.device)
+            table_clean = True
+            if not blocked:  # (a blocked lookup's gather zeroes the whole table: no cslot)
+                cslot = torch.empty(n, dtype=torch.int32, device=self.device)
         first = torch.empty(n, dtype=torch.int32, device=self.device)
         loc = torch.empty(n, dtype=torch.int64, device=self.device)
-        size = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        # (a blocked lookup packs each row's size into its offset word: no size array)
+        size = None if blocked else torch.empty(n + 1, dtype=torch.int64, device=self.device)
         off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         now = self.now() if now is None else now
         prefix = (torch.empty(int(c.LOOKUP_PREFIX_WORDS), dtype=torch.int64, device=self.device)
                   if blocked else None)
         shift = self._impl.lookup_coalesced(keys.data_ptr(), n, table.data_ptr(), slots,
-                                            first.data_ptr(), loc.data_ptr(), size.data_ptr(),
+                                            first.data_ptr(), loc.data_ptr(),
+                                            size.data_ptr() if size is not None else 0,
                                             off.data_ptr(), now, self._s(), int(reserve_bytes),
                                             int(total_slot),
                                             cslot.data_ptr() if cslot is not None else 0,
-                                            cslot is not None,
+                                            table_clean,
                                             prefix.data_ptr() if prefix is not None else 0,
                                             _stop_handle(index_done))
         return Lookup(loc, size, off, prefix, max(int(shift), 0)), first, cslot
@@ -469,24 +479,28 @@ class CacheShard:
         ``out_cap`` (GPU): the kernel writes nothing when off[n] exceeds it, so a gather
         can be queued before the total is known. ``expand`` (GPU, a coalesced lookup):
         (first, out_size, out_off, table, cslot) — the gather also writes every request's
-        (size, off) from its claimer and clears the coalescing table (``expand_out``)."""
+        (size, off) from its claimer and clears the coalescing table (``expand_out``: the
+        claimers' ``cslot`` slots, or for a blocked lookup the whole table)."""
         if out is None:
             total = int(lk.total().item()) if total is None else total
             out = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
         self._check(out, "out")
         if self.is_gpu:
             cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
-            ex = [0] * 6
+            ex, slots = [0] * 6, 0
             if expand is not None:
                 first, osz, ooff, table, cslot = expand
-                ex = [first.data_ptr(), lk.size.data_ptr(), osz.data_ptr(), ooff.data_ptr(),
+                ex = [first.data_ptr(), lk.size.data_ptr() if lk.size is not None else 0,
+                      osz.data_ptr(), ooff.data_ptr(),
                       table.data_ptr() if table is not None else 0,
                       cslot.data_ptr() if cslot is not None else 0]
+                slots = table.numel() if table is not None else 0
             elif lk.prefix is not None:
                 raise ValueError("a blocked lookup's offsets are read only with an expand tail")
             self._impl.gather(lk.loc.data_ptr(), lk.off_raw.data_ptr(), lk.n, out.data_ptr(),
                               self._s(), cap, *ex,
-                              lk.prefix.data_ptr() if lk.prefix is not None else 0, lk.shift)
+                              lk.prefix.data_ptr() if lk.prefix is not None else 0, lk.shift,
+                              slots)
         else:
             self._impl.gather(lk.loc.data_ptr(), lk.off.data_ptr(), lk.n, out.data_ptr())
         return out
