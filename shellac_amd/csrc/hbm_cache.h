@@ -363,8 +363,7 @@ class HbmCache {
   // (phase 1) may run while the previous batch's append and index insert still use theirs.
   // The dd_* / set_* members below point at the one in use (select_ws).
   struct SetWs {
-    uint64_t* dd_keys = nullptr;
-    int* dd_win = nullptr;
+    uint32_t* dd_tab = nullptr;   // dedupe table: 0 = empty, else the key's last row + 1
     uint32_t* dd_slot = nullptr;
     uint64_t *set_size = nullptr, *set_off = nullptr, *set_cnt = nullptr;
     uint32_t* set_claim = nullptr;
@@ -373,7 +372,7 @@ class HbmCache {
   int ws_next_ = 0;
   void select_ws(int p) {
     const SetWs& w = ws_[p];
-    dd_keys_ = w.dd_keys; dd_win_ = w.dd_win; dd_slot_ = w.dd_slot; set_size_ = w.set_size;
+    dd_tab_ = w.dd_tab; dd_slot_ = w.dd_slot; set_size_ = w.set_size;
     set_off_ = w.set_off; set_cnt_ = w.set_cnt; set_claim_ = w.set_claim;
   }
 
@@ -408,8 +407,7 @@ class HbmCache {
   unsigned long long* lb_state_ = nullptr;  // device: edge-GET look-back words (self-resetting)
   // SET workspace
   int64_t set_cap_ = 0;
-  uint64_t* dd_keys_ = nullptr;
-  int* dd_win_ = nullptr;
+  uint32_t* dd_tab_ = nullptr;
   uint32_t* dd_slot_ = nullptr;
   uint64_t* set_size_ = nullptr;
   uint64_t* set_off_ = nullptr;

@@ -16,8 +16,9 @@
 //                  in LDS) and every lane moves 16 x 16 B, so item-size skew
 //                  never idles lanes. Used for GET gathers, SET log writes and
 //                  packing SET payloads for the all-to-all.
-//   k_set_dedupe   batch-local open-addressing table: the last SET of a key in a
-//                  batch wins (request order = memcached/HTTP pipelining order).
+//   k_set_dedupe   batch-local open-addressing table, one word per slot (the key's
+//                  last row + 1; the key is read through that row): the last SET of a
+//                  key in a batch wins (request order = memcached/HTTP pipelining order).
 //   k_set_copy     load-balanced writer of [ItemHeader|value] into the log at
 //                  head + exclusive-scan(item sizes): batch allocation is a scan.
 //   k_set_index    4 lanes per key: two-choice insert with a 64-bit CAS on the
@@ -26,7 +27,8 @@
 //                  workgroup 0 publishes the new log head into the other of two
 //                  ping-pong head slots, and every item resets its dedupe slot.
 //   k_set_fixup    rewrites the digest words of entries a later insert of the same
-//                  batch re-claimed (the CAS arbitrates loc only).
+//                  batch re-claimed (the CAS arbitrates loc only); it stores only the
+//                  words that differ, so an entry that is already right stays clean.
 //   All per-op counters are block-reduced and added to one of 64 counter
 //   shards (one atomic per block per field; same-address fan-in measured at
 //   ~12 ns/atomic would otherwise serialise a 64K-wave probe into milliseconds).
@@ -1824,7 +1826,7 @@ __global__ __launch_bounds__(kSrvBlock) void k_edge_server(
 // ---------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(kBlock) void k_set_size(const uint32_t* __restrict__ vlen, int64_t n,
-                                                     const int* __restrict__ tw,
+                                                     const uint32_t* __restrict__ tw,
                                                      const uint32_t* __restrict__ slot_of,
                                                      uint32_t max_item,
                                                      uint64_t* __restrict__ size,
@@ -1837,7 +1839,7 @@ __global__ __launch_bounds__(kBlock) void k_set_size(const uint32_t* __restrict_
   const int64_t i1 = min(n, (int64_t)(blockIdx.x + 1) * plen);
   for (int64_t i = (int64_t)blockIdx.x * plen + threadIdx.x; i < i1; i += kBlock) {
     if (vlen[i] == kSkipVlen) { size[i] = 0; continue; }  // row addressed to another tier
-    const bool win = tw[slot_of[i]] == (int)i && vlen[i] <= max_item;
+    const bool win = tw[slot_of[i]] == (uint32_t)i + 1u && vlen[i] <= max_item;
     const uint64_t sz = win ? item_bytes(vlen[i]) : 0;
     size[i] = sz;
     psum += sz;
@@ -2072,8 +2074,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
     const uint64_t* __restrict__ off, const uint32_t* __restrict__ vlen,
     const uint32_t* __restrict__ expire, Entry* __restrict__ index, uint64_t mask,
     const uint64_t* __restrict__ head_ptr, uint64_t* __restrict__ head_next, uint64_t cap,
-    uint32_t now, const uint32_t* __restrict__ slot_of, unsigned long long* __restrict__ dd_keys,
-    int* __restrict__ dd_win, CacheCounters* __restrict__ ctr, uint32_t* __restrict__ claim,
+    uint32_t now, const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ dd_tab,
+    CacheCounters* __restrict__ ctr, uint32_t* __restrict__ claim,
     const uint64_t* __restrict__ from, int64_t r0, int64_t r1,
     const unsigned long long* __restrict__ r1_dev) {
   // r1_dev: the combined batch's effective hand window (rows past it are skip rows)
@@ -2086,11 +2088,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
   unsigned long long evicted = 0, bytes = 0, lost = 0, moved_away = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) *head_next = head_new;
   for (int64_t i = r0 + (((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 2); i < r1; i += ngroups) {
-    if (l4 == 0 && vlen[i] != kSkipVlen) {  // leave the dedupe table clean for the next batch
-      const uint32_t sl = slot_of[i];
-      dd_keys[sl] = 0ull;
-      dd_win[sl] = -1;
-    }
+    // leave the dedupe table clean for the next batch
+    if (l4 == 0 && vlen[i] != kSkipVlen) dd_tab[slot_of[i]] = 0u;
     if (l4 == 0) claim[i] = ~0u;  // no entry (yet)
     if (size[i] == 0) continue;   // uniform across the 4-lane group
     const Digest d = keys[i];
@@ -2266,7 +2265,8 @@ __device__ void deferred_insert(const Digest& d, uint64_t myloc, uint64_t myword
 
 // After k_set_index (kernel boundary: every CAS and word write is visible): each entry
 // whose loc is still the one a row of this batch claimed gets that row's digest and
-// vlen|expire words again, so no entry pairs one key's digest with another key's loc.
+// vlen|expire words again where they are not already its own, so no entry pairs one key's
+// digest with another key's loc.
 // Rows k_set_index deferred (kClaimDeferred: all 8 slots of the pair live) are inserted
 // here first, by deferred_insert.
 __global__ __launch_bounds__(kBlock) void k_set_fixup(
@@ -2308,10 +2308,16 @@ __global__ __launch_bounds__(kBlock) void k_set_fixup(
     if (c == ~0u) continue;
     Entry* const e = index + c;
     if (e->loc != base + off[i] + 1) continue;  // evicted again within the batch
+    // the words are wrong only where the claim was taken away and retaken inside the batch:
+    // they share the loc's 32-byte entry (no further request), and storing only what differs
+    // leaves the sector clean otherwise. A lookup may have set kRefBit meanwhile: it stays.
     const Digest d = keys[i];
-    e->d0 = d.lo;
-    e->d1 = d.hi;
-    *reinterpret_cast<uint64_t*>(&e->vlen) = pack2(vlen[i], expire ? expire[i] : 0u);
+    uint64_t* const ew = reinterpret_cast<uint64_t*>(&e->vlen);
+    const uint64_t w = pack2(vlen[i], expire ? expire[i] : 0u);
+    const uint64_t e0 = e->d0, e1 = e->d1, e3 = *ew;
+    if (e0 != d.lo) e->d0 = d.lo;
+    if (e1 != d.hi) e->d1 = d.hi;
+    if ((e3 & ~(uint64_t)kRefBit) != w) *ew = w;
   }
   block_count(ctr, evicted, &CacheCounters::set_evicted, lost, &CacheCounters::set_dropped, bytes,
               &CacheCounters::set_bytes);
@@ -2878,12 +2884,15 @@ __device__ __forceinline__ void rc_advance(const RcAdvance& r) {
   r.ctl[4] = consumed;  // the next batch's window (hand_window_eff)
 }
 
-// SET dedupe (last writer of a digest wins). `adv`: the CLOCK hand step before this batch
-// (k_rc_emit) left its cut in the control words; block 0 advances the hand.
+// SET dedupe (last writer of a digest wins). One word per table slot: 0 when empty, else
+// row + 1 of the last row so far that holds the slot's key — the key itself is read through
+// that row (every row that raises the word holds the same key, so whichever row a prober
+// finds there answers for the slot). A row without a duplicate costs one atomic.
+// `adv`: the CLOCK hand step before this batch (k_rc_emit) left its cut in the control
+// words; block 0 advances the hand.
 __global__ __launch_bounds__(kBlock) void k_set_dedupe(const Digest* __restrict__ keys,
                                                        const uint32_t* __restrict__ vlen, int64_t n,
-                                                       unsigned long long* __restrict__ tk,
-                                                       int* __restrict__ tw, uint32_t tmask,
+                                                       uint32_t* __restrict__ tw, uint32_t tmask,
                                                        uint32_t* __restrict__ slot_of,
                                                        RcAdvance adv) {
   if (adv.ctl && blockIdx.x == 0 && threadIdx.x == 0) rc_advance(adv);
@@ -2893,9 +2902,15 @@ __global__ __launch_bounds__(kBlock) void k_set_dedupe(const Digest* __restrict_
     const unsigned long long key = keys[i].lo ? keys[i].lo : 1ull;
     uint32_t s = (uint32_t)fmix64(key) & tmask;
     for (uint32_t probe = 0; probe <= tmask; ++probe) {
-      const unsigned long long prev = atomicCAS(&tk[s], 0ull, key);
-      if (prev == 0ull || prev == key) {
-        atomicMax(&tw[s], (int)i);
+      const uint32_t prev = atomicCAS(&tw[s], 0u, (uint32_t)i + 1u);
+      if (prev == 0u) {
+        slot_of[i] = s;
+        break;
+      }
+      // (prev <= n: a word of this batch; anything else is never read through)
+      const unsigned long long ok = prev <= (uint32_t)n ? keys[prev - 1].lo : 0ull;
+      if (prev <= (uint32_t)n && (ok ? ok : 1ull) == key) {
+        atomicMax(&tw[s], (uint32_t)i + 1u);
         slot_of[i] = s;
         break;
       }
@@ -3383,7 +3398,7 @@ HbmCache::~HbmCache() {
   (void)hipHostFree(host_buf_);
   (void)hipHostFree(host_slots_);
   for (SetWs& w : ws_)
-    for (void* p : {(void*)w.dd_keys, (void*)w.dd_win, (void*)w.dd_slot, (void*)w.set_size,
+    for (void* p : {(void*)w.dd_tab, (void*)w.dd_slot, (void*)w.set_size,
                     (void*)w.set_off, (void*)w.set_claim, (void*)w.set_cnt})
       (void)hipFree(p);
   (void)hipFree(ring_); (void)hipFree(rc_ctl_);
@@ -3567,16 +3582,14 @@ void HbmCache::ensure_set_ws(int64_t n, hipStream_t s) {
   for (SetWs& w : ws_) {
     // the old workspace may still be read by queued SET chains on other streams: retired
     // until their events say they finished (no device synchronisation on the serving path)
-    retire_group({w.dd_keys, w.dd_win, w.dd_slot, w.set_size, w.set_off, w.set_claim, w.set_cnt},
-                 2 * oc * 12 + oc * 8 + 3 * (oc + 1) * 8, s);
-    HIP_OK(hipMalloc(&w.dd_keys, tslots * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(&w.dd_win, tslots * sizeof(int)));
-    // the tables are cleared once here, on the stream of the SET that first uses them
+    retire_group({w.dd_tab, w.dd_slot, w.set_size, w.set_off, w.set_claim, w.set_cnt},
+                 2 * oc * 4 + oc * 8 + 3 * (oc + 1) * 8, s);
+    HIP_OK(hipMalloc(&w.dd_tab, tslots * sizeof(uint32_t)));
+    // the table is cleared once here, on the stream of the SET that first uses it
     // (ordered before its dedupe; the null stream is not: a non-blocking stream does not
     // wait for it, which once dropped the first batch's rows); k_set_index resets every
     // slot a batch used
-    HIP_OK(hipMemsetAsync(w.dd_keys, 0, tslots * sizeof(uint64_t), s));
-    HIP_OK(hipMemsetAsync(w.dd_win, 0xff, tslots * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(w.dd_tab, 0, tslots * sizeof(uint32_t), s));
     HIP_OK(hipMalloc(&w.dd_slot, cap * sizeof(uint32_t)));
     HIP_OK(hipMalloc(&w.set_size, (cap + 1) * sizeof(uint64_t)));
     HIP_OK(hipMalloc(&w.set_off, (cap + 1) * sizeof(uint64_t)));
@@ -4054,10 +4067,10 @@ void HbmCache::store_plan_locked(const Digest* keys, const uint32_t* vlen, int64
     rc_adv_w_ = 0;
   }
   hipLaunchKernelGGL(k_set_dedupe, dim3(grid), dim3(kBlock), 0, s, keys, vlen, n,
-                     (unsigned long long*)dd_keys_, dd_win_, dd_mask_, dd_slot_, adv);
+                     dd_tab_, dd_mask_, dd_slot_, adv);
   const int sgrid = grid_for(n, kBlock, kMaxGrid);
   uint64_t* part_cnt = ring_ ? part_ + 2 * kMaxGrid : nullptr;
-  hipLaunchKernelGGL(k_set_size, dim3(sgrid), dim3(kBlock), 0, s, vlen, n, dd_win_, dd_slot_,
+  hipLaunchKernelGGL(k_set_size, dim3(sgrid), dim3(kBlock), 0, s, vlen, n, dd_tab_, dd_slot_,
                      cfg_.max_item, set_size_, ctr_, part_ + kMaxGrid, part_cnt);
   HIP_OK(hipGetLastError());
   launch_offsets(set_size_, n, part_ + kMaxGrid, sgrid, set_off_, s, nullptr, 0, part_cnt,
@@ -4081,8 +4094,8 @@ void HbmCache::store_index_locked(const Digest* keys, const uint32_t* vlen,
     const int igrid = grid_for((r1 - r0) * 4, kBlock, kMaxGrid);
     hipLaunchKernelGGL(k_set_index, dim3(igrid), dim3(kBlock), 0, s, keys, n, set_size_, set_off_,
                        vlen, expire, index_, cfg_.nbuckets - 1, cur_head(), next_head(),
-                       cfg_.log_bytes, now, dd_slot_, (unsigned long long*)dd_keys_, dd_win_,
-                       ctr_, set_claim_, pass ? (const uint64_t*)nullptr : from, r0, r1,
+                       cfg_.log_bytes, now, dd_slot_, dd_tab_, ctr_, set_claim_,
+                       pass ? (const uint64_t*)nullptr : from, r0, r1,
                        pass || win_parity < 0 ? nullptr : rc_ctl_ + 5 + win_parity);
   }
   launch_stop(&stop_ev_, k_set_fixup, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), s, keys,
