@@ -92,6 +92,12 @@ void DramBackend::del(const std::string& key, const Digest& d, Executor*, DelCal
   if (done) done(found);
 }
 
+void DramBackend::purge_prefix(const std::string& prefix, Executor*, PurgeCallback done) {
+  // (an empty prefix is flush(), not a purge: refused, as by every tier)
+  const int64_t n = prefix.empty() ? -1 : (int64_t)cache_.purge_prefix(prefix, now());
+  if (done) done(n);
+}
+
 void DramBackend::flush() { cache_.clear(); }
 
 void DramBackend::stats(StatList* out) {
@@ -122,22 +128,29 @@ void TieredBackend::get(const std::string& key, const Digest& d, Executor* ex, G
   // made every reactor thread bump the same two reference counts (c=10 hit path:
   // 666K -> see docs/PERF.md).
   CacheBackend* l2 = l2_.get();
-  l1_->get(key, d, ex, [this, key, d, ex, l2, done = std::move(done)](bool hit,
-                                                                      CacheValue v) mutable {
+  const uint64_t epoch = purge_epoch_.load(std::memory_order_acquire);
+  l1_->get(key, d, ex, [this, key, d, ex, l2, epoch, done = std::move(done)](bool hit,
+                                                                             CacheValue v) mutable {
     if (hit) {
       l1_hits_.fetch_add(1, std::memory_order_relaxed);
       done(true, std::move(v));
       return;
     }
-    l2->get(key, d, ex, [this, key, d, done = std::move(done)](bool hit2, CacheValue v2) {
+    l2->get(key, d, ex, [this, key, d, epoch, done = std::move(done)](bool hit2, CacheValue v2) {
       if (hit2 && v2.data) {
         l2_hits_.fetch_add(1, std::memory_order_relaxed);
         if (v2.data->size() <= promote_max_) {
           // promote with the L2 entry's remaining TTL (0 = no expiry, -1 = unknown)
           const uint32_t ttl = v2.ttl_left > 0 ? (uint32_t)v2.ttl_left
                                                : (v2.ttl_left == 0 ? 0u : promote_ttl_);
-          l1_->set(key, d, v2.data, v2.flags, ttl);
-          promoted_.fetch_add(1, std::memory_order_relaxed);
+          // ...unless a purge ran since this GET started: the hit may be a purged object
+          std::shared_lock<std::shared_mutex> lk(promote_mu_);
+          if (purge_epoch_.load(std::memory_order_acquire) == epoch) {
+            l1_->set(key, d, v2.data, v2.flags, ttl);
+            promoted_.fetch_add(1, std::memory_order_relaxed);
+          } else {
+            promote_dropped_.fetch_add(1, std::memory_order_relaxed);
+          }
         } else {
           not_promoted_.fetch_add(1, std::memory_order_relaxed);
         }
@@ -155,11 +168,31 @@ void TieredBackend::set(const std::string& key, const Digest& d, Bytes value, ui
   l1_->set(key, d, std::move(value), flags, ttl_s);
 }
 
+// L2 first, then L1, with the purge epoch moved in between (as purge_prefix): a GET that hit
+// the object in L2 before it was deleted there cannot promote it into L1 after the L1 delete.
 void TieredBackend::del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) {
-  auto l2 = l2_;
-  l1_->del(key, d, ex, [key, d, ex, done, l2](bool f1) {
-    l2->del(key, d, ex, [done, f1](bool f2) {
+  l2_->del(key, d, ex, [this, key, d, ex, done](bool f2) {
+    move_purge_epoch();
+    l1_->del(key, d, ex, [done, f2](bool f1) {
       if (done) done(f1 || f2);
+    });
+  });
+}
+
+void TieredBackend::move_purge_epoch() {
+  std::unique_lock<std::shared_mutex> lk(promote_mu_);  // (waits for promotions under way)
+  purge_epoch_.fetch_add(1, std::memory_order_acq_rel);
+}
+
+void TieredBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->purge_prefix(prefix, ex, [this, prefix, ex, done = std::move(done)](int64_t n2) {
+    // L2 holds none of the objects now: a GET that starts after this move finds nothing
+    // there, and one that hit earlier has its promotion dropped, or landed it in L1 before
+    // the pass below
+    move_purge_epoch();
+    l1_->purge_prefix(prefix, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });
 }
@@ -175,6 +208,8 @@ void TieredBackend::stats(StatList* out) {
   out->emplace_back("tier_misses", misses_.load());
   out->emplace_back("tier_promoted", promoted_.load());
   out->emplace_back("tier_not_promoted_large", not_promoted_.load());
+  out->emplace_back("tier_purges", purges_.load());
+  out->emplace_back("tier_promote_dropped_purge", promote_dropped_.load());
   StatList a, b;
   l1_->stats(&a);
   l2_->stats(&b);

@@ -23,6 +23,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -59,6 +60,8 @@ struct CacheValue {
 };
 using GetCallback = std::function<void(bool hit, CacheValue v)>;
 using DelCallback = std::function<void(bool found)>;
+// Prefix purge: objects removed, or -1 if the tier cannot scan its keys.
+using PurgeCallback = std::function<void(int64_t removed)>;
 using StatList = std::vector<std::pair<std::string, uint64_t>>;
 
 // Asynchronous body compressor for the proxy's -z path: `done` runs on the compressor's
@@ -88,6 +91,17 @@ class CacheBackend {
   virtual void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
                    uint32_t ttl_s) = 0;
   virtual void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) = 0;
+  // Invalidation: remove every object whose key starts with `prefix`. `done` runs once, on
+  // `ex`'s thread (inline for synchronous backends), with the number of objects removed, or
+  // -1 where the tier cannot do it (the default: a tier that cannot enumerate its keys, e.g.
+  // memcached) and for an empty prefix, which every tier refuses (that is flush()). Objects stored before the call are gone
+  // when `done` runs; GETs racing the purge may still hit until then.
+  virtual void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
+    (void)prefix;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
   virtual void flush() = 0;
   virtual std::string name() const = 0;
   virtual void stats(StatList* out) = 0;
@@ -135,6 +149,7 @@ class DramBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
+  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
   void flush() override;
   std::string name() const override { return "dram"; }
   void stats(StatList* out) override;
@@ -224,6 +239,7 @@ class HbmBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
+  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
   void flush() override;
   std::string name() const override { return "hbm"; }
   // peer path chosen for src -> dst: 0 same device, 1 direct (peer access), 2 staged
@@ -235,8 +251,16 @@ class HbmBackend : public CacheBackend {
   void direct_detach() override;
 
   struct HotFill;
+  // One purge_prefix call fanned out over the shards: each shard's kind-5 request adds what
+  // its scan removed when its flight is reaped; the last one to finish (or fail) answers.
+  struct Purge {
+    std::atomic<int> left{0};
+    std::atomic<int64_t> removed{0};
+    Executor* ex = nullptr;
+    PurgeCallback cb;
+  };
   struct Req {
-    int kind;  // 0 get, 1 set, 2 del, 3 barrier, 4 hot-replica fill
+    int kind;  // 0 get, 1 set, 2 del, 3 barrier, 4 hot-replica fill, 5 prefix purge
     Digest d;
     std::string key;
     Bytes value;
@@ -248,6 +272,7 @@ class HbmBackend : public CacheBackend {
     // the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
     std::shared_ptr<HotFill> fill;
+    std::shared_ptr<Purge> purge;  // kind 5 (`key` holds the prefix)
   };
   struct Dev;
   struct Direct;
@@ -255,6 +280,12 @@ class HbmBackend : public CacheBackend {
   // with spreading off.
   StatList hot_refresh() override;
   bool hot_spreading() const { return hot_on_; }
+  // Tests: `fn` runs once, on the refreshing thread, in the next refresh that gets as far as
+  // its fills: after the owners' records have been snapshot, before any fill is queued.
+  void debug_before_fill(std::function<void()> fn) {
+    std::lock_guard<std::mutex> lk(hot_mu_);
+    before_fill_ = std::move(fn);
+  }
   // reactor contexts (host slots kDirectSlot0 + kDirectJobs * context + job)
   static constexpr int kDirectJobs = 2, kDirectSlot0 = 32, kDirectMax = 15;
 
@@ -296,6 +327,10 @@ class HbmBackend : public CacheBackend {
   std::atomic<uint64_t> up_mask_{0};  // bit i: shard i serves requests
   double epoch_;
   std::atomic<uint64_t> no_shard_misses_{0};
+  // purge_prefix calls begun / answered: a warm restore that overlapped one may have copied
+  // objects a peer had not purged yet, and flushes the restored shard again
+  std::atomic<uint64_t> purge_started_{0}, purge_done_{0};
+  void purge_finish(const std::shared_ptr<Purge>& p);
   // ---- hot-object spreading (hot_refresh_locked documents the protocol)
   std::unique_ptr<HostRouter> router_;  // ketama owners + the published hot table
   bool hot_on_ = false;
@@ -308,6 +343,7 @@ class HbmBackend : public CacheBackend {
   };
   std::unique_ptr<SampleStripe[]> samples_;
   std::mutex hot_mu_;  // one refresh at a time; guards the refresh state below
+  std::function<void()> before_fill_;  // debug_before_fill
   struct DigestHash {
     size_t operator()(const Digest& d) const { return (size_t)(d.lo ^ (d.hi * 0x9E3779B97F4A7C15ull)); }
   };
@@ -347,6 +383,10 @@ class TieredBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
+  // L2 first, then L1; the sum, or -1 if either level cannot purge. A GET that hit L2 before
+  // the purge does not promote its object into L1 after L1 was purged (purge_epoch_; del()
+  // does the same for one key).
+  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
   void flush() override;
   std::string name() const override { return l1_->name() + "+" + l2_->name(); }
   void stats(StatList* out) override;
@@ -371,6 +411,14 @@ class TieredBackend : public CacheBackend {
   uint64_t promote_max_;
   std::atomic<uint64_t> promoted_{0}, not_promoted_{0};
   std::atomic<uint64_t> l1_hits_{0}, l2_hits_{0}, misses_{0};
+  // Purge epoch: moved between the L2 and the L1 pass of a purge or a delete. A GET reads it
+  // when it starts and promotes its L2 hit (check + L1 set under the shared lock) only if it
+  // has not moved; the move takes the lock exclusively, so a promotion either lands before
+  // the L1 pass (which removes it) or sees the new epoch and is dropped.
+  std::atomic<uint64_t> purge_epoch_{0};
+  std::shared_mutex promote_mu_;
+  std::atomic<uint64_t> purges_{0}, promote_dropped_{0};
+  void move_purge_epoch();
 };
 
 // Fault injection: a decorator that makes the wrapped tier misbehave
@@ -394,6 +442,9 @@ class FaultBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
+  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override {
+    inner_->purge_prefix(prefix, ex, std::move(done));
+  }
   void flush() override { inner_->flush(); }
   std::string name() const override { return "fault(" + inner_->name() + ")"; }
   void stats(StatList* out) override;

@@ -215,6 +215,8 @@ struct Flight {
   std::vector<uint32_t> urow;              // GET request -> GPU row (host coalescing)
   size_t rows = 0;                         // distinct GET digests
   Mapped keys, offs, set_keys, set_vals, set_voff, set_meta, del_keys, del_found;
+  // prefix purges: pattern images (keyed.h) and {removed, bytes} word pairs, one per purge
+  Mapped purge_img, purge_out;
   std::shared_ptr<ArenaPool::Arena> arena;
   std::vector<uint64_t> wkeys;  // SET / DELETE digests (lo words) counted in Dev::pend_w
   bool flush = false;           // a flush runs on the stream right before this flight
@@ -268,6 +270,9 @@ struct HbmBackend::Dev {
   std::thread th;
   // health
   std::atomic<bool> forced_down{false};
+  // a purge found this shard out of service, or the shard failed one: it may hold purged
+  // objects, so its restore flushes it whatever flush_on_restore says
+  std::atomic<bool> purge_dirty{false};
   // back in the ring and still pulling its objects from peers: GETs neither skip on the
   // presence filter nor bypass the batcher (they queue behind the migration)
   std::atomic<bool> restoring{false};
@@ -326,7 +331,8 @@ struct HbmBackend::Dev {
       key_mismatch{0}, failures{0}, ejections{0}, restores{0}, regathers{0}, arena_misses{0},
       dropped{0}, staged_copies{0}, served_batches{0}, ordered_gets{0},
       migrated{0}, migrate_ns{0}, direct_jobs{0}, direct_reqs{0}, direct_fallbacks{0},
-      direct_overflows{0}, direct_timeouts{0}, direct_ns{0};
+      direct_overflows{0}, direct_timeouts{0}, direct_ns{0}, purged_objects{0},
+      purged_bytes{0};
 
   void loop();
   bool take_batch(std::vector<Req>* out, bool* do_flush, bool* rebuilding);
@@ -353,7 +359,8 @@ struct HbmBackend::Dev {
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto& f : flights) {
       for (Mapped* m : {&f->keys, &f->offs, &f->set_keys, &f->set_vals, &f->set_voff,
-                        &f->set_meta, &f->del_keys, &f->del_found})
+                        &f->set_meta, &f->del_keys, &f->del_found, &f->purge_img,
+                        &f->purge_out})
         m->release();
       f->arena.reset();
       if (f->ev) (void)hipEventDestroy(f->ev);
@@ -631,6 +638,12 @@ void HbmBackend::enqueue(int k, Req r) {
     // a write of an object being filled into this shard: the fill must not overwrite it
     if ((r.kind == 1 || r.kind == 2) && !dv.filling.empty() && dv.filling.count(r.d.lo))
       dv.touched.insert(r.d.lo);
+    // A purge names no digests, and the records of a refresh under way were read on their
+    // owners before it: a fill queued behind it must not store them here after this shard
+    // has scanned. Every object being filled counts as written (the fill drops its rows; a
+    // replica that is missing reads as a miss and is written through again by the next SET).
+    if (r.kind == 5 && !dv.filling.empty())
+      dv.touched.insert(dv.filling.begin(), dv.filling.end());
     dv.q.push_back(std::move(r));
     dv.qn.store(dv.q.size(), std::memory_order_release);
   }
@@ -770,6 +783,59 @@ void HbmBackend::enqueue_ctl(int k, std::function<void(bool)> cb) {
   r.d = Digest{0, 0};
   r.ccb = std::move(cb);
   enqueue(k, std::move(r));
+}
+
+void HbmBackend::purge_finish(const std::shared_ptr<Purge>& p) {
+  if (p->left.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  purge_done_.fetch_add(1, std::memory_order_acq_rel);
+  if (!p->cb) return;
+  const int64_t n = p->removed.load(std::memory_order_relaxed);
+  PurgeCallback cb = std::move(p->cb);
+  if (p->ex) p->ex->post([cb = std::move(cb), n]() { cb(n); });
+  else cb(n);
+}
+
+// Every shard scans its own index (a prefix has no owner, and the hot replicas live on all
+// of them): a kind-5 request per shard in service, launched by its batcher on the shard's
+// stream behind the writes queued before it. A shard that is out of service, or fails the
+// purge, is marked so that its restore flushes it.
+void HbmBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
+  if (prefix.empty() || prefix.size() > kMaxKeyedKey) {
+    if (!done) return;
+    if (ex) ex->post([done]() { done(-1); });
+    else done(-1);
+    return;
+  }
+  purge_started_.fetch_add(1, std::memory_order_acq_rel);
+  auto p = std::make_shared<Purge>();
+  p->ex = ex;
+  p->cb = std::move(done);
+  p->left.store((int)devs_.size() + 1, std::memory_order_release);  // + this call's own hold
+  const uint64_t up = up_mask_.load(std::memory_order_acquire);
+  for (size_t k = 0; k < devs_.size(); ++k) {
+    Dev* dv = devs_[k].get();
+    if (!((up >> k) & 1)) {
+      dv->purge_dirty.store(true, std::memory_order_release);
+      // Back in service meanwhile? Its restore may have taken its last look at the flag
+      // before the store above: then it scans like the others (a request queued to a shard
+      // that is up runs after the restore, on its batcher).
+      if (!dv->up()) {
+        purge_finish(p);
+        continue;
+      }
+    }
+    Req r;
+    r.kind = 5;
+    r.d = Digest{0, 0};
+    r.key = prefix;
+    r.purge = p;
+    r.ccb = [this, p, dv](bool ok) {
+      if (!ok) dv->purge_dirty.store(true, std::memory_order_release);
+      purge_finish(p);
+    };
+    enqueue((int)k, std::move(r));
+  }
+  purge_finish(p);
 }
 
 void HbmBackend::flush() {
@@ -1018,7 +1084,9 @@ bool HbmBackend::Dev::take_batch(std::vector<Req>* out, bool* do_flush, bool* re
       const Req& r = q[i];
       if (r.kind == 1 || r.kind == 2) {
         w.insert(r.d.lo);
-      } else if (r.kind == 4) {  // a fill ends its flight (it runs after the flight's writes)
+      } else if (r.kind == 4 || r.kind == 5) {
+        // a fill or a purge ends its flight (it runs after the flight's writes, and the
+        // writes queued behind a purge must not run before it)
         take = i + 1;
         break;
       } else if (r.kind == 0 && !w.empty() && w.count(r.d.lo)) {
@@ -1308,6 +1376,33 @@ void HbmBackend::Dev::launch(Flight& f) {
     cache->store(h.okeys, h.krec, h.ovoff, h.ometa, h.ometa + h.m, h.ometa + 2 * h.m, h.m,
                  h.bound, f.tnow, stream);
   }
+  // ---- prefix purges: after the SETs and DELETEs queued before them (a purge is its
+  // flight's last request); pattern image and result words in mapped memory
+  {
+    size_t np = 0, img_bytes = 0;
+    for (uint32_t i : f.ctls)
+      if (f.reqs[i].kind == 5) {
+        ++np;
+        img_bytes += keyed_prefix_image_bytes(f.reqs[i].key.size());
+      }
+    if (np) {
+      f.purge_img.ensure(img_bytes);
+      f.purge_out.ensure(np * 16);
+      size_t off = 0, j = 0;
+      for (uint32_t i : f.ctls) {
+        const Req& r = f.reqs[i];
+        if (r.kind != 5) continue;
+        write_keyed_prefix_image(f.purge_img.host<uint8_t>() + off,
+                                 reinterpret_cast<const uint8_t*>(r.key.data()), r.key.size());
+        uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * j;
+        res[0] = res[1] = 0;
+        cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
+                                   f.tnow, f.purge_out.dev<uint64_t>() + 2 * j, stream);
+        off += keyed_prefix_image_bytes(r.key.size());
+        ++j;
+      }
+    }
+  }
   HB_OK(hipEventRecord(f.ev, stream));
   batches++;
   batched_reqs += f.reqs.size();
@@ -1363,8 +1458,17 @@ bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
   }
   if (f.active) {
     deliver_dels(f);
-    for (uint32_t i : f.ctls)
-      if (f.reqs[i].ccb) f.reqs[i].ccb(true);
+    size_t pj = 0;
+    for (uint32_t i : f.ctls) {
+      Req& r = f.reqs[i];
+      if (r.kind == 5) {  // what this shard's scan removed (the event has completed)
+        const uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * pj++;
+        purged_objects += res[0];
+        purged_bytes += res[1];
+        if (r.purge) r.purge->removed.fetch_add((int64_t)res[0], std::memory_order_relaxed);
+      }
+      if (r.ccb) r.ccb(true);
+    }
     batch_ns += (uint64_t)((wall_s() - f.t0) * 1e9);
   }
   f.active = false;
@@ -1531,11 +1635,16 @@ void HbmBackend::Dev::eject(const char* why) {
 void HbmBackend::Dev::maybe_restore() {
   if (forced_down.load(std::memory_order_acquire)) return;
   if (failed && wall_s() < retry_at) return;
+  // (done before started: equal counts mean no purge was under way when they were read)
+  const uint64_t purges_done = be->purge_done_.load(std::memory_order_acquire);
+  const uint64_t purges_begun = be->purge_started_.load(std::memory_order_acquire);
+  const bool dirty = purge_dirty.exchange(false, std::memory_order_acq_rel);
   try {
     for (auto& f : flights) HB_OK(hipEventSynchronize(f->ev));
-    if (be->cfg_.flush_on_restore) cache->flush(stream);
+    if (be->cfg_.flush_on_restore || dirty) cache->flush(stream);
     HB_OK(hipStreamSynchronize(stream));
   } catch (const std::exception&) {
+    if (dirty) purge_dirty.store(true, std::memory_order_release);
     retry_at = wall_s() + be->cfg_.retry_s;
     return;
   }
@@ -1568,6 +1677,25 @@ void HbmBackend::Dev::maybe_restore() {
         std::fprintf(stderr, "[shellac hbm] warm restore from gpu %d failed: %s\n",
                      other->device, e.what());
       }
+    }
+  }
+  // A purge that overlapped the restore found this shard out of service (purge_dirty) or
+  // reached the peers only after their objects were copied here: drop what was warmed (the
+  // requests queued since the shard is back run after this, on this thread).
+  if (purge_dirty.exchange(false, std::memory_order_acq_rel) ||
+      (moved && (purges_done != purges_begun ||
+                 be->purge_started_.load(std::memory_order_acquire) != purges_begun))) {
+    try {
+      cache->flush(stream);
+      HB_OK(hipStreamSynchronize(stream));
+      moved = 0;
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "[shellac hbm] gpu %d flush after a purge failed: %s\n", device,
+                   e.what());
+      restoring.store(false, std::memory_order_release);
+      eject("flush error");
+      purge_dirty.store(true, std::memory_order_release);
+      return;
     }
   }
   restoring.store(false, std::memory_order_release);
@@ -1945,6 +2073,18 @@ StatList HbmBackend::hot_refresh_locked() {
     dv.touched.clear();
     for (const Digest& d : fill_objs) dv.filling.insert(d.lo);
   }
+  // A purge already under way may have reached some shards before the recording began and
+  // reach the owners only after their barrier: nothing is filled this time (a purge that
+  // starts from here on marks the objects itself, in enqueue()).
+  {
+    const uint64_t done = purge_done_.load(std::memory_order_acquire);
+    if (purge_started_.load(std::memory_order_acquire) != done)
+      for (int r = 0; r < N; ++r) {
+        Dev& dv = *devs_[(size_t)r];
+        std::lock_guard<std::mutex> lk(dv.mu);
+        dv.touched.insert(dv.filling.begin(), dv.filling.end());
+      }
+  }
   auto stop_recording = [&] {
     for (auto& dv : devs_) {
       std::lock_guard<std::mutex> lk(dv->mu);
@@ -2058,6 +2198,11 @@ StatList HbmBackend::hot_refresh_locked() {
   std::unordered_set<Digest, DigestHash, DigestEq> filled_ok;
   for (int o = 0; o < N; ++o)
     for (const Digest& d : snap[(size_t)o].keys) filled_ok.insert(d);
+  if (before_fill_) {  // tests: between the owners' snapshots and the fills
+    std::function<void()> fn;
+    fn.swap(before_fill_);
+    fn();
+  }
   // ---- 6. fills, one per target shard
   std::vector<std::shared_ptr<HotFill>> fills((size_t)N);
   uint64_t fill_bytes = 0;
@@ -2343,6 +2488,9 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_migrated", sum(&Dev::migrated));
   out->emplace_back("hbm_migrate_ns", sum(&Dev::migrate_ns));
   out->emplace_back("hbm_dropped_sets", sum(&Dev::dropped));
+  out->emplace_back("hbm_purges", purge_started_.load());
+  out->emplace_back("hbm_purged_objects", sum(&Dev::purged_objects));
+  out->emplace_back("hbm_purged_bytes", sum(&Dev::purged_bytes));
   out->emplace_back("hbm_no_shard_misses", no_shard_misses_.load());
   // per-shard GET routing (the load hot-object spreading evens out) and the hot set
   for (size_t i = 0; i < devs_.size(); ++i)

@@ -12,6 +12,7 @@
 #include "bind_parts.h"
 #include "hbm_cache.h"
 #include "host_cache.h"
+#include "keyed.h"
 #include "trace.h"
 
 namespace py = pybind11;
@@ -39,6 +40,7 @@ py::dict counters_dict(const CacheCounters& c) {
   d["reinserted"] = c.reinserted;
   d["reinsert_bytes"] = c.reinsert_bytes;
   d["reinsert_lost"] = c.reinsert_lost;
+  d["purged"] = c.purged;
   return d;
 }
 
@@ -62,6 +64,21 @@ PYBIND11_MODULE(_shellac_core, m) {
     return py::make_tuple(d.lo, d.hi);
   }, "128-bit digest (lo, hi) of a byte string");
   m.def("item_bytes", [](uint32_t vlen) { return item_bytes(vlen); });
+  m.def("keyed", [](py::bytes key, py::bytes payload) {
+    const std::string k = key, p = payload;
+    SH_CHECK(k.size() <= kMaxKeyedKey, "key too long for a keyed value");
+    std::string v(keyed_size(k.size(), p.size()), '\0');
+    write_keyed(reinterpret_cast<uint8_t*>(&v[0]), k, p.data(), p.size());
+    return py::bytes(v);
+  }, "the keyed value [u16 key length | key | payload] the backends store");
+  m.def("keyed_prefix_image", [](py::bytes prefix) {
+    const std::string p = prefix;
+    SH_CHECK(p.size() >= 1 && p.size() <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+    std::string img(keyed_prefix_image_bytes(p.size()), '\0');
+    write_keyed_prefix_image(reinterpret_cast<uint8_t*>(&img[0]),
+                             reinterpret_cast<const uint8_t*>(p.data()), p.size());
+    return py::bytes(img);
+  }, "pattern image of a purge prefix for HbmCache.remove_keyed_prefix");
   m.def("bucket_pair", [](uint64_t lo, uint64_t hi, uint64_t nbuckets) {
     const Digest d{lo, hi};
     return std::vector<uint64_t>{bucket1(d, nbuckets - 1), bucket2(d, nbuckets - 1)};
@@ -203,6 +220,13 @@ PYBIND11_MODULE(_shellac_core, m) {
         py::gil_scoped_release nogil;
         c.remove(P<const Digest>(keys), n, P<uint8_t>(found), now, S(s));
       })
+      // image: keyed_prefix_image(prefix) in device-readable memory; out: 2 words (device
+      // or mapped pinned memory); asynchronous on the stream
+      .def("remove_keyed_prefix", [](HbmCache& c, uintptr_t image, uint32_t plen, uint32_t now,
+                                     uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.remove_keyed_prefix(P<const uint8_t>(image), plen, now, P<uint64_t>(out), S(s));
+      }, py::arg("image"), py::arg("plen"), py::arg("now"), py::arg("out"), py::arg("stream"))
       .def("sweep", [](HbmCache& c, uint32_t now, uintptr_t s) {
         uint64_t live = 0, bytes = 0;
         {
@@ -376,6 +400,13 @@ PYBIND11_MODULE(_shellac_core, m) {
         py::gil_scoped_release nogil;
         c.remove(P<const Digest>(keys), n, P<uint8_t>(found), now);
       })
+      .def("remove_keyed_prefix", [](HostCache& c, py::bytes prefix, uint32_t now) {
+        const std::string p = prefix;
+        uint64_t out[2] = {0, 0};
+        c.remove_keyed_prefix(reinterpret_cast<const uint8_t*>(p.data()), (uint32_t)p.size(), now,
+                              out);
+        return py::make_tuple(out[0], out[1]);
+      }, py::arg("prefix"), py::arg("now"))
       .def("sweep", [](HostCache& c, uint32_t now) {
         uint64_t live = 0, bytes = 0;
         c.sweep(now, &live, &bytes);

@@ -71,6 +71,23 @@ bool blocking_del(CacheBackend* be, const std::string& key) {
   return found;
 }
 
+int64_t blocking_purge(CacheBackend* be, const std::string& prefix) {
+  std::mutex mu;
+  std::condition_variable cv;
+  bool done = false;
+  int64_t removed = -1;
+  py::gil_scoped_release nogil;
+  be->purge_prefix(prefix, &g_inline, [&](int64_t n) {
+    std::lock_guard<std::mutex> lk(mu);
+    removed = n;
+    done = true;
+    cv.notify_all();
+  });
+  std::unique_lock<std::mutex> lk(mu);
+  cv.wait(lk, [&] { return done; });
+  return removed;
+}
+
 }  // namespace
 
 void bind_net(py::module_& m) {
@@ -171,6 +188,10 @@ void bind_net(py::module_& m) {
         h.be->set(k, d, std::make_shared<const std::string>(std::string(value)), flags, ttl);
       }, py::arg("key"), py::arg("value"), py::arg("flags") = 0, py::arg("ttl") = 0)
       .def("delete", [](BackendHandle& h, py::bytes key) { return blocking_del(h.be.get(), key); })
+      // objects whose key starts with `prefix` removed (blocking); -1: the tier cannot scan
+      .def("purge_prefix", [](BackendHandle& h, py::bytes prefix) {
+        return blocking_purge(h.be.get(), prefix);
+      }, py::arg("prefix"))
       .def("get_many", [](BackendHandle& h, std::vector<std::string> keys) {
         // every GET issued at once (one batch stream, as concurrent clients would), then
         // waited for: [(value, flags) or None]
@@ -295,6 +316,44 @@ void bind_net(py::module_& m) {
     for (auto& kv : st) d[py::str(kv.first)] = kv.second;
     return d;
   }, py::arg("backend"));
+  // Tests: one hot-set refresh with a prefix purge queued in its middle, after the owners'
+  // records were snapshot and before the replica fills are queued; returns (the refresh's
+  // counts, objects the purge removed).
+  m.def("hot_refresh_purging", [](BackendHandle& h, py::bytes prefix) {
+    auto* hb = dynamic_cast<HbmBackend*>(h.be.get());
+    if (!hb) throw Error("not an HBM backend");
+    const std::string pre = prefix;
+    struct State {
+      std::mutex mu;
+      std::condition_variable cv;
+      bool queued = false, done = false;
+      int64_t removed = -1;
+    };
+    auto st = std::make_shared<State>();
+    StatList out;
+    {
+      py::gil_scoped_release nogil;
+      hb->debug_before_fill([hb, pre, st] {
+        {
+          std::lock_guard<std::mutex> lk(st->mu);
+          st->queued = true;
+        }
+        hb->purge_prefix(pre, nullptr, [st](int64_t n) {
+          std::lock_guard<std::mutex> lk(st->mu);
+          st->removed = n;
+          st->done = true;
+          st->cv.notify_all();
+        });
+      });
+      out = hb->hot_refresh();
+      hb->debug_before_fill(nullptr);
+      std::unique_lock<std::mutex> lk(st->mu);
+      if (st->queued) st->cv.wait(lk, [&] { return st->done; });
+    }
+    py::dict d;
+    for (auto& kv : out) d[py::str(kv.first)] = kv.second;
+    return py::make_tuple(d, st->queued ? py::object(py::int_(st->removed)) : py::object(py::none()));
+  }, py::arg("backend"), py::arg("prefix"));
   m.def("inject_shard_down", [](BackendHandle& h, int shard, bool down) {
     return h.be->inject_shard_down(shard, down);
   }, py::arg("backend"), py::arg("shard"), py::arg("down") = true);
@@ -320,8 +379,11 @@ void bind_net(py::module_& m) {
                        uint64_t stream_high_water, const std::string& health_path,
                        int health_interval_ms, int health_timeout_ms, int health_fails,
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
-                       uint64_t max_inflate_bytes, int gzip_workers) {
+                       uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge) {
              ProxyConfig c;
+             SH_CHECK(purge == "off" || purge == "loopback" || purge == "any",
+                      "purge must be off, loopback or any");
+             c.purge = purge;
              c.spin_us = spin_us;
              c.gzip_gpu = gzip_gpu;
              c.gzip_batch_us = gzip_batch_us;
@@ -371,13 +433,21 @@ void bind_net(py::module_& m) {
            py::arg("health_timeout_ms") = 500, py::arg("health_fails") = 2,
            py::arg("cpus") = std::vector<int>{}, py::arg("spin_us") = 0,
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
-           py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2)
+           py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
+           py::arg("purge") = "off")
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)
       .def_property_readonly("port", &Proxy::port)
       .def_property_readonly("running", &Proxy::running)
       .def("stats_json", &Proxy::stats_json);
+
+  // the proxy's PURGE admission for a client at IPv4 address `client_ip` (tests)
+  m.def("purge_allowed", [](const std::string& mode, const std::string& client_ip) {
+    in_addr a{};
+    SH_CHECK(inet_pton(AF_INET, client_ip.c_str(), &a) == 1, "not an IPv4 address");
+    return purge_allowed(mode, ipv4_is_loopback(ntohl(a.s_addr)));
+  }, py::arg("mode"), py::arg("client_ip"));
 
   py::class_<CacheServer>(m, "CacheServer")
       .def(py::init([](BackendHandle& be, uint16_t port, const std::string& bind, int threads) {

@@ -237,6 +237,20 @@ class HbmCache {
   static void destroy_graph(StoreGraph* g);
   // DELETE a batch; found[i] = 1 if a live entry was removed.
   void remove(const Digest* keys, int64_t n, uint8_t* found, uint32_t now, hipStream_t s);
+  // Prefix purge of *keyed* values ([u16 klen | key | payload], keyed.h): removes every
+  // live entry whose stored key starts with the prefix, exactly as DELETE removes one (the
+  // entry's loc is zeroed; the log and the item-start ring stay). `image`: the pattern image
+  // write_keyed_prefix_image() made of the prefix (keyed_prefix_image_bytes(plen) bytes,
+  // 16-byte aligned, device-readable: device or mapped pinned memory); 1 <= plen <= 65535
+  // (an empty prefix is flush()). `out` (device or mapped pinned memory, 2 words) receives
+  // {entries removed, their item bytes}; the removed entries are also counted as `purged`.
+  // Asynchronous and ordered on `s` like remove(): no allocation, no synchronisation (one
+  // purge at a time per shard: the result is accumulated in the shard's scratch words).
+  // Dead entries (empty, locked, expired, overwritten) are neither read nor removed nor
+  // counted. Defined for keyed values only: on other values it is memory-safe and removes
+  // whatever happens to parse as a matching keyed record.
+  void remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t now, uint64_t* out,
+                           hipStream_t s);
   // Reclaim index slots whose items expired or were overwritten. Synchronises;
   // returns {live entries, live item bytes}.
   void sweep(uint32_t now, hipStream_t s, uint64_t* live_entries, uint64_t* live_bytes);

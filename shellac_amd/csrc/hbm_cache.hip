@@ -32,6 +32,9 @@
 //   All per-op counters are block-reduced and added to one of 64 counter
 //   shards (one atomic per block per field; same-address fan-in measured at
 //   ~12 ns/atomic would otherwise serialise a 64K-wave probe into milliseconds).
+//   k_purge_prefix one lane per index slot (k_sweep's traversal): a live entry's record is
+//                  read from the log and the entry removed if its stored key starts with
+//                  the pattern (16-B granules against a host-prepared, shifted image).
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -46,6 +49,7 @@
 #include <vector>
 
 #include "hbm_cache.h"
+#include "keyed.h"
 #include "trace.h"
 
 namespace shellac {
@@ -2989,6 +2993,109 @@ __global__ __launch_bounds__(kBlock) void k_sweep(Entry* __restrict__ index, uin
   }
 }
 
+// Prefix purge: remove every live entry whose stored *keyed* value ([u16 klen | key |
+// payload], keyed.h) has a key that starts with the pattern. One lane per index slot, as
+// k_sweep: the index is a coalesced 32-B-per-lane stream; each live entry costs one
+// dependent, scattered read of its record (header 32 B + the first value granule, which
+// holds klen and key bytes 0..13 and rejects nearly every non-matching record); only the
+// survivors read the further granules. `img` is the host-prepared pattern image of keyed.h
+// (granule masks, then the pattern shifted by the 2-byte klen word), `ngran` its pattern
+// granules; the granules after the first are staged in LDS up to kPurgeLdsGranules and read
+// from global memory (one address per wave: a broadcast) beyond that.
+//
+// What it relies on. Exactness (every matching object stored before the call is removed,
+// nothing else) comes from stream order against appends: the backend queues it between SET
+// chains. Beside a concurrent append on another stream it stays memory-safe and never
+// removes a live non-matching object, through the header re-check (as k_edge_server's
+// claim / re-check): the record must still carry the entry's digest, vlen and the magic
+// word, every read stays inside [record, record + item_bytes(vlen)) with vlen <= max_item
+// (inside the log's slack), and the removal is a CAS of the very loc that was read — a
+// record an append tore while it was compared belongs to an entry the append is about to
+// kill anyway, and an entry a SET re-pointed meanwhile keeps its new loc.
+// The item-start ring and the log are untouched (as after k_delete): the CLOCK hand skips
+// ring entries whose index entry is gone, and a detached hand's move-CAS of a purged entry
+// loses (reinsert_lost).
+constexpr int kPurgeLdsGranules = 64;  // 1 KiB: prefixes up to 1022 bytes compare from LDS
+
+__device__ __forceinline__ bool purge_granule_eq(const uint4 v, const uint4 m, const uint4 p) {
+  return (((v.x & m.x) ^ p.x) | ((v.y & m.y) ^ p.y) | ((v.z & m.z) ^ p.z) |
+          ((v.w & m.w) ^ p.w)) == 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void k_purge_prefix(
+    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    const uint4* __restrict__ img, uint32_t plen, uint32_t ngran,
+    unsigned long long* __restrict__ out, CacheCounters* __restrict__ ctr) {
+  // the two masks and the first pattern granules: one read of the image per workgroup (it
+  // may be mapped host memory)
+  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
+  const uint4* const s_pat = s_img + 2;
+  const uint4* const pat = img + 2;
+  for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
+    s_img[g] = img[g];
+  __syncthreads();
+  const uint4 m0 = s_img[0], mlast = s_img[1], p0 = s_pat[0];
+  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);  // the granules between: every byte
+  const uint64_t head = *head_ptr;
+  unsigned long long removed = 0, bytes = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < kKeyedPrefix + plen || vlen > max_item || ((loc - 1) & 15)) continue;
+    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    const uint4 v0 = rec[2];
+    const uint32_t klen = v0.x & 0xffffu;
+    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
+    if (!purge_granule_eq(v0, m0, p0)) continue;
+    bool eq = true;
+    for (uint32_t g = 1; g < ngran; ++g) {
+      const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_pat[g] : pat[g];
+      const uint4 v = rec[2 + g];
+      if (!purge_granule_eq(v, g + 1 == ngran ? mlast : ones, p)) {
+        eq = false;
+        break;
+      }
+    }
+    if (!eq) continue;
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
+                  0ull) == loc) {
+      ++removed;
+      bytes += item_bytes(vlen);
+    }
+  }
+  block_count(ctr, removed, &CacheCounters::purged);
+  // the result words: one add per word per workgroup, after its whole grid-stride loop (a
+  // matching purge with an add per wave spent ~0.4 ms on the same-address fan-in alone)
+  __shared__ unsigned long long s_res[2][kBlock / 64];
+  removed = wave_sum(removed);
+  bytes = wave_sum(bytes);
+  if ((threadIdx.x & 63) == 0) {
+    s_res[0][threadIdx.x >> 6] = removed;
+    s_res[1][threadIdx.x >> 6] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0, t1 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+      t0 += s_res[0][k];
+      t1 += s_res[1][k];
+    }
+    if (t0) atomicAdd(&out[0], t0);
+    if (t1) atomicAdd(&out[1], t1);
+  }
+}
 
 // Export the digests of all live entries (rebalancing / warm restore). One atomic
 // per workgroup per pass reserves the output range; lanes write in block order.
@@ -4190,6 +4297,24 @@ void HbmCache::sweep(uint32_t now, hipStream_t s, uint64_t* live_entries, uint64
   reap_retired(false);  // (the idle-time maintenance call: grown-out workspaces that are done)
   if (live_entries) *live_entries = host_buf_[0];
   if (live_bytes) *live_bytes = host_buf_[1];
+}
+
+void HbmCache::remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t now,
+                                   uint64_t* out, hipStream_t s) {
+  TraceRange tr("hbm.purge_prefix");
+  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+  SH_CHECK(image && out, "purge needs a pattern image and a result buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 4;  // (words 0..1 are sweep's and export's)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_purge_prefix, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
+                     0, s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
+                     reinterpret_cast<const uint4*>(image), plen,
+                     (uint32_t)keyed_prefix_granules(plen), acc, ctr_);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
 }
 
 uint64_t HbmCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now, hipStream_t s) {

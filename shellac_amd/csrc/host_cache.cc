@@ -1,6 +1,8 @@
 // Host-DRAM cache shard: same layout and policies as the HBM kernels.
 #include "host_cache.h"
 
+#include "keyed.h"
+
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -371,6 +373,39 @@ void HostCache::sweep(uint32_t now, uint64_t* live_entries, uint64_t* live_bytes
   }
   if (live_entries) *live_entries = live;
   if (live_bytes) *live_bytes = bytes;
+}
+
+void HostCache::remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now,
+                                    uint64_t out[2]) {
+  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t removed = 0, bytes = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    Entry& e = index_[k];
+    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
+    const uint32_t vlen = entry_vlen(e.vlen);
+    // (vlen <= max_item and an aligned loc hold for every stored entry: they keep the reads
+    // of an entry debug_set_entry made up inside the log's slack)
+    if (vlen < kKeyedPrefix + plen || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
+    const uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
+    const uint8_t* const v = rec + kItemHeaderBytes;
+    uint16_t klen;
+    std::memcpy(&klen, v, kKeyedPrefix);
+    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
+    if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
+    e.loc = 0;
+    ++removed;
+    bytes += item_bytes(vlen);
+  }
+  ctr_.purged += removed;
+  if (out) {
+    out[0] = removed;
+    out[1] = bytes;
+  }
 }
 
 uint64_t HostCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now) {

@@ -31,6 +31,11 @@ class HostCache {
              uint32_t now, uint64_t bytes_bound = 0);  // 0: the batch's exact bytes
   void remove(const Digest* keys, int64_t n, uint8_t* found, uint32_t now);
   void sweep(uint32_t now, uint64_t* live_entries, uint64_t* live_bytes);
+  // Prefix purge of keyed values (HbmCache::remove_keyed_prefix, whose semantic reference
+  // this is): removes every live entry whose record is its own (magic, digest, vlen) and
+  // whose stored key starts with prefix[0..plen), 1 <= plen <= 65535;
+  // out = {entries removed, their item bytes}, also counted as `purged`.
+  void remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now, uint64_t out[2]);
   void flush();
   // Tests: see HbmCache::debug_bucket / debug_set_entry.
   std::vector<uint64_t> debug_bucket(uint64_t b);

@@ -37,4 +37,33 @@ inline bool keyed_match(const char* v, size_t n, const std::string& key, size_t*
   return true;
 }
 
+// ---- prefix purge (HbmCache / HostCache::remove_keyed_prefix) -------------------------------
+// A keyed value starts 16-byte aligned in the log and its key starts at value byte 2, so
+// the prefix scan compares 16-byte granules of the value against a pattern *image*: the
+// prefix shifted by those 2 bytes, with byte masks for the first granule (the key length
+// word is not compared) and the last one (bytes past the prefix are not compared).
+//   image = [mask of granule 0 | mask of the last granule | G granules of masked pattern]
+//   G = ceil((2 + plen) / 16); with G == 1 both masks hold the one combined mask.
+constexpr size_t kPurgeGranule = 16;
+
+inline size_t keyed_prefix_granules(size_t plen) {
+  return (kKeyedPrefix + plen + kPurgeGranule - 1) / kPurgeGranule;
+}
+inline size_t keyed_prefix_image_bytes(size_t plen) {
+  return (2 + keyed_prefix_granules(plen)) * kPurgeGranule;
+}
+inline void write_keyed_prefix_image(uint8_t* dst, const uint8_t* prefix, size_t plen) {
+  const size_t g = keyed_prefix_granules(plen), end = kKeyedPrefix + plen;
+  std::memset(dst, 0, keyed_prefix_image_bytes(plen));
+  uint8_t* const m0 = dst;
+  uint8_t* const ml = dst + kPurgeGranule;
+  uint8_t* const pat = dst + 2 * kPurgeGranule;
+  for (size_t b = kKeyedPrefix; b < kPurgeGranule && b < end; ++b) m0[b] = 0xff;
+  for (size_t b = 0; b < kPurgeGranule; ++b) {
+    const size_t at = (g - 1) * kPurgeGranule + b;
+    if (at >= kKeyedPrefix && at < end) ml[b] = 0xff;
+  }
+  std::memcpy(pat + kKeyedPrefix, prefix, plen);
+}
+
 }  // namespace shellac

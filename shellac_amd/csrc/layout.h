@@ -165,7 +165,8 @@ struct CacheCounters {
   // reinsertions indexed as moves whose entry had moved on (a SET or DELETE of the key
   // landed after the hand read the index): their log bytes are dead on arrival
   unsigned long long reinsert_lost;
-  unsigned long long reserved[2];
+  unsigned long long purged;        // live entries removed by remove_keyed_prefix()
+  unsigned long long reserved[1];
 };
 static_assert(sizeof(CacheCounters) == 128, "CacheCounters layout");
 

@@ -196,6 +196,30 @@ bool ObjectCache::del(const std::string& key, const Digest& d, uint32_t now) {
   return true;
 }
 
+uint64_t ObjectCache::purge_prefix(const std::string& prefix, uint32_t now) {
+  uint64_t removed = 0;
+  for (auto& sp : stripes_) {
+    Stripe& s = *sp;
+    std::vector<std::shared_ptr<const std::string>> dead;  // freed outside the stripe lock
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (size_t id = 0; id < s.slots.size(); ++id) {
+      const Obj& o = s.slots[id];
+      if (!o.data || (o.expire && o.expire <= now)) continue;
+      const std::string& v = *o.data;
+      if (v.size() < kKeyedPrefix + prefix.size()) continue;
+      uint16_t kl;
+      std::memcpy(&kl, v.data(), kKeyedPrefix);
+      if (kl < prefix.size() || v.size() < kKeyedPrefix + kl) continue;
+      if (std::memcmp(v.data() + kKeyedPrefix, prefix.data(), prefix.size()) != 0) continue;
+      if (int32_t* pos = find(s, o.d)) {
+        erase_slot(s, pos, &dead);
+        ++removed;
+      }
+    }
+  }
+  return removed;
+}
+
 void ObjectCache::clear() {
   for (auto& sp : stripes_) {
     Stripe& s = *sp;

@@ -41,6 +41,9 @@ class ObjectCache {
   void set(const std::string& key, const Digest& d, const char* payload, size_t n,
            uint32_t flags, uint32_t expire, uint32_t now);
   bool del(const std::string& key, const Digest& d, uint32_t now);
+  // Drops every live object whose stored key starts with `prefix` (a walk of every stripe
+  // under its lock); returns how many.
+  uint64_t purge_prefix(const std::string& prefix, uint32_t now);
   void clear();
   ObjectCacheStats stats() const;
 

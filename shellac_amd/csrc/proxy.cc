@@ -223,6 +223,7 @@ struct Pend {
   bool lookup, head, client_gzip;
   std::string base_key;
   std::shared_ptr<const std::vector<Header>> req_headers;
+  uint64_t purge_gen = 0;  // Proxy::purge_generation() when the fetch was forwarded
 };
 
 struct Upstream : Conn {
@@ -257,7 +258,7 @@ class Reactor : public Executor {
       cache_sets{0}, bad_requests{0}, upstream_failures{0}, retries{0}, collapsed{0},
       streamed{0}, stream_pauses{0}, gzip_gpu_bodies{0}, gzip_gpu_inflated{0}, identity_decoded{0},
       vary_stored{0},
-      vary_hits{0};
+      vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0};
   // event-loop health: the longest iteration (events handled between two epoll_waits)
   // and how many took over 10 ms — a reactor that stalls stops accepting connections
   std::atomic<uint64_t> loop_max_us{0}, loop_slow{0}, client_resets{0};
@@ -275,6 +276,9 @@ class Reactor : public Executor {
   void on_client(Client* c, uint32_t ev);
   void on_upstream(Upstream* u, uint32_t ev);
   void on_request(Client* c);
+  void on_purge(Client* c, Slot* s, const std::string& key, bool prefix);
+  void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
+                    const std::string& body);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
   void forward(Client* c, Slot* s);
   static std::string upstream_request(HttpParser& q);
@@ -504,7 +508,7 @@ void Reactor::accept_all() {
     c->kind = 0;
     c->id = next_id_++;
     c->ctime = c->atime = now_s();
-    c->loopback = (ntohl(sa.sin_addr.s_addr) >> 24) == 127;
+    c->loopback = ipv4_is_loopback(ntohl(sa.sin_addr.s_addr));
     conns_[c->id] = c;
     epoll_event ev{};
     ev.events = EPOLLIN | EPOLLRDHUP;
@@ -618,6 +622,15 @@ void Reactor::on_request(Client* c) {
     return;
   }
   const std::string& method = q.method();
+  if (method == "PURGE" && cfg_.purge != "off") {
+    const std::string* host = q.header("host");
+    const std::string key = cfg_.key_host && host ? *host + url : url;  // as a GET's
+    const std::string* mode = q.header("x-purge-mode");
+    const bool prefix = mode && to_lower(*mode) == "prefix";
+    c->slots.push_back(std::move(s));
+    on_purge(c, sp, key, prefix);
+    return;
+  }
   s->head = method == "HEAD";
   s->client_gzip = contains_ci(q.header("accept-encoding"), "gzip");
   const std::string* host = q.header("host");
@@ -637,6 +650,61 @@ void Reactor::on_request(Client* c) {
   } else {
     forward(c, sp);
   }
+}
+
+// PURGE (ProxyConfig::purge): the request holds its slot like any other (pipelined order is
+// kept) and is answered when the backend's callbacks arrive.
+//   exact : the URL's object (for a URL whose responses Vary, the marker) and every variant
+//           — the variants live under vary_key(base, ...) = base + '\x1f' + ..., and
+//           deleting only the marker would make them reachable again once a new marker is
+//           stored;
+//   prefix: every object whose key starts with the URL's key.
+void Reactor::on_purge(Client* c, Slot* s, const std::string& key, bool prefix) {
+  const uint64_t cid = c->id, seq = s->seq;
+  if (!purge_allowed(cfg_.purge, c->loopback)) {
+    purge_denied++;
+    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
+    return;
+  }
+  purge_requests++;
+  CacheBackend* be = px_->backend_.get();
+  if (!be || !px_->cfg_.cache_enabled) {
+    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
+    return;
+  }
+  px_->note_purge(key, prefix);  // before the tier is touched: fills in flight are refused
+  if (prefix) {
+    be->purge_prefix(key, this, [this, cid, seq](int64_t n) {
+      if (n < 0) {
+        answer_purge(cid, seq, 501, "Not Implemented",
+                     "{\"mode\":\"prefix\",\"error\":\"the cache tier cannot scan its keys\"}");
+        return;
+      }
+      purged_objects += (uint64_t)n;
+      answer_purge(cid, seq, 200, "OK",
+                   "{\"mode\":\"prefix\",\"purged\":" + std::to_string(n) + "}");
+    });
+    return;
+  }
+  const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(key.data()), key.size());
+  be->del(key, d, this, [this, be, key, cid, seq](bool found) {
+    be->purge_prefix(key + '\x1f', this, [this, cid, seq, found](int64_t n) {
+      purged_objects += (found ? 1 : 0) + (uint64_t)(n > 0 ? n : 0);
+      answer_purge(cid, seq, 200, "OK",
+                   std::string("{\"mode\":\"exact\",\"found\":") + (found ? "true" : "false") +
+                       ",\"variants\":" + std::to_string(n < 0 ? -1 : n) + "}");
+    });
+  });
+}
+
+void Reactor::answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
+                           const std::string& body) {
+  Client* c = find_client(cid);
+  if (!c) return;
+  Slot* s = find_slot(c, seq);
+  if (!s || s->ready) return;
+  complete_slot(c, s, std::make_shared<const std::string>(simple_response(
+                          code, reason, cfg_.server_name, body + "\n", "application/json")));
 }
 
 void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
@@ -953,7 +1021,7 @@ void Reactor::forward(Client* c, Slot* s) {
   }
   u->out.write(s->fwd);
   u->pend.push_back(Pend{c->id, s->seq, s->key, s->d, s->lookup, s->head, s->client_gzip,
-                        s->base_key, s->req_headers});
+                        s->base_key, s->req_headers, px_->purge_generation()});
   u->count++;
   upstream_reqs++;
   flush_upstream(u);
@@ -1204,7 +1272,15 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
   uint32_t ttl = cfg_.ttl;
   bool cached = false, waiters_share = true;
   if (p.lookup && !p.head && cacheable_response(r, &ttl)) {
-    if (vnames.empty()) {
+    if (px_->purged_since(p.purge_gen, p.key, p.base_key)) {
+      // fetched before a purge of this key: delivered (the collapsed waiters share it as
+      // they would have), not stored
+      fills_purged++;
+      cached = true;
+      if (!vnames.empty())
+        waiters_share = vnames[0] != "*" && p.req_headers &&
+                        p.key == vary_key(p.base_key, vnames, *p.req_headers);
+    } else if (vnames.empty()) {
       cached = true;
       px_->backend_->set(p.key, p.d, obj, 0, ttl);  // Server.py:432 mc.set(key, obj, time=ttl)
       cache_sets++;
@@ -1583,10 +1659,34 @@ std::string prometheus_text(const std::string& stats_json) {
   return o.str();
 }
 
+void Proxy::note_purge(const std::string& pattern, bool prefix) {
+  std::lock_guard<std::mutex> lk(purge_mu_);
+  if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
+  const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
+  PurgeRec& r = purge_ring_[gen % kPurgeRing];
+  r.gen = gen;
+  r.pattern = pattern;
+  r.prefix = prefix;
+  purge_gen_.store(gen, std::memory_order_release);
+}
+
+bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string& base_key) {
+  if (purge_gen_.load(std::memory_order_acquire) == gen) return false;  // the common case
+  std::lock_guard<std::mutex> lk(purge_mu_);
+  const uint64_t cur = purge_gen_.load(std::memory_order_relaxed);
+  if (cur - gen > kPurgeRing) return true;  // the ring wrapped past this fetch: assume purged
+  for (uint64_t g = gen + 1; g <= cur; ++g) {
+    const PurgeRec& r = purge_ring_[g % kPurgeRing];
+    if (r.prefix ? key.compare(0, r.pattern.size(), r.pattern) == 0 : base_key == r.pattern)
+      return true;
+  }
+  return false;
+}
+
 std::string Proxy::stats_json() {
   uint64_t req = 0, hit = 0, miss = 0, ur = 0, resp = 0, bo = 0, err = 0, cl = 0, up = 0, acc = 0,
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
-           lslow = 0, idd = 0, vst = 0, vh = 0;
+           lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0;
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t h[kHistBuckets] = {};
   for (auto& r : reactors_) {
@@ -1601,6 +1701,8 @@ std::string Proxy::stats_json() {
     idd += r->identity_decoded;
     vst += r->vary_stored;
     vh += r->vary_hits;
+    prq += r->purge_requests; pob += r->purged_objects; pdn += r->purge_denied;
+    fpg += r->fills_purged;
     for (int k = 0; k < 5; ++k) pmax[k] = std::max<uint64_t>(pmax[k], r->phase_max_us[k]);
     for (int b = 0; b < kHistBuckets; ++b) h[b] += r->hist[b];
   }
@@ -1626,6 +1728,8 @@ std::string Proxy::stats_json() {
     << ",\"upstream_conns\":" << up << ",\"accepts\":" << acc << ",\"gc_closed\":" << gcc
     << ",\"client_resets\":" << crst << ",\"identity_decoded\":" << idd
     << ",\"vary_stored\":" << vst << ",\"vary_hits\":" << vh
+    << ",\"purge_requests\":" << prq << ",\"purged_objects\":" << pob
+    << ",\"purge_denied\":" << pdn << ",\"fills_not_cached_purged\":" << fpg
     << ",\"loop_max_us\":" << lmax << ",\"loop_slow\":" << lslow
     << ",\"loop_phase_max_us\":{\"accept\":" << pmax[0] << ",\"client\":" << pmax[1]
     << ",\"upstream\":" << pmax[2] << ",\"posted\":" << pmax[3] << ",\"timer\":" << pmax[4]

@@ -52,6 +52,11 @@ struct ProxyConfig {
   std::string policy = "rfc";         // "rfc" | "reference" (cache every response)
   bool kill_switch = true;            // GET /kill stops the proxy (Server.py:329-331)
   bool kill_loopback_only = true;
+  // The PURGE method (cache invalidation): "off" (a PURGE request is handled like any other
+  // method: forwarded upstream), "loopback" (clients on 127/8 only, others get 403), "any".
+  // `PURGE <url>` removes the URL's object and all its Vary variants; with the header
+  // `X-Purge-Mode: prefix` every object whose key starts with the URL's key.
+  std::string purge = "off";
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
   bool key_host = false;
@@ -107,6 +112,17 @@ class Proxy {
   void upstream_failed(int idx, double now);
   int next_rr() { return rr_++; }
 
+  // Purges and fills in flight: a miss fetched from the origin before a purge must not be
+  // stored after it. Every purge takes a generation and is remembered in a small ring; a
+  // fetch remembers the generation when it is forwarded, and its fill is delivered but not
+  // cached if a newer purge matches its key or the ring has wrapped past its generation.
+  static constexpr size_t kPurgeRing = 64;
+  uint64_t purge_generation() const { return purge_gen_.load(std::memory_order_acquire); }
+  void note_purge(const std::string& pattern, bool prefix);
+  // `key`: the key the object would be stored under; `base_key`: its URL key (an exact
+  // purge of the URL covers every variant)
+  bool purged_since(uint64_t gen, const std::string& key, const std::string& base_key);
+
  private:
   friend class Reactor;
   ProxyConfig cfg_;
@@ -124,9 +140,25 @@ class Proxy {
   std::thread health_th_;
   void health_loop();
   std::atomic<int> rr_{0};
+  struct PurgeRec {
+    uint64_t gen = 0;
+    std::string pattern;
+    bool prefix = false;
+  };
+  std::atomic<uint64_t> purge_gen_{0};
+  std::mutex purge_mu_;
+  std::vector<PurgeRec> purge_ring_;  // slot gen % kPurgeRing
   std::mutex wait_mu_;
   double start_time_ = 0;
 };
+
+// Who may PURGE (ProxyConfig::purge) and what counts as a loopback client: the predicates
+// the reactor applies to a connection's peer address (IPv4, host byte order) at accept and
+// to a PURGE request. "off" admits nobody (the method is not handled at all).
+inline bool ipv4_is_loopback(uint32_t addr_host_order) { return (addr_host_order >> 24) == 127; }
+inline bool purge_allowed(const std::string& mode, bool client_loopback) {
+  return mode == "any" || (mode == "loopback" && client_loopback);
+}
 
 // The stats JSON (Proxy::stats_json) as Prometheus text-format samples (GET
 // /_shellac/metrics): nested keys joined with '_' under `shellac_`, array elements as an

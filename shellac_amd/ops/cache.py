@@ -92,6 +92,13 @@ def pack_values(values: Sequence[bytes], device: str | torch.device = "cpu"):
     )
 
 
+def keyed(key: bytes, payload: bytes) -> bytes:
+    """The *keyed* value ``[u16 key length | key | payload]`` the cache backends store for
+    full-key identity (``csrc/keyed.h`` ``write_keyed``): what ``remove_keyed_prefix``
+    scans. Store it under ``digest_strings([key])``."""
+    return core().keyed(bytes(key), bytes(payload))
+
+
 def unpack_records(out: torch.Tensor, off: torch.Tensor, size: torch.Tensor) -> list:
     """Decode GET output ([ItemHeader | value | pad] per hit) -> list of (value, flags) or None."""
     o = out.cpu().numpy()
@@ -598,6 +605,30 @@ class CacheShard:
         else:
             self._impl.remove(keys.data_ptr(), n, found.data_ptr(), now)
         return found.bool()
+
+    def remove_keyed_prefix(self, prefix: bytes, now: Optional[int] = None) -> tuple[int, int]:
+        """Prefix purge: remove every live object whose stored key starts with ``prefix``
+        (1..65535 bytes; an empty prefix is ``flush``). Returns (objects removed, their
+        item bytes); the objects are also counted in ``counters()["purged"]``. Synchronises,
+        like ``sweep``. On a GPU shard ``k_purge_prefix`` walks the index and compares the
+        key bytes stored in the value log.
+
+        Defined for *keyed* values only (``keyed(key, payload)``, what the proxy's backends
+        store): the key is read from the value. On other values it is memory-safe and
+        removes whatever happens to parse as a matching keyed record."""
+        prefix = bytes(prefix)
+        if not 1 <= len(prefix) <= 0xFFFF:
+            raise ValueError("purge prefix must hold 1..65535 bytes")
+        now = self.now() if now is None else now
+        if not self.is_gpu:
+            return tuple(self._impl.remove_keyed_prefix(prefix, now))
+        img = np.frombuffer(core().keyed_prefix_image(prefix), dtype=np.uint8)
+        image = torch.from_numpy(img.copy()).to(self.device)
+        out = torch.empty(2, dtype=torch.int64, device=self.device)
+        self._impl.remove_keyed_prefix(image.data_ptr(), len(prefix), now, out.data_ptr(),
+                                       self._s())
+        removed, nbytes = out.tolist()  # (waits for the stream)
+        return int(removed), int(nbytes)
 
     def sweep(self, now: Optional[int] = None) -> tuple[int, int]:
         now = self.now() if now is None else now

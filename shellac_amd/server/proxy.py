@@ -155,7 +155,14 @@ class Server:
                  health_timeout_ms: int = 500, health_fails: int = 2,
                  cpus: Sequence[int] = (), spin_us: int = 0, gzip_gpu: int = -1,
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
-                 max_inflate_bytes: int = 64 << 20, **backend_opts):
+                 max_inflate_bytes: int = 64 << 20, purge: str = "off", **backend_opts):
+        """``purge``: who may invalidate with the ``PURGE`` method — ``"off"`` (default: a
+        ``PURGE`` request is forwarded upstream like any other method), ``"loopback"``
+        (clients on 127.0.0.0/8; others get 403) or ``"any"``. ``PURGE <url>`` removes the
+        URL's object and all its Vary variants; with ``X-Purge-Mode: prefix`` every object
+        whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU)."""
+        if purge not in ("off", "loopback", "any"):
+            raise ValueError("purge must be 'off', 'loopback' or 'any'")
         if not servers:
             raise ValueError("No upstream web servers specified.")
         self._backend = backend
@@ -174,7 +181,8 @@ class Server:
             health_interval_ms=health_interval_ms, health_timeout_ms=health_timeout_ms,
             health_fails=health_fails, cpus=[int(c) for c in cpus], spin_us=int(spin_us),
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
-            max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers))
+            max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
+            purge=purge)
         self._started = False
 
     @property
@@ -274,6 +282,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-fails", type=int, default=2,
                    help="consecutive failed probes that take an upstream out of rotation")
     p.add_argument("--no-kill-switch", action="store_true", help="disable GET /kill")
+    p.add_argument("--purge", choices=["off", "loopback", "any"], default="off",
+                   help="who may invalidate with the PURGE method: off (default; PURGE is "
+                        "forwarded upstream), loopback (127.0.0.0/8 only, others get 403) or "
+                        "any. 'PURGE /url' drops the URL and its Vary variants; with the header "
+                        "'X-Purge-Mode: prefix' everything under that URL prefix")
     p.add_argument("--fault", default="",
                    help="fault injection on the cache tier, e.g. get_miss=0.1,set_drop=0.5,"
                         "delay_us=500, down, or gpu_down=K (eject GPU shard K; drills; "
@@ -324,7 +337,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  health_interval_ms=args.health_interval_ms, health_fails=args.health_fails,
                  cpus=parse_cpus(args.cpus), spin_us=args.spin_us,
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
-                 max_inflate_bytes=args.max_inflate_mb << 20,
+                 max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,
