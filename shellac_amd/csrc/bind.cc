@@ -279,9 +279,36 @@ PYBIND11_MODULE(_shellac_core, m) {
   m.def("trace_pop", []() { trace_pop(); });
   m.def("trace_mark", [](const std::string& name) { trace_mark(name.c_str()); });
   m.def("segcopy", [](uintptr_t src, uintptr_t src_off, uintptr_t dst_off, int64_t n,
-                      uintptr_t dst, uintptr_t s) {
+                      uintptr_t dst, uintptr_t s, uint64_t dst_cap) {
     segcopy(P<const uint8_t>(src), P<const uint64_t>(src_off), P<const uint64_t>(dst_off), n,
-            P<uint8_t>(dst), S(s));
+            P<uint8_t>(dst), S(s), dst_cap);
+  }, py::arg("src"), py::arg("src_off"), py::arg("dst_off"), py::arg("n"), py::arg("dst"),
+     py::arg("stream"), py::arg("dst_cap") = ~0ull);
+  m.def("segcopy_sized", [](uintptr_t src, uintptr_t src_off, uintptr_t dst_off,
+                            uintptr_t seg_len, int64_t n, uintptr_t dst, uintptr_t s,
+                            uint64_t cap) {
+    segcopy_sized(P<const uint8_t>(src), P<const uint64_t>(src_off), P<const uint64_t>(dst_off),
+                  P<const uint64_t>(seg_len), n, P<uint8_t>(dst), S(s), cap);
+  }, py::arg("src"), py::arg("src_off"), py::arg("dst_off"), py::arg("seg_len"), py::arg("n"),
+     py::arg("dst"), py::arg("stream"), py::arg("cap") = ~0ull);
+  m.def("segcopy_dev", [](uintptr_t src_off, uintptr_t dst_off, uintptr_t n_dev, uintptr_t dst,
+                          uintptr_t s, uint64_t dst_cap) {
+    segcopy_dev(P<const uint64_t>(src_off), P<const uint64_t>(dst_off), P<const int64_t>(n_dev),
+                P<uint8_t>(dst), S(s), dst_cap);
+  }, py::arg("src_off"), py::arg("dst_off"), py::arg("n_dev"), py::arg("dst"),
+     py::arg("stream"), py::arg("dst_cap") = ~0ull);
+  m.def("segcopy_geometry", []() {
+    const SegcopyGeometry g = segcopy_geometry();
+    py::dict grid;
+    for (int mode = 0; mode < 5; ++mode) grid[py::int_(mode)] = g.grid[mode];
+    py::dict d;
+    d["min_tile"] = g.min_tile;
+    d["stage"] = g.stage;
+    d["stage_sized"] = g.stage_sized;
+    d["stage_glds"] = g.stage_glds;
+    d["glds"] = g.glds;
+    d["grid"] = grid;
+    return d;
   });
   m.def("coalesce_table_slots", &coalesce_table_slots);
   m.def("coalesce_keys", [](uintptr_t keys, int64_t n, uintptr_t table, int64_t slots,
@@ -451,10 +478,18 @@ PYBIND11_MODULE(_shellac_core, m) {
     host_exclusive_scan(P<const uint64_t>(in), P<uint64_t>(out), n);
   });
   m.def("host_segcopy", [](uintptr_t src, uintptr_t src_off, uintptr_t dst_off, int64_t n,
-                           uintptr_t dst) {
+                           uintptr_t dst, uint64_t dst_cap) {
     host_segcopy(P<const uint8_t>(src), P<const uint64_t>(src_off), P<const uint64_t>(dst_off), n,
-                 P<uint8_t>(dst));
-  });
+                 P<uint8_t>(dst), dst_cap);
+  }, py::arg("src"), py::arg("src_off"), py::arg("dst_off"), py::arg("n"), py::arg("dst"),
+     py::arg("dst_cap") = ~0ull);
+  m.def("host_segcopy_sized", [](uintptr_t src, uintptr_t src_off, uintptr_t dst_off,
+                                 uintptr_t seg_len, int64_t n, uintptr_t dst, uint64_t cap) {
+    host_segcopy_sized(P<const uint8_t>(src), P<const uint64_t>(src_off),
+                       P<const uint64_t>(dst_off), P<const uint64_t>(seg_len), n, P<uint8_t>(dst),
+                       cap);
+  }, py::arg("src"), py::arg("src_off"), py::arg("dst_off"), py::arg("seg_len"), py::arg("n"),
+     py::arg("dst"), py::arg("cap") = ~0ull);
   m.def("host_digest_keys", [](uintptr_t bytes, uintptr_t offs, int64_t n, uintptr_t out) {
     host_digest_keys(P<const uint8_t>(bytes), P<const int64_t>(offs), n, P<Digest>(out));
   });

@@ -472,6 +472,17 @@ void segcopy_dev(const uint64_t* src_off, const uint64_t* dst_off, const int64_t
 void segcopy_sized(const uint8_t* src, const uint64_t* src_off, const uint64_t* dst_off,
                    const uint64_t* seg_len, int64_t n, uint8_t* dst, hipStream_t s,
                    uint64_t cap = ~0ull);
+// What the byte mover's partition is made of, for tests that must reach a given path:
+// the minimum tile (16-B chunks), the segments staged per pass (modes 0/1/3/4, mode 2, the
+// LDS-DMA variant), whether this process runs the LDS-DMA variant (SHELLAC_GLDS), and the
+// workgroups each mode is launched with on the current device.
+struct SegcopyGeometry {
+  int min_tile = 0;
+  int stage = 0, stage_sized = 0, stage_glds = 0;
+  bool glds = false;
+  int grid[5] = {0, 0, 0, 0, 0};
+};
+SegcopyGeometry segcopy_geometry();
 
 // GET coalescing: first[i] = the row that serves row i (one row per distinct digest
 // serves all its duplicates). `table` is scratch of coalesce_table_slots(n) u32 words.

@@ -79,6 +79,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 //    as fast as at all of them: memory-bound).
 constexpr int kSegMinTile = 1024;  // 16-B chunks
 constexpr int kSegOcc64 = 48;
+// Segments k_segcopy stages in LDS per pass. Mode 2 stages a length per segment too (fewer
+// segments per pass keep 8 waves/SIMD); the LDS-DMA variant keeps room for its staging area.
+constexpr int seg_stage_cap(int mode, bool glds) {
+  return mode == 2 ? 768 : glds ? 512 : kTileSegCap;
+}
 
 struct DeviceGuard {
   int prev = -1;
@@ -1122,8 +1127,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
     const uint64_t* __restrict__ head_ptr, uint64_t cap, int min_tile, ExpandTail ex) {
   // the copy (a uniform early exit per workgroup skips to the expand tail)
   do {
-  // mode 2 stages a length per segment too: fewer segments per pass keep 8 waves/SIMD
-  constexpr int TSC = MODE == 2 ? 768 : GLDS ? 512 : kTileSegCap;
+  constexpr int TSC = seg_stage_cap(MODE, GLDS);
   __shared__ uint64_t s_off[TSC + 1];
   __shared__ __attribute__((aligned(16))) uint8_t s_stage[GLDS ? kBlock / 64 : 1][GLDS ? U : 1]
                                                          [GLDS ? 1024 : 16];
@@ -1315,21 +1319,36 @@ inline bool seg_glds() {
   return on != 0;
 }
 
+// The workgroups a mode's byte mover is launched with on the current device (the one place
+// that decides it: the launch below and segcopy_geometry() both ask here). `glds` is the
+// LDS-DMA variant (modes 0 / 4 only).
+template <int MODE>
+int segcopy_grid(bool glds) {
+  static int grid[64];
+  const int g =
+      std::max(1, resident_grid(k_segcopy<MODE, 4, 8, true>, grid) * seg_occ64(MODE) / 64);
+  if constexpr (MODE == 0 || MODE == 4) {
+    if (glds) {
+      static int ggrid[64];
+      return std::min(g, resident_grid(k_segcopy<MODE, 4, 8, true, true>, ggrid));
+    }
+  }
+  return g;
+}
+
 template <int MODE, typename... Args>
 void launch_segcopy_ex(hipStream_t s, const ExpandTail& ex, Args... args) {
-  static int grid[64];
   const auto kern = k_segcopy<MODE, 4, 8, true>;
-  const int g = std::max(1, resident_grid(kern, grid) * seg_occ64(MODE) / 64);
   if constexpr (MODE == 0 || MODE == 4) {
     if (seg_glds()) {
-      static int ggrid[64];
       const auto gk = k_segcopy<MODE, 4, 8, true, true>;
-      hipLaunchKernelGGL(gk, dim3(std::min(g, resident_grid(gk, ggrid))), dim3(kBlock), 0, s,
-                         args..., kSegMinTile, ex);
+      hipLaunchKernelGGL(gk, dim3(segcopy_grid<MODE>(true)), dim3(kBlock), 0, s, args...,
+                         kSegMinTile, ex);
       return;
     }
   }
-  hipLaunchKernelGGL(kern, dim3(g), dim3(kBlock), 0, s, args..., kSegMinTile, ex);
+  hipLaunchKernelGGL(kern, dim3(segcopy_grid<MODE>(false)), dim3(kBlock), 0, s, args...,
+                     kSegMinTile, ex);
 }
 template <int MODE, typename... Args>
 void launch_segcopy(hipStream_t s, Args... args) {
@@ -4493,6 +4512,23 @@ uint64_t HbmCache::head(hipStream_t s) {
   HIP_OK(hipMemcpyAsync(host_buf_, cur_head(), sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   return host_buf_[0];
+}
+
+// (after every launch site: it names each mode's kernel and must not reorder them in the
+// code object)
+SegcopyGeometry segcopy_geometry() {
+  SegcopyGeometry g;
+  g.min_tile = kSegMinTile;
+  g.stage = seg_stage_cap(0, false);
+  g.stage_sized = seg_stage_cap(2, false);
+  g.stage_glds = seg_stage_cap(0, true);
+  g.glds = seg_glds();
+  g.grid[0] = segcopy_grid<0>(g.glds);
+  g.grid[1] = segcopy_grid<1>(false);
+  g.grid[2] = segcopy_grid<2>(false);
+  g.grid[3] = segcopy_grid<3>(false);
+  g.grid[4] = segcopy_grid<4>(g.glds);
+  return g;
 }
 
 }  // namespace shellac

@@ -574,11 +574,23 @@ void host_exclusive_scan(const uint64_t* in, uint64_t* out, int64_t n) {
 }
 
 void host_segcopy(const uint8_t* src, const uint64_t* src_off, const uint64_t* dst_off, int64_t n,
-                  uint8_t* dst) {
+                  uint8_t* dst, uint64_t dst_cap) {
+  if (n <= 0 || dst_off[n] > dst_cap) return;  // as the device op: all or nothing
   for (int64_t i = 0; i < n; ++i) {
     const uint64_t sz = dst_off[i + 1] - dst_off[i];
+    if (src_off[i] == kHostSegSkip) continue;  // a gap: nothing read or written
     // integer address math: src may be null with absolute addresses in src_off
     if (sz) std::memcpy(dst + dst_off[i], reinterpret_cast<const uint8_t*>((uintptr_t)src + src_off[i]), sz);
+  }
+}
+
+void host_segcopy_sized(const uint8_t* src, const uint64_t* src_off, const uint64_t* dst_off,
+                        const uint64_t* seg_len, int64_t n, uint8_t* dst, uint64_t cap) {
+  for (int64_t i = 0; i < n; ++i) {
+    // a segment holds at most the room up to the next one; past `cap` it is dropped
+    const uint64_t sz = std::min(seg_len[i], dst_off[i + 1] - dst_off[i]);
+    if (!sz || dst_off[i] + seg_len[i] > cap) continue;
+    std::memcpy(dst + dst_off[i], reinterpret_cast<const uint8_t*>((uintptr_t)src + src_off[i]), sz);
   }
 }
 

@@ -102,8 +102,15 @@ class HostCache {
 
 // CPU versions of the device batch helpers (same contracts as hbm_cache.h).
 void host_exclusive_scan(const uint64_t* in, uint64_t* out, int64_t n);
+// src_off[i] == kHostSegSkip (hbm_cache.h kSegSkip): segment i is a gap, nothing read or
+// written; nothing at all is copied when dst_off[n] > dst_cap.
+constexpr uint64_t kHostSegSkip = ~0ull;
 void host_segcopy(const uint8_t* src, const uint64_t* src_off, const uint64_t* dst_off, int64_t n,
-                  uint8_t* dst);
+                  uint8_t* dst, uint64_t dst_cap = ~0ull);
+// Segment i holds seg_len[i] bytes at dst + dst_off[i]; the bytes up to dst_off[i + 1] are
+// left as they are, and a segment that does not end within `cap` is dropped.
+void host_segcopy_sized(const uint8_t* src, const uint64_t* src_off, const uint64_t* dst_off,
+                        const uint64_t* seg_len, int64_t n, uint8_t* dst, uint64_t cap = ~0ull);
 void host_digest_keys(const uint8_t* bytes, const int64_t* offs, int64_t n, Digest* out);
 void host_route_keys(const Digest* keys, int64_t n, const uint32_t* ring_pts,
                      const int32_t* ring_owner, int32_t npts, int32_t* dest, int64_t* counts,

@@ -45,17 +45,56 @@ def exclusive_scan(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+SEG_SKIP = -1  # src_off of a gap (kSegSkip, all ones): the segment's bytes stay as they are
+_NO_CAP = (1 << 64) - 1
+
+
 def segcopy(src: torch.Tensor, src_off: torch.Tensor, dst_off: torch.Tensor,
-            dst: torch.Tensor) -> torch.Tensor:
+            dst: torch.Tensor, dst_cap: int | None = None) -> torch.Tensor:
     """Copy segment i (dst_off[i+1]-dst_off[i] bytes) from src[src_off[i]:] to dst[dst_off[i]:].
-    Offsets and lengths must be multiples of 16."""
+    Offsets and lengths must be multiples of 16. A segment whose ``src_off`` is ``SEG_SKIP``
+    is a gap; with ``dst_cap`` set, nothing is copied when ``dst_off[n] > dst_cap``."""
     n = src_off.numel()
     assert dst_off.numel() == n + 1
+    cap = _NO_CAP if dst_cap is None else int(dst_cap)
     if src.is_cuda:
         core().segcopy(src.data_ptr(), src_off.data_ptr(), dst_off.data_ptr(), n, dst.data_ptr(),
-                       _s(src))
+                       _s(src), dst_cap=cap)
     else:
-        core().host_segcopy(src.data_ptr(), src_off.data_ptr(), dst_off.data_ptr(), n, dst.data_ptr())
+        core().host_segcopy(src.data_ptr(), src_off.data_ptr(), dst_off.data_ptr(), n,
+                            dst.data_ptr(), dst_cap=cap)
+    return dst
+
+
+def segcopy_sized(src: torch.Tensor, src_off: torch.Tensor, dst_off: torch.Tensor,
+                  seg_len: torch.Tensor, dst: torch.Tensor, cap: int | None = None) -> torch.Tensor:
+    """Like ``segcopy`` but segment i holds only ``seg_len[i]`` bytes at ``dst[dst_off[i]:]``
+    (at most the room up to ``dst_off[i+1]``; the rest of that room is left as it is), and a
+    segment that does not end within ``cap`` is dropped while the others still land."""
+    n = src_off.numel()
+    assert dst_off.numel() == n + 1 and seg_len.numel() == n
+    cap = _NO_CAP if cap is None else int(cap)
+    if src.is_cuda:
+        core().segcopy_sized(src.data_ptr(), src_off.data_ptr(), dst_off.data_ptr(),
+                             seg_len.data_ptr(), n, dst.data_ptr(), _s(src), cap=cap)
+    else:
+        core().host_segcopy_sized(src.data_ptr(), src_off.data_ptr(), dst_off.data_ptr(),
+                                  seg_len.data_ptr(), n, dst.data_ptr(), cap=cap)
+    return dst
+
+
+def segcopy_dev(addrs: torch.Tensor, dst_off: torch.Tensor, n_dev: torch.Tensor,
+                dst: torch.Tensor, dst_cap: int | None = None) -> torch.Tensor:
+    """``gather_segments`` whose segment count is the int64 word ``n_dev`` on dst's device,
+    read by the kernel: entries of ``addrs`` / ``dst_off`` past it are never looked at."""
+    assert n_dev.dtype == torch.int64 and n_dev.numel() == 1 and addrs.dtype == torch.int64
+    cap = _NO_CAP if dst_cap is None else int(dst_cap)
+    if dst.is_cuda:
+        core().segcopy_dev(addrs.data_ptr(), dst_off.data_ptr(), n_dev.data_ptr(), dst.data_ptr(),
+                           _s(dst), dst_cap=cap)
+    else:
+        core().host_segcopy(0, addrs.data_ptr(), dst_off.data_ptr(), int(n_dev.item()),
+                            dst.data_ptr(), dst_cap=cap)
     return dst
 
 
