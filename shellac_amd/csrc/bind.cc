@@ -204,12 +204,16 @@ PYBIND11_MODULE(_shellac_core, m) {
                        uintptr_t append_after, uintptr_t append_done, int phase,
                        uintptr_t plan_done, uintptr_t done) {
         py::gil_scoped_release nogil;
+        StoreOpts o;
+        o.index_after = reinterpret_cast<hipEvent_t>(index_after);
+        o.append_after = reinterpret_cast<hipEvent_t>(append_after);
+        o.append_done = reinterpret_cast<hipEvent_t>(append_done);
+        o.plan_done = reinterpret_cast<hipEvent_t>(plan_done);
+        o.done = reinterpret_cast<hipEvent_t>(done);
+        o.phase = phase;
         c.store(P<const Digest>(keys), P<const uint8_t>(values), P<const uint64_t>(val_off),
                 P<const uint32_t>(vlen), P<const uint32_t>(flags), P<const uint32_t>(expire), n,
-                bytes_bound, now, S(s), reinterpret_cast<hipEvent_t>(index_after), true,
-                reinterpret_cast<hipEvent_t>(append_after),
-                reinterpret_cast<hipEvent_t>(append_done), phase,
-                reinterpret_cast<hipEvent_t>(plan_done), reinterpret_cast<hipEvent_t>(done));
+                bytes_bound, now, S(s), o);
       }, py::arg("keys"), py::arg("values"), py::arg("val_off"), py::arg("vlen"),
          py::arg("flags"), py::arg("expire"), py::arg("n"), py::arg("bytes_bound"), py::arg("now"),
          py::arg("stream"), py::arg("index_after") = 0, py::arg("append_after") = 0,

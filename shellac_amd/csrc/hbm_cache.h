@@ -39,6 +39,43 @@ struct ShardConfig {
   int serve_blocks = 8;       // resident edge-server blocks (serve_get jobs side by side)
 };
 
+// What HbmCache::store waits for, completes and queues beyond the plain chain (all optional).
+struct StoreOpts {
+  // The chain up to the log write runs at once, the index insert waits for this event. A
+  // lookup enqueued (on another stream) before this store and followed by the event
+  // therefore runs concurrently with the SET's dedupe, sizing and log append: it reads the
+  // index and the current head slot, which only the index insert changes, and a `reserve`
+  // covering this SET keeps its gather off the bytes the append overwrites.
+  hipEvent_t index_after = nullptr;
+  // The log append (and what follows) waits for this event; the CLOCK hand, the dedupe and
+  // the sizing (reads only) run at once — beside a gather that still reads the region the
+  // append will overwrite.
+  hipEvent_t append_after = nullptr;
+  // Recorded right after the log append (a caller can keep its gather from contending with
+  // it).
+  hipEvent_t append_done = nullptr;
+  // Recorded after the batch's planning kernels (dedupe, sizes, offsets).
+  hipEvent_t plan_done = nullptr;
+  // Completes with everything this call queued; carried by the chain's last kernel as its
+  // completion signal (profiles/r6_hop: ~2.4 us sooner across queues than a recorded
+  // event), or recorded when the call queued no chain.
+  hipEvent_t done = nullptr;
+  // 1 queues only the batch's CLOCK hand and planning, 2 the rest of its chain (0: both).
+  // A phase-1 hand is *detached*: it may run as soon as the previous batch's planning is
+  // done (`plan_done` of that batch's phase 2), beside that batch's log append and index
+  // insert. It reads the head the previous append will reach (the claim word) and the ring
+  // tail of the batch before (the last one whose ring entries are written), and its
+  // reinsertions are indexed as *moves*: a reinsertion row's insert CASes the entry from
+  // the item's old location to the new one, and is dropped when the entry has moved on
+  // (a SET or DELETE of the key landed after the hand read the index) — so an early hand
+  // can never resurrect a superseded or deleted value. Two hand buffers alternate, so the
+  // hand of batch k+1 never writes what batch k's append still reads.
+  int phase = 0;
+  // false: no CLOCK hand this batch (the append stays within `bytes_bound`; a caller that
+  // reserved only that much for it, see would_reclaim).
+  bool allow_reclaim = true;
+};
+
 class HbmCache {
  public:
   explicit HbmCache(const ShardConfig& cfg);
@@ -177,39 +214,11 @@ class HbmCache {
               int shift = 0, int64_t table_slots = 0);
   // SET a batch. values + val_off[i] holds vlen[i] bytes (val_off 16-byte aligned,
   // the buffer readable 16 bytes past every value). Later duplicates of a key in
-  // the same batch win. `bytes_bound` must bound sum(item_bytes(vlen)).
-  // `index_after`: the chain up to the log write runs at once, the index insert waits
-  // for this event. A lookup enqueued (on another stream) before this store and
-  // followed by the event therefore runs concurrently with the SET's dedupe, sizing
-  // and log append: it reads the index and the current head slot, which only the index
-  // insert changes, and a `reserve` covering this SET keeps its gather off the bytes
-  // the append overwrites.
-  // `allow_reclaim` false: no CLOCK hand this batch (the append stays within
-  // `bytes_bound`; a caller that reserved only that much for it, see would_reclaim).
-  // `append_after`: the log append (and what follows) waits for this event; the CLOCK
-  // hand, the dedupe and the sizing (reads only) run at once — beside a gather that
-  // still reads the region the append will overwrite. `append_done`: recorded right after
-  // the log append (a caller can keep its gather from contending with it).
-  // `phase` 1 queues only the batch's CLOCK hand, 2 the rest of its chain (0: both).
-  // A phase-1 hand is *detached*: it may run as soon as the previous batch's planning is
-  // done (`plan_done` of that batch's phase 2), beside that batch's log append and index
-  // insert. It reads the head the previous append will reach (the claim word) and the ring
-  // tail of the batch before (the last one whose ring entries are written), and its
-  // reinsertions are indexed as *moves*: a reinsertion row's insert CASes the entry from
-  // the item's old location to the new one, and is dropped when the entry has moved on
-  // (a SET or DELETE of the key landed after the hand read the index) — so an early hand
-  // can never resurrect a superseded or deleted value. Two hand buffers alternate, so the
-  // hand of batch k+1 never writes what batch k's append still reads.
-  // `plan_done`: recorded after the batch's planning kernels (dedupe, sizes, offsets).
-  // `done`: completes with everything this call queued; carried by the chain's last kernel
-  // as its completion signal (profiles/r6_hop: ~2.4 us sooner across queues than a
-  // recorded event), or recorded when the call queued no chain.
+  // the same batch win. `bytes_bound` must bound sum(item_bytes(vlen)). `o`: the events
+  // the chain waits for and completes, and which part of it this call queues (StoreOpts).
   void store(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
              const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire, int64_t n,
-             uint64_t bytes_bound, uint32_t now, hipStream_t s, hipEvent_t index_after = nullptr,
-             bool allow_reclaim = true, hipEvent_t append_after = nullptr,
-             hipEvent_t append_done = nullptr, int phase = 0, hipEvent_t plan_done = nullptr,
-             hipEvent_t done = nullptr);
+             uint64_t bytes_bound, uint32_t now, hipStream_t s, const StoreOpts& o = {});
   // Whether a SET of `bytes_bound` bytes issued now would run the CLOCK hand (the log is
   // within a few batches of wrapping); the answer can only turn true later.
   bool would_reclaim(uint64_t bytes_bound) const {
@@ -300,10 +309,6 @@ class HbmCache {
   void ensure_rc_ws(int64_t w, hipStream_t s);
   void ensure_cb(int b, int64_t rows, hipStream_t s);
   bool should_reclaim(uint64_t bytes_bound) const;
-  void reclaim_locked(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
-                      const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire,
-                      int64_t n, int64_t w, uint64_t rmax, uint32_t now, hipStream_t s,
-                      bool detached, bool lead);
   uint64_t* cur_ring_tail() const { return head_ + 2 + hsel_; }
   uint64_t* next_ring_tail() const { return head_ + 2 + (hsel_ ^ 1); }
   // Deferred frees (no device-wide synchronisation on the serving path): a grown buffer's
@@ -319,7 +324,17 @@ class HbmCache {
     std::vector<hipEvent_t> ev;
     uint64_t bytes = 0;
   };
-  void retire_group(std::initializer_list<void*> ptrs, uint64_t bytes, hipStream_t s);
+  // One buffer of a growable set: where its pointer lives and its bytes at a capacity of
+  // the set. A set's table (set_bufs, hand_bufs, rc_bufs) is its only list: growth, the
+  // retired-bytes figure and the destructor all walk it.
+  struct Buf {
+    void** p;
+    uint64_t (*bytes)(uint64_t cap);
+  };
+  using BufSet = std::vector<Buf>;
+  // Retires the set's blocks of capacity `old_cap` (if any), then allocates `cap`.
+  void grow_bufs(const BufSet& set, int64_t old_cap, int64_t cap, hipStream_t s);
+  void retire_group(const BufSet& set, int64_t cap, hipStream_t s);
   void reap_retired(bool all);
   void note_stream(hipStream_t s);
   void note_store_end(hipStream_t s);
@@ -345,21 +360,25 @@ class HbmCache {
   uint64_t rmax_ = 0;
   int64_t rc_cap_ = 0;
   uint64_t *rc_loc_ = nullptr, *rc_h_ = nullptr, *rc_part_ = nullptr, *rc_hx_ = nullptr;
-  int64_t rc_adv_w_ = 0;
-  // store(phase=1) queued a batch's CLOCK hand and planning; store(phase=2) runs the rest
-  // of its chain (append, index insert) from this record
+  BufSet rc_bufs();
+  // A batch between its planning and its tail (append, index insert): the rows the chain
+  // runs on and the buffers it planned into. A batch with a hand is the combined one:
+  // `nmove` reinsertion rows (moves), then the caller's `n`, all in hand buffer `hand`.
   struct Pending {
-    bool active = false;
-    int64_t n = 0, rows = 0, nmove = 0;  // caller rows; rows of the (combined) batch; moves
-    int parity = 0;                       // its SET workspace and hand buffer
     const Digest* keys = nullptr;
     const uint8_t* values = nullptr;
     const uint64_t* voff = nullptr;
     const uint32_t *vlen = nullptr, *flags = nullptr, *expire = nullptr;
+    int64_t n = 0, rows = 0;       // caller rows; rows of the (combined) batch
     const uint64_t* from = nullptr;
+    int64_t nmove = 0;
+    int ws = 0;                    // its SET workspace (ws_)
+    int hand = -1;                 // its hand buffer (hb_), -1: the hand did not run
+    bool active = false;           // pend_ only: a phase 1 waits for its phase 2
   };
+  // store(phase=1) queued a batch's CLOCK hand and planning; store(phase=2) runs the rest
+  // of its chain from this record
   Pending pend_;
-  int hand_b_ = 0;  // the hand buffer reclaim_locked fills
   // The combined SET batch (reinsertion rows, then the batch's own rows) and the staged
   // reinsertion records, two buffers taken in turn (a detached hand fills one while the
   // previous batch's chain still reads the other). `from`: a reinsertion row's old entry
@@ -373,22 +392,20 @@ class HbmCache {
     uint8_t* scratch = nullptr;  // staged reinsertions (rmax_ + 64 bytes)
   };
   HandBuf hb_[2];
+  static BufSet hand_bufs(HandBuf& h);  // (not `scratch`: fixed size, freed with the cache)
   // SET workspaces, two taken in turn by consecutive batches (ws_next_): a batch's planning
   // (phase 1) may run while the previous batch's append and index insert still use theirs.
-  // The dd_* / set_* members below point at the one in use (select_ws).
+  // A graph (store_graph) bakes its workspace in: always the first.
   struct SetWs {
     uint32_t* dd_tab = nullptr;   // dedupe table: 0 = empty, else the key's last row + 1
     uint32_t* dd_slot = nullptr;
-    uint64_t *set_size = nullptr, *set_off = nullptr, *set_cnt = nullptr;
-    uint32_t* set_claim = nullptr;
+    uint64_t *set_size = nullptr, *set_off = nullptr;
+    uint32_t* set_claim = nullptr;  // entry each SET row claimed (k_set_fixup)
+    uint64_t* set_cnt = nullptr;    // ring ordinal of each stored SET row (CLOCK)
   };
   SetWs ws_[2];
   int ws_next_ = 0;
-  void select_ws(int p) {
-    const SetWs& w = ws_[p];
-    dd_tab_ = w.dd_tab; dd_slot_ = w.dd_slot; set_size_ = w.set_size;
-    set_off_ = w.set_off; set_cnt_ = w.set_cnt; set_claim_ = w.set_claim;
-  }
+  static BufSet set_bufs(SetWs& w);
 
   ShardConfig cfg_;
   uint8_t* log_ = nullptr;
@@ -419,34 +436,23 @@ class HbmCache {
   void serve_launch_locked();
   unsigned int* done_ctr_ = nullptr; // device: edge-GET workgroups finished + fail flag (self-resetting)
   unsigned long long* lb_state_ = nullptr;  // device: edge-GET look-back words (self-resetting)
-  // SET workspace
+  // SET workspaces (ws_): rows either holds, and the mask of their dedupe tables
   int64_t set_cap_ = 0;
-  uint32_t* dd_tab_ = nullptr;
-  uint32_t* dd_slot_ = nullptr;
-  uint64_t* set_size_ = nullptr;
-  uint64_t* set_off_ = nullptr;
-  uint32_t* set_claim_ = nullptr;  // entry each SET row claimed (k_set_fixup)
-  uint64_t* set_cnt_ = nullptr;    // ring ordinal of each stored SET row (CLOCK)
   uint32_t dd_mask_ = 0;
   uint64_t ws_gen_ = 0;  // bumped when the SET workspace moves (invalidates graphs)
   std::mutex mu_;
-  // store(done): the event the call's last kernel carries as its completion signal (taken
-  // by that launch; recorded by a marker if the path queued no such kernel)
-  hipEvent_t stop_ev_ = nullptr;
-  void store_locked(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
-                    const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire,
-                    int64_t n, uint32_t now, hipStream_t s, hipEvent_t index_after = nullptr,
-                    hipEvent_t append_after = nullptr, hipEvent_t append_done = nullptr,
-                    const uint64_t* from = nullptr, hipEvent_t plan_done = nullptr,
-                    int64_t nmove = 0);
-  void store_plan_locked(const Digest* keys, const uint32_t* vlen, int64_t n, hipStream_t s,
-                         bool detached = false);
-  void store_tail_locked(uint32_t now, hipStream_t s, hipEvent_t index_after,
-                         hipEvent_t append_after, hipEvent_t append_done);
-  void store_index_locked(const Digest* keys, const uint32_t* vlen, const uint32_t* expire,
-                          int64_t n, uint32_t now, hipStream_t s, hipEvent_t index_after,
-                          const uint64_t* from = nullptr, int64_t nmove = 0,
-                          int win_parity = -1);
+  // The SET chain, one for every caller (store in each phase, store_graph's capture):
+  // reclaim_locked (the CLOCK hand, turning the caller's batch into the combined one), then
+  // store_plan_locked (dedupe, sizes, offsets), then store_tail_locked (log append, then
+  // store_index_locked: index insert and fix-up). `done` (store's; null, or pointing at
+  // null: none) is taken by the launch that carries it.
+  Pending reclaim_locked(const Pending& own, int64_t w, uint64_t rmax, uint32_t now,
+                         hipStream_t s, bool detached);
+  void store_plan_locked(const Pending& p, hipStream_t s, bool detached);
+  void store_tail_locked(const Pending& p, uint32_t now, hipStream_t s, const StoreOpts& o,
+                         hipEvent_t* done);
+  void store_index_locked(const Pending& p, uint32_t now, hipStream_t s,
+                          hipEvent_t index_after, hipEvent_t* done);
 };
 
 // ---- Generic device kernels used by the distributed serving path ----------------

@@ -19,8 +19,8 @@
 //   k_set_dedupe   batch-local open-addressing table, one word per slot (the key's
 //                  last row + 1; the key is read through that row): the last SET of a
 //                  key in a batch wins (request order = memcached/HTTP pipelining order).
-//   k_set_copy     load-balanced writer of [ItemHeader|value] into the log at
-//                  head + exclusive-scan(item sizes): batch allocation is a scan.
+//   k_segcopy<1>   (the SET append) load-balanced writer of [ItemHeader|value] into the
+//                  log at head + exclusive-scan(item sizes): batch allocation is a scan.
 //   k_set_index    4 lanes per key: two-choice insert with a 64-bit CAS on the
 //                  entry's loc word; replaces the key's own entry, else a dead
 //                  slot in the emptier bucket, else evicts the oldest item;
@@ -3523,29 +3523,71 @@ HbmCache::~HbmCache() {
   (void)hipFree(part_);
   (void)hipHostFree(host_buf_);
   (void)hipHostFree(host_slots_);
-  for (SetWs& w : ws_)
-    for (void* p : {(void*)w.dd_tab, (void*)w.dd_slot, (void*)w.set_size,
-                    (void*)w.set_off, (void*)w.set_claim, (void*)w.set_cnt})
-      (void)hipFree(p);
   (void)hipFree(ring_); (void)hipFree(rc_ctl_);
-  for (void* p : {(void*)rc_loc_, (void*)rc_h_, (void*)rc_part_, (void*)rc_hx_}) (void)hipFree(p);
-  for (HandBuf& b : hb_)
-    for (void* p : {(void*)b.keys, (void*)b.voff, (void*)b.from, (void*)b.vlen, (void*)b.flags,
-                    (void*)b.expire, (void*)b.scratch})
-      (void)hipFree(p);
+  const auto free_bufs = [](const BufSet& set) {
+    for (const Buf& b : set) (void)hipFree(*b.p);
+  };
+  free_bufs(rc_bufs());
+  for (SetWs& w : ws_) free_bufs(set_bufs(w));
+  for (HandBuf& h : hb_) {
+    free_bufs(hand_bufs(h));
+    (void)hipFree(h.scratch);
+  }
   reap_retired(true);
   if (ws_ready_) (void)hipEventDestroy(ws_ready_);
   for (const SetStream& x : set_streams_)
     if (x.last) (void)hipEventDestroy(x.last);
 }
 
-void HbmCache::retire_group(std::initializer_list<void*> ptrs, uint64_t bytes, hipStream_t s) {
+// The growable buffer sets: each buffer with its bytes at a capacity of `cap` rows (SetWs,
+// HandBuf) or window entries (the hand-scan workspace).
+#define SH_BUF(ptr, expr) \
+  Buf { reinterpret_cast<void**>(&(ptr)), [](uint64_t cap) -> uint64_t { return expr; } }
+HbmCache::BufSet HbmCache::set_bufs(SetWs& w) {
+  return {SH_BUF(w.dd_tab, 2 * cap * sizeof(uint32_t)),  // slots: a power of two >= 2 x rows
+          SH_BUF(w.dd_slot, cap * sizeof(uint32_t)),
+          SH_BUF(w.set_size, (cap + 1) * sizeof(uint64_t)),
+          SH_BUF(w.set_off, (cap + 1) * sizeof(uint64_t)),
+          SH_BUF(w.set_claim, cap * sizeof(uint32_t)),
+          SH_BUF(w.set_cnt, (cap + 1) * sizeof(uint64_t))};
+}
+HbmCache::BufSet HbmCache::hand_bufs(HandBuf& h) {
+  return {SH_BUF(h.keys, cap * sizeof(Digest)), SH_BUF(h.voff, cap * 8),
+          SH_BUF(h.from, cap * 8),              SH_BUF(h.vlen, cap * 4),
+          SH_BUF(h.flags, cap * 4),             SH_BUF(h.expire, cap * 4)};
+}
+HbmCache::BufSet HbmCache::rc_bufs() {
+  return {SH_BUF(rc_loc_, cap * 8), SH_BUF(rc_h_, cap * 8),
+          SH_BUF(rc_part_, (cap / kBlock + 5) * 8),  // + K - 1 sub-blocks of the scan
+          SH_BUF(rc_hx_, (cap + 1) * 8)};
+}
+#undef SH_BUF
+
+// Buffers grow without a device synchronisation: queued work on any stream may still read
+// the old blocks, so they are retired until the chains' events say they finished.
+void HbmCache::grow_bufs(const BufSet& set, int64_t old_cap, int64_t cap, hipStream_t s) {
+  retire_group(set, old_cap, s);
+  for (const Buf& b : set) HIP_OK(hipMalloc(b.p, b.bytes((uint64_t)cap)));
+}
+
+namespace {
+// The capacity a set of `cap` rows (0: none yet, start at `first`) doubles to for `want`.
+int64_t grown_cap(int64_t cap, int64_t want, int64_t first) {
+  int64_t c = cap ? cap : first;
+  while (c < want) c *= 2;
+  return c;
+}
+}  // namespace
+
+void HbmCache::retire_group(const BufSet& set, int64_t cap, hipStream_t s) {
   RetiredGroup g;
-  for (void* p : ptrs)
-    if (p) g.ptrs.push_back(p);
+  for (const Buf& b : set)
+    if (*b.p) {
+      g.ptrs.push_back(*b.p);
+      g.bytes += b.bytes((uint64_t)cap);
+    }
   if (g.ptrs.empty()) return;
-  g.bytes = bytes;
-  retired_ever_ += bytes;
+  retired_ever_ += g.bytes;
   // the growing stream waits for the other SET streams' last stores (their events, not
   // their streams: a stream a caller has destroyed is never touched), then one event
   for (const SetStream& x : set_streams_)
@@ -3612,20 +3654,11 @@ uint64_t HbmCache::hbm_bytes() const {
          ring_cap_ * sizeof(uint64_t) + (hb_[0].scratch ? 2 * (rmax_ + 64) : 0);
 }
 
-// Hand-step workspace for windows of w ring entries. Buffers grow without a device
-// synchronisation: the old blocks are retired (freed with the cache), since queued work on
-// any stream may still read them.
+// Hand-step workspace for windows of w ring entries.
 void HbmCache::ensure_rc_ws(int64_t w, hipStream_t s) {
   if (w <= rc_cap_) return;
-  int64_t cap = rc_cap_ ? rc_cap_ : 4096;
-  while (cap < w) cap *= 2;
-  const uint64_t oc = (uint64_t)rc_cap_;
-  retire_group({rc_loc_, rc_h_, rc_part_, rc_hx_}, oc * 8 * 2 + (oc / kBlock + 5) * 8 + (oc + 1) * 8,
-               s);
-  HIP_OK(hipMalloc(&rc_loc_, cap * 8));
-  HIP_OK(hipMalloc(&rc_h_, cap * 8));
-  HIP_OK(hipMalloc(&rc_part_, (cap / kBlock + 5) * 8));  // + K - 1 sub-blocks of the scan
-  HIP_OK(hipMalloc(&rc_hx_, (cap + 1) * 8));
+  const int64_t cap = grown_cap(rc_cap_, w, 4096);
+  grow_bufs(rc_bufs(), rc_cap_, cap, s);
   rc_cap_ = cap;
 }
 
@@ -3633,15 +3666,8 @@ void HbmCache::ensure_rc_ws(int64_t w, hipStream_t s) {
 void HbmCache::ensure_cb(int b, int64_t rows, hipStream_t s) {
   HandBuf& h = hb_[b];
   if (rows <= h.cap) return;
-  int64_t cap = h.cap ? h.cap : 4096;
-  while (cap < rows) cap *= 2;
-  retire_group({h.keys, h.voff, h.from, h.vlen, h.flags, h.expire}, (uint64_t)h.cap * 44, s);
-  HIP_OK(hipMalloc(&h.keys, cap * sizeof(Digest)));
-  HIP_OK(hipMalloc(&h.voff, cap * 8));
-  HIP_OK(hipMalloc(&h.from, cap * 8));
-  HIP_OK(hipMalloc(&h.vlen, cap * 4));
-  HIP_OK(hipMalloc(&h.flags, cap * 4));
-  HIP_OK(hipMalloc(&h.expire, cap * 4));
+  const int64_t cap = grown_cap(h.cap, rows, 4096);
+  grow_bufs(hand_bufs(h), h.cap, cap, s);
   h.cap = cap;
 }
 
@@ -3657,18 +3683,20 @@ bool HbmCache::should_reclaim(uint64_t bytes_bound) const {
   return h + 4 * (bytes_bound + rmax_) > cfg_.log_bytes;
 }
 
-void HbmCache::reclaim_locked(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
-                              const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire,
-                              int64_t n, int64_t w, uint64_t rmax, uint32_t now, hipStream_t s,
-                              bool detached, bool lead) {
+// Queues the CLOCK hand for the caller's batch `own` with a window of w ring entries, into
+// hand buffer own.hand (sized by the caller), and returns the combined batch: the
+// reinsertions first (log order), then the batch's rows (its SETs win). The combined batch's
+// dedupe advances the hand by its `nmove`.
+HbmCache::Pending HbmCache::reclaim_locked(const Pending& own, int64_t w, uint64_t rmax,
+                                           uint32_t now, hipStream_t s, bool detached) {
   // The head: the claim word, i.e. the head every queued append will have reached (equal to
   // the head slot once they have run). The ring tail: a detached hand may run before the
   // previous batch's fixup writes its ring entries and tail, so it reads the tail of the
   // batch before that one (the other ping-pong slot), whose entries are written.
-  RcArgs a{ring_, ring_cap_ - 1, detached ? next_ring_tail() : cur_ring_tail(), rc_ctl_, w, n,
-           hand_b_, claim_ptr(), cfg_.log_bytes, now, rmax, lead ? 1ull : 0ull};
+  RcArgs a{ring_, ring_cap_ - 1, detached ? next_ring_tail() : cur_ring_tail(), rc_ctl_, w,
+           own.n, own.hand, claim_ptr(), cfg_.log_bytes, now, rmax, lead_ ? 1ull : 0ull};
   const int g = (int)((w + kBlock - 1) / kBlock);
-  const HandBuf& hb = hb_[hand_b_];
+  const HandBuf& hb = hb_[own.hand];
   const RcBatch cb{hb.keys, hb.voff, hb.vlen, hb.flags, hb.expire, hb.from};
   // window entries per lane of the scan (SHELLAC_RCSCAN_K: A/B experiments); its part_h stays
   // one word per 256 entries, rc_part_ is sized for g + K of them
@@ -3677,53 +3705,34 @@ void HbmCache::reclaim_locked(const Digest* keys, const uint8_t* values, const u
     const int v = e ? atoi(e) : kRcScanK;
     return v == 1 || v == 2 || v == 4 ? v : kRcScanK;
   }();
-  const int gk = (g + rk - 1) / rk;
-  if (rk == 4)
-    hipLaunchKernelGGL(k_rc_scan<4>, dim3(gk), dim3(kBlock), 0, s, a, cb, log_, index_,
-                       cfg_.nbuckets - 1, keys, values, val_off, vlen, flags, expire, n,
-                       cfg_.max_item, rc_loc_, rc_h_, rc_part_);
-  else if (rk == 2)
-    hipLaunchKernelGGL(k_rc_scan<2>, dim3(gk), dim3(kBlock), 0, s, a, cb, log_, index_,
-                       cfg_.nbuckets - 1, keys, values, val_off, vlen, flags, expire, n,
-                       cfg_.max_item, rc_loc_, rc_h_, rc_part_);
-  else
-    hipLaunchKernelGGL(k_rc_scan<1>, dim3(gk), dim3(kBlock), 0, s, a, cb, log_, index_,
-                       cfg_.nbuckets - 1, keys, values, val_off, vlen, flags, expire, n,
-                       cfg_.max_item, rc_loc_, rc_h_, rc_part_);
+  auto scan = k_rc_scan<4>;
+  if (rk == 2) scan = k_rc_scan<2>;
+  if (rk == 1) scan = k_rc_scan<1>;
+  hipLaunchKernelGGL(scan, dim3((g + rk - 1) / rk), dim3(kBlock), 0, s, a, cb, log_, index_,
+                     cfg_.nbuckets - 1, own.keys, own.values, own.voff, own.vlen, own.flags,
+                     own.expire, own.n, cfg_.max_item, rc_loc_, rc_h_, rc_part_);
   hipLaunchKernelGGL(k_rc_emit, dim3(g), dim3(kBlock), 0, s, a, cb, log_, rc_loc_, rc_h_,
                      rc_part_, rc_hx_, hb.scratch, ctr_);
-  if (!lead)
+  if (!lead_)
     launch_segcopy<2>(s, log_, rc_loc_, rc_hx_, w, hb.scratch, nullptr, nullptr, nullptr,
                       nullptr, rc_h_, rmax);
-  rc_adv_w_ = w;  // the combined batch's dedupe advances the hand
   HIP_OK(hipGetLastError());
+  return Pending{hb.keys, nullptr, hb.voff,  hb.vlen, hb.flags, hb.expire,
+                 own.n,   w + own.n, hb.from, w,      own.ws,   own.hand};
 }
 
 void HbmCache::ensure_set_ws(int64_t n, hipStream_t s) {
   if (n <= set_cap_) return;
-  int64_t cap = set_cap_ ? set_cap_ : 1024;
-  while (cap < n) cap *= 2;
-  const uint64_t tslots = (uint64_t)cap * 2;
-  const uint64_t oc = (uint64_t)set_cap_;
+  const int64_t cap = grown_cap(set_cap_, n, 1024);
   for (SetWs& w : ws_) {
-    // the old workspace may still be read by queued SET chains on other streams: retired
-    // until their events say they finished (no device synchronisation on the serving path)
-    retire_group({w.dd_tab, w.dd_slot, w.set_size, w.set_off, w.set_claim, w.set_cnt},
-                 2 * oc * 4 + oc * 8 + 3 * (oc + 1) * 8, s);
-    HIP_OK(hipMalloc(&w.dd_tab, tslots * sizeof(uint32_t)));
+    grow_bufs(set_bufs(w), set_cap_, cap, s);
     // the table is cleared once here, on the stream of the SET that first uses it
     // (ordered before its dedupe; the null stream is not: a non-blocking stream does not
     // wait for it, which once dropped the first batch's rows); k_set_index resets every
     // slot a batch used
-    HIP_OK(hipMemsetAsync(w.dd_tab, 0, tslots * sizeof(uint32_t), s));
-    HIP_OK(hipMalloc(&w.dd_slot, cap * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&w.set_size, (cap + 1) * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(&w.set_off, (cap + 1) * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(&w.set_claim, cap * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&w.set_cnt, (cap + 1) * sizeof(uint64_t)));
+    HIP_OK(hipMemsetAsync(w.dd_tab, 0, (size_t)cap * 2 * sizeof(uint32_t), s));
   }
-  select_ws(0);
-  dd_mask_ = (uint32_t)(tslots - 1);
+  dd_mask_ = (uint32_t)(cap * 2 - 1);
   set_cap_ = cap;
   ++ws_gen_;
   // a store on another stream waits for these clears (the dedupe tables were
@@ -4046,12 +4055,10 @@ void HbmCache::gather(const uint64_t* loc, const uint64_t* off, int64_t n, uint8
 void HbmCache::store(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
                      const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire,
                      int64_t n, uint64_t bytes_bound, uint32_t now, hipStream_t s,
-                     hipEvent_t index_after, bool allow_reclaim, hipEvent_t append_after,
-                     hipEvent_t append_done, int phase, hipEvent_t plan_done,
-                     hipEvent_t done) {
+                     const StoreOpts& o) {
   TraceRange tr("hbm.store");
   if (n <= 0) {
-    if (done) HIP_OK(hipEventRecord(done, s));  // nothing queued to carry it
+    if (o.done) HIP_OK(hipEventRecord(o.done, s));  // nothing queued to carry it
     return;
   }
   SH_CHECK(bytes_bound <= cfg_.log_bytes / 2,
@@ -4059,174 +4066,131 @@ void HbmCache::store(const Digest* keys, const uint8_t* values, const uint64_t* 
   std::lock_guard<std::mutex> lk(mu_);
   DeviceGuard g(cfg_.device);
   note_stream(s);
-  stop_ev_ = done;  // the chain's last kernel (the index fix-up) takes it
   struct EndMark {  // the stream's `last` event, after whatever this call queues
     HbmCache* c;
     hipStream_t s;
+    hipEvent_t done;  // the chain's last kernel (the index fix-up) takes it
     ~EndMark() {
-      if (c->stop_ev_) {  // no chain kernel took `done`
-        (void)hipEventRecord(c->stop_ev_, s);
-        c->stop_ev_ = nullptr;
-      }
+      if (done) (void)hipEventRecord(done, s);  // no chain kernel took it
       c->note_store_end(s);
     }
-  } end_mark{this, s};
+  } end_mark{this, s, o.done};
   if (!retired_.empty()) reap_retired(false);  // grown-out workspaces whose chains finished
-  // phase 2: the rest of the chain of the batch a phase-1 call planned
-  if (phase == 2) {
+  Pending p{keys, values, val_off, vlen, flags, expire, n, n};
+  if (o.phase == 2) {  // the rest of the chain of the batch a phase-1 call planned
     SH_CHECK(pend_.active && pend_.n == n, "store phase 2 without the same batch's phase 1");
-    store_tail_locked(now, s, index_after, append_after, append_done);
-    return;
-  }
-  SH_CHECK(!pend_.active, "store: a phase-1 batch is still waiting for its phase 2");
-  // the CLOCK hand's reinsertions share the half-log bound with the batch
-  const uint64_t rmax = std::min<uint64_t>(rmax_, cfg_.log_bytes / 2 - bytes_bound) / 16 * 16;
-  const bool hand = allow_reclaim && rmax && should_reclaim(bytes_bound);
-  lead_ = hand_lead(cfg_.log_bytes, bytes_bound, rmax, lead_);  // every batch, as HostCache
-  if (!hand && phase == 0 && n <= kSmallSetRows && !index_after && !append_after &&
-      !append_done && !plan_done) {
-    // one launch for the whole chain (the proxy's small SET batches)
-    hipLaunchKernelGGL(k_set_small, dim3(1), dim3(kBlock), 0, s, keys, values, val_off, vlen,
-                       flags, expire, (int)n, cfg_.max_item, index_, cfg_.nbuckets - 1,
-                       cur_head(), next_head(),
-                       reinterpret_cast<unsigned long long*>(claim_ptr()), cfg_.log_bytes, now,
-                       log_, ring_, ring_ ? ring_cap_ - 1 : 0ull, cur_ring_tail(),
-                       next_ring_tail(), host_slots_ + kHeadSlot, ctr_);
-    HIP_OK(hipGetLastError());
-    hsel_ ^= 1;
-    return;
-  }
-  // consecutive batches take the two SET workspaces and hand buffers in turn
-  Pending p;
-  p.active = true;
-  p.n = n;
-  p.parity = ws_next_;
-  ws_next_ ^= 1;
-  const bool detached = phase == 1;
-  if (hand) {
-    const int64_t w = hand_window(n);
-    ensure_rc_ws(w, s);
-    hand_b_ = p.parity;
-    ensure_cb(hand_b_, w + n, s);
-    ensure_set_ws(w + n, s);
-    reclaim_locked(keys, values, val_off, vlen, flags, expire, n, w, rmax, now, s, detached,
-                   lead_);
-    // combined batch: reinsertions first (log order), then the batch (its SETs win)
-    const HandBuf& hb = hb_[hand_b_];
-    p.rows = w + n;
-    p.nmove = w;
-    p.keys = hb.keys;
-    p.values = nullptr;
-    p.voff = hb.voff;
-    p.vlen = hb.vlen;
-    p.flags = hb.flags;
-    p.expire = hb.expire;
-    p.from = hb.from;
+    p = pend_;
+    pend_.active = false;
   } else {
-    ensure_set_ws(n, s);
-    p.rows = n;
-    p.keys = keys;
-    p.values = values;
-    p.voff = val_off;
-    p.vlen = vlen;
-    p.flags = flags;
-    p.expire = expire;
+    SH_CHECK(!pend_.active, "store: a phase-1 batch is still waiting for its phase 2");
+    // the CLOCK hand's reinsertions share the half-log bound with the batch
+    const uint64_t rmax =
+        std::min<uint64_t>(rmax_, cfg_.log_bytes / 2 - bytes_bound) / 16 * 16;
+    const bool hand = o.allow_reclaim && rmax && should_reclaim(bytes_bound);
+    lead_ = hand_lead(cfg_.log_bytes, bytes_bound, rmax, lead_);  // every batch, as HostCache
+    if (!hand && o.phase == 0 && n <= kSmallSetRows && !o.index_after && !o.append_after &&
+        !o.append_done && !o.plan_done) {
+      // one launch for the whole chain (the proxy's small SET batches)
+      hipLaunchKernelGGL(k_set_small, dim3(1), dim3(kBlock), 0, s, keys, values, val_off, vlen,
+                         flags, expire, (int)n, cfg_.max_item, index_, cfg_.nbuckets - 1,
+                         cur_head(), next_head(),
+                         reinterpret_cast<unsigned long long*>(claim_ptr()), cfg_.log_bytes,
+                         now, log_, ring_, ring_ ? ring_cap_ - 1 : 0ull, cur_ring_tail(),
+                         next_ring_tail(), host_slots_ + kHeadSlot, ctr_);
+      HIP_OK(hipGetLastError());
+      hsel_ ^= 1;
+      return;
+    }
+    // consecutive batches take the two SET workspaces and hand buffers in turn
+    p.ws = ws_next_;
+    ws_next_ ^= 1;
+    const bool detached = o.phase == 1;
+    if (hand) {
+      const int64_t w = hand_window(n);
+      p.hand = p.ws;
+      ensure_rc_ws(w, s);
+      ensure_cb(p.hand, w + n, s);
+      ensure_set_ws(w + n, s);
+      p = reclaim_locked(p, w, rmax, now, s, detached);
+    } else {
+      ensure_set_ws(n, s);
+    }
+    ws_order(s);
+    store_plan_locked(p, s, detached);
+    if (o.plan_done) HIP_OK(hipEventRecord(o.plan_done, s));
+    if (detached) {  // the chain follows in phase 2
+      pend_ = p;
+      pend_.active = true;
+      return;
+    }
   }
-  ws_order(s);
-  select_ws(p.parity);
-  store_plan_locked(p.keys, p.vlen, p.rows, s, detached);
-  if (plan_done) HIP_OK(hipEventRecord(plan_done, s));
-  pend_ = p;
-  if (detached) return;  // the chain follows in phase 2
-  store_tail_locked(now, s, index_after, append_after, append_done);
-}
-
-// The planned batch's log append (after `append_after`) and index insert (after
-// `index_after`); publishes the new head (the ping-pong slot flips).
-void HbmCache::store_tail_locked(uint32_t now, hipStream_t s, hipEvent_t index_after,
-                                 hipEvent_t append_after, hipEvent_t append_done) {
-  const Pending p = pend_;
-  pend_.active = false;
-  select_ws(p.parity);
-  if (append_after) HIP_OK(hipStreamWaitEvent(s, append_after, 0));
-  launch_segcopy<1>(s, p.values, p.voff, set_off_, p.rows, log_, p.keys, p.vlen, p.flags,
-                    p.expire, cur_head(), cfg_.log_bytes);
-  HIP_OK(hipGetLastError());
-  if (append_done) HIP_OK(hipEventRecord(append_done, s));
-  store_index_locked(p.keys, p.vlen, p.expire, p.rows, now, s, index_after, p.from, p.nmove,
-                     p.nmove ? p.parity : -1);
+  store_tail_locked(p, now, s, o, &end_mark.done);
   hsel_ ^= 1;  // later operations on the stream read the published slot
 }
 
-// The SET kernel chain (caller holds mu_, workspace sized): dedupe (last writer wins),
-// sizes + fused scan, log append (k_segcopy<1>), two-choice CAS index insert that also
-// publishes the new head into the other head slot. The planning kernels (dedupe, sizes,
-// scan) touch neither the log, the index nor the head; the log write touches only bytes a
-// reserving lookup treats as gone; the index insert (+ fix-up), queued after
-// `index_after`, is the only part a concurrent lookup can observe.
-void HbmCache::store_locked(const Digest* keys, const uint8_t* values, const uint64_t* val_off,
-                            const uint32_t* vlen, const uint32_t* flags, const uint32_t* expire,
-                            int64_t n, uint32_t now, hipStream_t s, hipEvent_t index_after,
-                            hipEvent_t append_after, hipEvent_t append_done,
-                            const uint64_t* from, hipEvent_t plan_done, int64_t nmove) {
-  store_plan_locked(keys, vlen, n, s);
-  if (plan_done) HIP_OK(hipEventRecord(plan_done, s));
-  if (append_after) HIP_OK(hipStreamWaitEvent(s, append_after, 0));
-  launch_segcopy<1>(s, values, val_off, set_off_, n, log_, keys, vlen, flags, expire, cur_head(),
-                    cfg_.log_bytes);
+// The planned batch's log append (after `append_after`, k_segcopy<1>) and index insert (after
+// `index_after`), which also publishes the new head into the other head slot: the caller
+// flips hsel_. The log write touches only bytes a reserving lookup treats as gone.
+void HbmCache::store_tail_locked(const Pending& p, uint32_t now, hipStream_t s,
+                                 const StoreOpts& o, hipEvent_t* done) {
+  if (o.append_after) HIP_OK(hipStreamWaitEvent(s, o.append_after, 0));
+  launch_segcopy<1>(s, p.values, p.voff, ws_[p.ws].set_off, p.rows, log_, p.keys, p.vlen,
+                    p.flags, p.expire, cur_head(), cfg_.log_bytes);
   HIP_OK(hipGetLastError());
-  if (append_done) HIP_OK(hipEventRecord(append_done, s));
-  store_index_locked(keys, vlen, expire, n, now, s, index_after, from, nmove);
+  if (o.append_done) HIP_OK(hipEventRecord(o.append_done, s));
+  store_index_locked(p, now, s, o.index_after, done);
 }
 
+// The planning kernels (caller holds mu_, workspace sized): dedupe (last writer wins), sizes
+// + fused scan. They touch neither the log, the index nor the head.
 // `detached`: the planning of a phase-1 batch, which may run before the previous batch's
 // append and index insert: the ring tail it clamps the hand with is the batch-before's (the
 // last one written), and the claim grows from itself (the head every queued append
 // reaches) rather than from the head slot the previous index insert has not published yet.
-void HbmCache::store_plan_locked(const Digest* keys, const uint32_t* vlen, int64_t n,
-                                 hipStream_t s, bool detached) {
+void HbmCache::store_plan_locked(const Pending& p, hipStream_t s, bool detached) {
+  const SetWs& w = ws_[p.ws];
+  const int64_t n = p.rows;
   const int grid = grid_for(n, kBlock, kMaxGrid);
   RcAdvance adv;
-  if (rc_adv_w_ > 0) {
+  if (p.nmove > 0)  // a combined batch: its dedupe advances the hand past the window
     adv = RcAdvance{rc_ctl_, detached ? next_ring_tail() : cur_ring_tail(), ring_cap_ - 1,
-                    rc_adv_w_, ring_, claim_ptr(), cfg_.log_bytes, catch_up_ ? 1 : 0};
-    rc_adv_w_ = 0;
-  }
-  hipLaunchKernelGGL(k_set_dedupe, dim3(grid), dim3(kBlock), 0, s, keys, vlen, n,
-                     dd_tab_, dd_mask_, dd_slot_, adv);
+                    p.nmove, ring_, claim_ptr(), cfg_.log_bytes, catch_up_ ? 1 : 0};
+  hipLaunchKernelGGL(k_set_dedupe, dim3(grid), dim3(kBlock), 0, s, p.keys, p.vlen, n, w.dd_tab,
+                     dd_mask_, w.dd_slot, adv);
   const int sgrid = grid_for(n, kBlock, kMaxGrid);
   uint64_t* part_cnt = ring_ ? part_ + 2 * kMaxGrid : nullptr;
-  hipLaunchKernelGGL(k_set_size, dim3(sgrid), dim3(kBlock), 0, s, vlen, n, dd_tab_, dd_slot_,
-                     cfg_.max_item, set_size_, ctr_, part_ + kMaxGrid, part_cnt);
+  hipLaunchKernelGGL(k_set_size, dim3(sgrid), dim3(kBlock), 0, s, p.vlen, n, w.dd_tab,
+                     w.dd_slot, cfg_.max_item, w.set_size, ctr_, part_ + kMaxGrid, part_cnt);
   HIP_OK(hipGetLastError());
-  launch_offsets(set_size_, n, part_ + kMaxGrid, sgrid, set_off_, s, nullptr, 0, part_cnt,
-                 ring_ ? set_cnt_ : nullptr, detached ? claim_ptr() : cur_head(), claim_ptr());
+  launch_offsets(w.set_size, n, part_ + kMaxGrid, sgrid, w.set_off, s, nullptr, 0, part_cnt,
+                 ring_ ? w.set_cnt : nullptr, detached ? claim_ptr() : cur_head(),
+                 claim_ptr());
 }
 
-void HbmCache::store_index_locked(const Digest* keys, const uint32_t* vlen,
-                                  const uint32_t* expire, int64_t n, uint32_t now, hipStream_t s,
-                                  hipEvent_t index_after, const uint64_t* from, int64_t nmove,
-                                  int win_parity) {
+// Two-choice CAS index insert, then the fix-up (which carries `*done`).
+void HbmCache::store_index_locked(const Pending& p, uint32_t now, hipStream_t s,
+                                  hipEvent_t index_after, hipEvent_t* done) {
+  const SetWs& w = ws_[p.ws];
+  const int64_t n = p.rows;
   // the index insert is the only SET kernel a concurrent lookup can observe
   if (index_after) HIP_OK(hipStreamWaitEvent(s, index_after, 0));
   // A combined batch's reinsertions (rows [0, nmove), moves) land in a launch of their own
   // before the batch's rows: a batch row may claim the slot of an item this batch's append
   // overwrites as dead, and must not take a reinserted item's entry from under its move
   // (the host twin runs the rows in this order too).
-  if (!from) nmove = 0;
-  for (int pass = nmove > 0 ? 0 : 1; pass < 2; ++pass) {
-    const int64_t r0 = pass ? nmove : 0, r1 = pass ? n : nmove;
+  for (int pass = p.nmove > 0 ? 0 : 1; pass < 2; ++pass) {
+    const int64_t r0 = pass ? p.nmove : 0, r1 = pass ? n : p.nmove;
     if (r1 <= r0) continue;
     const int igrid = grid_for((r1 - r0) * 4, kBlock, kMaxGrid);
-    hipLaunchKernelGGL(k_set_index, dim3(igrid), dim3(kBlock), 0, s, keys, n, set_size_, set_off_,
-                       vlen, expire, index_, cfg_.nbuckets - 1, cur_head(), next_head(),
-                       cfg_.log_bytes, now, dd_slot_, dd_tab_, ctr_, set_claim_,
-                       pass ? (const uint64_t*)nullptr : from, r0, r1,
-                       pass || win_parity < 0 ? nullptr : rc_ctl_ + 5 + win_parity);
+    hipLaunchKernelGGL(k_set_index, dim3(igrid), dim3(kBlock), 0, s, p.keys, n, w.set_size,
+                       w.set_off, p.vlen, p.expire, index_, cfg_.nbuckets - 1, cur_head(),
+                       next_head(), cfg_.log_bytes, now, w.dd_slot, w.dd_tab, ctr_, w.set_claim,
+                       pass ? (const uint64_t*)nullptr : p.from, r0, r1,
+                       pass ? nullptr : rc_ctl_ + 5 + p.hand);
   }
-  launch_stop(&stop_ev_, k_set_fixup, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), s, keys,
-              n, set_off_, vlen, expire, cur_head(), set_claim_, index_, set_size_, ring_,
-              ring_ ? ring_cap_ - 1 : 0ull, cur_ring_tail(), next_ring_tail(), set_cnt_,
+  launch_stop(done, k_set_fixup, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), s, p.keys,
+              n, w.set_off, p.vlen, p.expire, cur_head(), w.set_claim, index_, w.set_size,
+              ring_, ring_ ? ring_cap_ - 1 : 0ull, cur_ring_tail(), next_ring_tail(), w.set_cnt,
               host_slots_ + kHeadSlot, cfg_.nbuckets - 1, cfg_.log_bytes, now, ctr_);
   HIP_OK(hipGetLastError());
 }
@@ -4254,7 +4218,9 @@ void HbmCache::store_graph(StoreGraph* g, const Digest* keys, const uint8_t* val
   DeviceGuard dg(cfg_.device);
   ensure_set_ws(n, s);  // before any capture: allocation is not capturable
   ws_order(s);
-  select_ws(0);         // (graphs bake the workspace in: always the first)
+  // The chain store() runs for a plain batch, on the first workspace always (graphs bake it
+  // in, and ws_next_ does not move); no hand, no events, and pend_ is not involved.
+  const Pending b{keys, values, val_off, vlen, flags, expire, n, n};
   const void* ptrs[6] = {keys, values, val_off, vlen, flags, expire};
   bool same = g->n == n && g->bound == bytes_bound && g->now == now && g->ws_gen == ws_gen_ &&
               g->exec[0] && g->exec[1];
@@ -4267,7 +4233,8 @@ void HbmCache::store_graph(StoreGraph* g, const Digest* keys, const uint8_t* val
       hipGraph_t graph = nullptr;
       HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
       try {
-        store_locked(keys, values, val_off, vlen, flags, expire, n, now, s);
+        store_plan_locked(b, s, false);
+        store_tail_locked(b, now, s, StoreOpts{}, nullptr);
       } catch (...) {
         (void)hipStreamEndCapture(s, &graph);
         if (graph) (void)hipGraphDestroy(graph);

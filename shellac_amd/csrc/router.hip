@@ -1762,8 +1762,10 @@ void RoutedStep::store_sets(const uint8_t* Rs, HbmCache* shard, HbmCache* replic
   // under a look-ahead reserve, after the previous step's reply gather with
   // `index_after` = this probe): the probes reserved these bytes (k_owner_prep), so the
   // append never touches a record a reply gather reads. The next owner_probe joins it.
-  shard->store(rkeys, nullptr, roff, v0, fl, ex, ms, bound, now, sset, index_after,
-               allow_reclaim);
+  StoreOpts o;
+  o.index_after = index_after;
+  o.allow_reclaim = allow_reclaim;
+  shard->store(rkeys, nullptr, roff, v0, fl, ex, ms, bound, now, sset, o);
   RT_OK(hipEventRecord(ev_join_, sset));
   sets_pending_ = true;
   // replica (tier 1) on `s`, after this step's local gather (same stream) and the fill
@@ -1842,8 +1844,10 @@ void RoutedStep::store_fixed(const uint8_t* Rs, int64_t slotS, const std::vector
     RT_OK(hipEventRecord(ev_rep_, sset));
     rep_pending_ = true;
   }
-  shard->store(rkeys, nullptr, roff, v0, fl, ex, nrows, bound, now, sset, index_after,
-               allow_reclaim);
+  StoreOpts o;
+  o.index_after = index_after;
+  o.allow_reclaim = allow_reclaim;
+  shard->store(rkeys, nullptr, roff, v0, fl, ex, nrows, bound, now, sset, o);
   RT_OK(hipEventRecord(ev_join_, sset));
   sets_pending_ = true;
 }

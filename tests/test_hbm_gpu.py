@@ -137,6 +137,57 @@ def test_small_set_kernel_matches_host_engine(cuda_dev, evict):
         assert cg[k] == ch[k], k
 
 
+@pytest.mark.parametrize("evict", ["clock", "fifo"])
+def test_split_store_equals_whole_store(cuda_dev, evict):
+    """A batch stored with ``phase=1`` then ``phase=2`` runs the chain ``phase=0`` runs: two
+    shards fed the same batches, one whole and one split, end with the same head, the same
+    record for every key (equal to the host truth) and the same SET counters. 200 rows:
+    the whole store is the fused small kernel; 257: the smallest batch that leaves it;
+    1025: the workspace grows past its initial 1024 rows. Each batch repeats a key three
+    times (the last value wins) and holds one skip row. Under 4 MiB go into a 64 MiB log
+    (reinsertion budget 2 MiB), so no CLOCK hand runs and the comparison is exact."""
+    from shellac_amd.models.sharded_cache import SKIP_VLEN
+
+    whole = CacheShard(64 << 20, 1 << 14, 4096, cuda_dev, evict=evict)
+    split = CacheShard(64 << 20, 1 << 14, 4096, cuda_dev, evict=evict)
+    rng = np.random.default_rng(11)
+    truth, now = {}, 30
+    for b, n in enumerate((200, 257, 1025)):
+        # keys shared with the batch before (overwritten), one key three times, one skip row
+        keys = [f"/split/{(b * 150 + i) % 1200}".encode() for i in range(n)]
+        rep, skip = n // 3, n // 2
+        keys[5] = keys[rep] = keys[n - 1] = f"/split/rep/{b}".encode()
+        keys[skip] = f"/split/skip/{b}".encode()
+        vals = [rng.integers(0, 256, size=int(rng.integers(16, 2049)), dtype=np.uint8).tobytes()
+                for _ in keys]
+        fl = torch.arange(n, dtype=torch.int32) + 1000 * b
+        d, v, vo, vl = _batch(keys, vals, cuda_dev)
+        vl[skip] = SKIP_VLEN
+        args = [t.to(cuda_dev) for t in (d, v, vo, vl, fl)]
+        whole.store(*args, now=now, phase=0)
+        split.store(*args, now=now, phase=1)
+        split.store(*args, now=now, phase=2)
+        for i, k in enumerate(keys):
+            if i != skip:
+                truth[k] = (vals[i], int(fl[i]))
+    probe = sorted(truth) + [f"/split/skip/{b}".encode() for b in range(3)]
+    d = digest_strings(probe).to(cuda_dev)
+    recs = []
+    for s in (whole, split):
+        out, off, size = s.get(d, now=now)
+        assert unpack_records(out, off, size) == [truth.get(k) for k in probe]
+        o, of, sz = out.cpu().numpy(), off.cpu().numpy(), size.cpu().numpy()
+        recs.append([o[int(of[i]) : int(of[i]) + int(sz[i])].tobytes() for i in range(len(probe))])
+    assert recs[0] == recs[1]  # whole records: header (digest, length, flags, expiry) and value
+    assert whole.head() == split.head() > 0
+    cw, cs = whole.counters(), split.counters()
+    assert cw["reinserted"] == 0 and cs["reinserted"] == 0  # no hand ran on either shard
+    set_keys = [k for k in cw if k.startswith("set_")]
+    assert {"set_ops", "set_bytes", "set_dropped", "set_evicted"} <= set(set_keys)
+    for k in set_keys:
+        assert cw[k] == cs[k], k
+
+
 def test_bucket_overflow_eviction_invariants(cuda_dev):
     g = CacheShard(1 << 20, 2, 64, cuda_dev)  # 8 slots total
     keys = [f"/o/{i}".encode() for i in range(20)]
