@@ -98,6 +98,13 @@ void DramBackend::purge_prefix(const std::string& prefix, Executor*, PurgeCallba
   if (done) done(n);
 }
 
+void DramBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
+                        const uint32_t* flags, Executor*, TouchCallback done) {
+  const uint32_t n = now();
+  const bool ok = cache_.touch(key, d, ttl_s ? n + ttl_s : 0, flags, n);
+  if (done) done(ok ? 1 : 0);
+}
+
 void DramBackend::flush() { cache_.clear(); }
 
 void DramBackend::stats(StatList* out) {
@@ -110,6 +117,7 @@ void DramBackend::stats(StatList* out) {
   out->emplace_back("cache_objects", t.objects);
   out->emplace_back("cache_bytes", t.bytes);
   out->emplace_back("cache_key_mismatch", t.key_mismatch);
+  out->emplace_back("cache_touched", t.touched);
 }
 
 // =====================================================================================
@@ -175,6 +183,18 @@ void TieredBackend::del(const std::string& key, const Digest& d, Executor* ex, D
     move_purge_epoch();
     l1_->del(key, d, ex, [done, f2](bool f1) {
       if (done) done(f1 || f2);
+    });
+  });
+}
+
+void TieredBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
+                          const uint32_t* flags, Executor* ex, TouchCallback done) {
+  const bool has_flags = flags != nullptr;
+  const uint32_t fl = has_flags ? *flags : 0u;  // (the caller's word need not outlive the call)
+  l2_->touch(key, d, ttl_s, flags, ex, [this, key, d, ttl_s, has_flags, fl, ex, done](int s2) {
+    move_purge_epoch();
+    l1_->touch(key, d, ttl_s, has_flags ? &fl : nullptr, ex, [done, s2](int) {
+      if (done) done(s2);
     });
   });
 }

@@ -62,6 +62,8 @@ using GetCallback = std::function<void(bool hit, CacheValue v)>;
 using DelCallback = std::function<void(bool found)>;
 // Prefix purge: objects removed, or -1 if the tier cannot scan its keys.
 using PurgeCallback = std::function<void(int64_t removed)>;
+// In-place touch: 1 touched, 0 not found, -1 the tier cannot do it.
+using TouchCallback = std::function<void(int status)>;
 using StatList = std::vector<std::pair<std::string, uint64_t>>;
 
 // Asynchronous body compressor for the proxy's -z path: `done` runs on the compressor's
@@ -98,6 +100,23 @@ class CacheBackend {
   // when `done` runs; GETs racing the purge may still hit until then.
   virtual void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
     (void)prefix;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
+  // Touch: give the live object of exactly `key` the TTL `ttl_s` from now (0 = never expires)
+  // and, when `flags` is not null (read before the call returns), new flags, without moving
+  // its bytes. A write: ordered with
+  // the SETs and DELETEs of the key issued before and after it. `done` runs once, on `ex`'s
+  // thread (inline for synchronous backends): 1 touched, 0 no such live object, -1 where the
+  // tier cannot do it (the default; memcached's wire TOUCH cannot change flags) — the caller
+  // then re-stores the object.
+  virtual void touch(const std::string& key, const Digest& d, uint32_t ttl_s,
+                     const uint32_t* flags, Executor* ex, TouchCallback done) {
+    (void)key;
+    (void)d;
+    (void)ttl_s;
+    (void)flags;
     if (!done) return;
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
@@ -150,6 +169,8 @@ class DramBackend : public CacheBackend {
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
+             Executor* ex, TouchCallback done) override;
   void flush() override;
   std::string name() const override { return "dram"; }
   void stats(StatList* out) override;
@@ -240,6 +261,11 @@ class HbmBackend : public CacheBackend {
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  // Routed like del(): to the owner, and for a hot object written through to every shard in
+  // service (the answer is the owner's). Queued on the shard's stream behind the writes
+  // queued before it; a flight's touches are one key-exact HbmCache::touch launch.
+  void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
+             Executor* ex, TouchCallback done) override;
   void flush() override;
   std::string name() const override { return "hbm"; }
   // peer path chosen for src -> dst: 0 same device, 1 direct (peer access), 2 staged
@@ -260,14 +286,16 @@ class HbmBackend : public CacheBackend {
     PurgeCallback cb;
   };
   struct Req {
-    int kind;  // 0 get, 1 set, 2 del, 3 barrier, 4 hot-replica fill, 5 prefix purge
+    int kind;  // 0 get, 1 set, 2 del, 3 barrier, 4 hot-replica fill, 5 prefix purge, 6 touch
     Digest d;
     std::string key;
     Bytes value;
     uint32_t flags = 0, ttl = 0;
+    bool has_flags = false;  // kind 6: `flags` replaces the object's (else they stay)
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
+    TouchCallback tcb;
     // kinds 3 / 4: runs on the batcher thread once the request's flight has finished on
     // the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
@@ -387,6 +415,11 @@ class TieredBackend : public CacheBackend {
   // the purge does not promote its object into L1 after L1 was purged (purge_epoch_; del()
   // does the same for one key).
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
+  // writes both levels). A promotion that straddles the touch is dropped, as for del(): it
+  // would carry the pre-touch TTL and flags into L1.
+  void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
+             Executor* ex, TouchCallback done) override;
   void flush() override;
   std::string name() const override { return l1_->name() + "+" + l2_->name(); }
   void stats(StatList* out) override;
@@ -444,6 +477,10 @@ class FaultBackend : public CacheBackend {
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override {
     inner_->purge_prefix(prefix, ex, std::move(done));
+  }
+  void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
+             Executor* ex, TouchCallback done) override {
+    inner_->touch(key, d, ttl_s, flags, ex, std::move(done));
   }
   void flush() override { inner_->flush(); }
   std::string name() const override { return "fault(" + inner_->name() + ")"; }

@@ -210,15 +210,20 @@ class ArenaPool : public std::enable_shared_from_this<ArenaPool> {
 // One batch in flight on a GPU.
 struct Flight {
   std::vector<HbmBackend::Req> reqs;
-  std::vector<uint32_t> gets, sets, dels;  // request indices by kind
+  std::vector<uint32_t> gets, sets, dels, touches;  // request indices by kind
   std::vector<uint32_t> ctls;              // barriers and hot-replica fills
   std::vector<uint32_t> urow;              // GET request -> GPU row (host coalescing)
   size_t rows = 0;                         // distinct GET digests
   Mapped keys, offs, set_keys, set_vals, set_voff, set_meta, del_keys, del_found;
   // prefix purges: pattern images (keyed.h) and {removed, bytes} word pairs, one per purge
   Mapped purge_img, purge_out;
+  // touches: the distinct rows' {digests, key offsets, expiries, flags, hit bytes} and their
+  // packed key bytes; trow maps a touch request to its row (the last request of a key wins)
+  Mapped touch_rows, touch_kbytes;
+  std::vector<uint32_t> trow;
+  const uint8_t* touch_hit = nullptr;
   std::shared_ptr<ArenaPool::Arena> arena;
-  std::vector<uint64_t> wkeys;  // SET / DELETE digests (lo words) counted in Dev::pend_w
+  std::vector<uint64_t> wkeys;  // SET / DELETE / touch digests (lo words) counted in Dev::pend_w
   bool flush = false;           // a flush runs on the stream right before this flight
   hipEvent_t ev = nullptr;
   int slot = -1;
@@ -316,6 +321,7 @@ struct HbmBackend::Dev {
   // flight: a GET of such a key takes the stream path, ordered after them
   std::unordered_map<uint64_t, uint32_t> pend_w;
   std::unordered_set<uint64_t> take_wset;  // take_batch scratch: write digests so far
+  std::unordered_set<uint64_t> take_tset;  // ... and those of them that are touches
   uint32_t pend_flush = 0;
   void track_writes(const Flight& f, int dir);
   double avg_row_bytes = 4096;
@@ -332,7 +338,7 @@ struct HbmBackend::Dev {
       dropped{0}, staged_copies{0}, served_batches{0}, ordered_gets{0},
       migrated{0}, migrate_ns{0}, direct_jobs{0}, direct_reqs{0}, direct_fallbacks{0},
       direct_overflows{0}, direct_timeouts{0}, direct_ns{0}, purged_objects{0},
-      purged_bytes{0};
+      purged_bytes{0}, touch_reqs{0};
 
   void loop();
   bool take_batch(std::vector<Req>* out, bool* do_flush, bool* rebuilding);
@@ -340,6 +346,8 @@ struct HbmBackend::Dev {
   bool try_reap(Flight& f, bool block);
   void deliver_gets(Flight& f);
   void deliver_dels(Flight& f);
+  void launch_touches(Flight& f);
+  void deliver_touches(Flight& f);
   void overflow_misses(Flight& f);
   void fail_flight(Flight& f);
   // `unlaunched`: the requests never reached the GPU (their SETs / DELETEs end here)
@@ -360,7 +368,7 @@ struct HbmBackend::Dev {
     for (auto& f : flights) {
       for (Mapped* m : {&f->keys, &f->offs, &f->set_keys, &f->set_vals, &f->set_voff,
                         &f->set_meta, &f->del_keys, &f->del_found, &f->purge_img,
-                        &f->purge_out})
+                        &f->purge_out, &f->touch_rows, &f->touch_kbytes})
         m->release();
       f->arena.reset();
       if (f->ev) (void)hipEventDestroy(f->ev);
@@ -636,7 +644,8 @@ void HbmBackend::enqueue(int k, Req r) {
       if (dv.filt_next) dv.filt_next->add(r.d);
     }
     // a write of an object being filled into this shard: the fill must not overwrite it
-    if ((r.kind == 1 || r.kind == 2) && !dv.filling.empty() && dv.filling.count(r.d.lo))
+    if ((r.kind == 1 || r.kind == 2 || r.kind == 6) && !dv.filling.empty() &&
+        dv.filling.count(r.d.lo))
       dv.touched.insert(r.d.lo);
     // A purge names no digests, and the records of a refresh under way were read on their
     // owners before it: a fill queued behind it must not store them here after this shard
@@ -771,6 +780,60 @@ void HbmBackend::del(const std::string& key, const Digest& d, Executor* ex, DelC
       if (f) fan->found.store(true, std::memory_order_relaxed);
       if (fan->left.fetch_sub(1, std::memory_order_acq_rel) == 1 && fan->cb)
         fan->cb(fan->found.load(std::memory_order_relaxed));
+    };
+    write_begin(d.lo);
+    enqueue(j, std::move(c));
+  }
+}
+
+// A touch is a write, routed like del(): the owner, and every other shard in service for a
+// hot object (the replicas must not outlive, or die before, the owner's copy). The answer is
+// the owner's, once every copy has answered.
+void HbmBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
+                       const uint32_t* flags, Executor* ex, TouchCallback done) {
+  Req r;
+  r.kind = 6;
+  r.d = d;
+  r.key = key;
+  r.ttl = ttl_s;
+  r.has_flags = flags != nullptr;
+  r.flags = flags ? *flags : 0u;
+  r.ex = ex;
+  std::unique_ptr<HostRouter::Read> rd;  // write-through: held until every copy is queued
+  if (hot_on_) rd = std::make_unique<HostRouter::Read>(*router_);
+  const uint64_t up = up_mask_.load(std::memory_order_acquire);
+  const int k = owner_of(d, up);
+  if (k < 0 || key.size() > kMaxKeyedKey) {  // no shard in service (or never storable): not found
+    if (!done) return;
+    if (ex) ex->post([done] { done(0); });
+    else done(0);
+    return;
+  }
+  std::vector<int> to{k};
+  if (rd && rd->hot_rank(d) != HostRouter::kNotHot)
+    for (size_t j = 0; j < devs_.size(); ++j)
+      if ((int)j != k && ((up >> j) & 1)) to.push_back((int)j);
+  if (to.size() == 1) {
+    r.tcb = std::move(done);
+    write_begin(d.lo);
+    enqueue(k, std::move(r));
+    return;
+  }
+  struct Fan {
+    std::atomic<int> left;
+    std::atomic<int> owner{0};
+    TouchCallback cb;
+  };
+  auto fan = std::make_shared<Fan>();
+  fan->left.store((int)to.size());
+  fan->cb = std::move(done);
+  for (int j : to) {
+    Req c = r;
+    const bool is_owner = j == k;
+    c.tcb = [fan, is_owner](int st) {
+      if (is_owner) fan->owner.store(st, std::memory_order_relaxed);
+      if (fan->left.fetch_sub(1, std::memory_order_acq_rel) == 1 && fan->cb)
+        fan->cb(fan->owner.load(std::memory_order_relaxed));
     };
     write_begin(d.lo);
     enqueue(j, std::move(c));
@@ -1079,11 +1142,22 @@ bool HbmBackend::Dev::take_batch(std::vector<Req>* out, bool* do_flush, bool* re
   size_t take = std::min(q.size(), (size_t)std::max(cfg.max_batch, 1));
   {
     std::unordered_set<uint64_t>& w = take_wset;
+    std::unordered_set<uint64_t>& tw = take_tset;
     w.clear();
+    tw.clear();
     for (size_t i = 0; i < take; ++i) {
       const Req& r = q[i];
       if (r.kind == 1 || r.kind == 2) {
+        // a flight's touches run after its SETs and DELETEs: a write queued behind a touch
+        // of the same key goes into the next flight
+        if (!tw.empty() && tw.count(r.d.lo)) {
+          take = i;
+          break;
+        }
         w.insert(r.d.lo);
+      } else if (r.kind == 6) {
+        w.insert(r.d.lo);
+        tw.insert(r.d.lo);
       } else if (r.kind == 4 || r.kind == 5) {
         // a fill or a purge ends its flight (it runs after the flight's writes, and the
         // writes queued behind a purge must not run before it)
@@ -1249,9 +1323,11 @@ void HbmBackend::Dev::launch(Flight& f) {
   f.sets.clear();
   f.dels.clear();
   f.ctls.clear();
+  f.touches.clear();
   for (uint32_t i = 0; i < f.reqs.size(); ++i) {
     const int kd = f.reqs[i].kind;
-    (kd == 0 ? f.gets : kd == 1 ? f.sets : kd == 2 ? f.dels : f.ctls).push_back(i);
+    (kd == 0 ? f.gets : kd == 1 ? f.sets : kd == 2 ? f.dels : kd == 6 ? f.touches : f.ctls)
+        .push_back(i);
   }
   f.tnow = be->now();
   f.t0 = wall_s();
@@ -1355,6 +1431,7 @@ void HbmBackend::Dev::launch(Flight& f) {
     cache->remove(f.del_keys.dev<Digest>(), (int64_t)nd, f.del_found.dev<uint8_t>(), f.tnow,
                   stream);
   }
+  launch_touches(f);
   // ---- hot-replica fills (last in the flight: every write queued before them ran first)
   for (uint32_t i : f.ctls) {
     if (f.reqs[i].kind != 4) continue;
@@ -1411,6 +1488,80 @@ void HbmBackend::Dev::launch(Flight& f) {
   }
 }
 
+// TOUCH: after the flight's SETs and DELETEs (take_batch keeps a write queued behind a touch
+// of its key out of the flight). One row per distinct key, the last request's (HbmCache::touch
+// leaves duplicates to the caller); rows that keep their flags first, then those that replace
+// them — one key-exact launch each, everything in mapped memory.
+void HbmBackend::Dev::launch_touches(Flight& f) {
+  const size_t nt = f.touches.size();
+  if (!nt) return;
+  // distinct (key, digest) pairs in arrival order; `last`: the last request of each
+  std::unordered_map<std::string, uint32_t> seen;
+  std::vector<uint32_t> last, slot(nt);
+  for (size_t j = 0; j < nt; ++j) {
+    const Req& r = f.reqs[f.touches[j]];
+    std::string id = r.key;
+    id.append(reinterpret_cast<const char*>(&r.d), sizeof(Digest));
+    const auto it = seen.emplace(std::move(id), (uint32_t)last.size());
+    if (it.second) last.push_back((uint32_t)j);
+    else last[it.first->second] = (uint32_t)j;
+    slot[j] = it.first->second;
+  }
+  const size_t n = last.size();
+  std::vector<uint32_t> order(n), row_of(n);  // rows: the flag-keeping pairs first
+  for (size_t k = 0; k < n; ++k) order[k] = (uint32_t)k;
+  std::stable_partition(order.begin(), order.end(), [&](uint32_t k) {
+    return !f.reqs[f.touches[last[k]]].has_flags;
+  });
+  size_t nkeep = 0, kbytes = 16;
+  for (size_t row = 0; row < n; ++row) {
+    const Req& r = f.reqs[f.touches[last[order[row]]]];
+    row_of[order[row]] = (uint32_t)row;
+    nkeep += r.has_flags ? 0 : 1;
+    kbytes += r.key.size();
+  }
+  f.trow.resize(nt);
+  for (size_t j = 0; j < nt; ++j) f.trow[j] = row_of[slot[j]];
+  // {digests | offsets (one array per launch, n + 2 words in all) | expiries | flags | hit}
+  const size_t o_offs = align_up(n * sizeof(Digest), 16), o_exp = o_offs + align_up((n + 2) * 8, 16),
+               o_fl = o_exp + align_up(n * 4, 16), o_hit = o_fl + align_up(n * 4, 16);
+  f.touch_rows.ensure(o_hit + n);
+  f.touch_kbytes.ensure(kbytes);
+  uint8_t* const hb = f.touch_rows.host<uint8_t>();
+  uint8_t* const db = f.touch_rows.dev<uint8_t>();
+  Digest* kk = reinterpret_cast<Digest*>(hb);
+  int64_t* offs = reinterpret_cast<int64_t*>(hb + o_offs);
+  uint32_t* ex = reinterpret_cast<uint32_t*>(hb + o_exp);
+  uint32_t* fl = reinterpret_cast<uint32_t*>(hb + o_fl);
+  std::memset(hb + o_hit, 0, n);
+  f.touch_hit = hb + o_hit;
+  uint8_t* kb = f.touch_kbytes.host<uint8_t>();
+  int64_t at = 0;
+  for (size_t row = 0; row < n; ++row) {
+    const Req& r = f.reqs[f.touches[last[order[row]]]];
+    kk[row] = r.d;
+    ex[row] = r.ttl ? f.tnow + r.ttl : 0;
+    fl[row] = r.flags;
+    // the second launch's offsets start one word further on (its own n + 1 words)
+    offs[row + (row >= nkeep ? 1 : 0)] = at;
+    std::memcpy(kb + at, r.key.data(), r.key.size());
+    at += (int64_t)r.key.size();
+    if (row + 1 == nkeep || row + 1 == n) offs[row + 1 + (row >= nkeep ? 1 : 0)] = at;
+  }
+  const uint8_t* const dkb = f.touch_kbytes.dev<uint8_t>();
+  if (nkeep)
+    cache->touch(reinterpret_cast<const Digest*>(db), reinterpret_cast<const uint32_t*>(db + o_exp),
+                 nullptr, dkb, reinterpret_cast<const int64_t*>(db + o_offs), (int64_t)nkeep,
+                 db + o_hit, f.tnow, stream);
+  if (n > nkeep)
+    cache->touch(reinterpret_cast<const Digest*>(db) + nkeep,
+                 reinterpret_cast<const uint32_t*>(db + o_exp) + nkeep,
+                 reinterpret_cast<const uint32_t*>(db + o_fl) + nkeep, dkb,
+                 reinterpret_cast<const int64_t*>(db + o_offs) + nkeep + 1,
+                 (int64_t)(n - nkeep), db + o_hit + nkeep, f.tnow, stream);
+  touch_reqs += nt;
+}
+
 // Completion of flight f (non-blocking unless `block`): GET results as soon as the edge
 // GET's slot fires, DELETE results and the flight's buffers once its event completes.
 bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
@@ -1429,7 +1580,7 @@ bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
       // SET/DELETE in this flight and no later flight queued on the stream. Otherwise the
       // GETs answer "miss" (always a valid cache answer: the proxy goes to the origin);
       // reading a newer state would reorder them after later SETs.
-      if (f.sets.empty() && f.dels.empty() && inflight == 1) {
+      if (f.sets.empty() && f.dels.empty() && f.touches.empty() && inflight == 1) {
         regathers++;
         HB_OK(hipEventSynchronize(f.ev));
         f.arena = pool->take(total + (64u << 10));
@@ -1458,6 +1609,7 @@ bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
   }
   if (f.active) {
     deliver_dels(f);
+    deliver_touches(f);
     size_t pj = 0;
     for (uint32_t i : f.ctls) {
       Req& r = f.reqs[i];
@@ -1485,6 +1637,7 @@ void HbmBackend::Dev::track_writes(const Flight& f, int dir) {
     m.wkeys.clear();
     for (uint32_t i : f.sets) m.wkeys.push_back(f.reqs[i].d.lo);
     for (uint32_t i : f.dels) m.wkeys.push_back(f.reqs[i].d.lo);
+    for (uint32_t i : f.touches) m.wkeys.push_back(f.reqs[i].d.lo);
     for (uint64_t k : m.wkeys) ++pend_w[k];
     if (f.flush) ++pend_flush;
     return;
@@ -1568,11 +1721,33 @@ void HbmBackend::Dev::deliver_dels(Flight& f) {
   pg.flush();
 }
 
+void HbmBackend::Dev::deliver_touches(Flight& f) {
+  if (f.touches.empty()) return;
+  PostGroups pg;
+  for (size_t j = 0; j < f.touches.size(); ++j) {
+    Req& r = f.reqs[f.touches[j]];
+    const int st = f.touch_hit[f.trow[j]] ? 1 : 0;  // (every request of a key: its row's answer)
+    auto cb = std::move(r.tcb);
+    if (!cb) continue;
+    if (r.ex)
+      pg.at(r.ex).push_back([cb = std::move(cb), st]() { cb(st); });
+    else
+      cb(st);
+  }
+  pg.flush();
+}
+
 void HbmBackend::Dev::fail_requests(std::vector<Req>& reqs, bool unlaunched) {
   PostGroups pg;
   for (auto& r : reqs) {
-    if (unlaunched && (r.kind == 1 || r.kind == 2)) be->write_end(r.d.lo);
-    if (r.kind >= 3) {
+    if (unlaunched && (r.kind == 1 || r.kind == 2 || r.kind == 6)) be->write_end(r.d.lo);
+    if (r.kind == 6) {  // a touch that cannot run: not found
+      if (r.tcb) {
+        auto cb = std::move(r.tcb);
+        if (r.ex) pg.at(r.ex).push_back([cb = std::move(cb)]() { cb(0); });
+        else cb(0);
+      }
+    } else if (r.kind >= 3) {
       if (r.ccb) r.ccb(false);
       r.ccb = nullptr;
     } else if (r.kind == 0 && r.gcb) {
@@ -1599,12 +1774,14 @@ void HbmBackend::Dev::fail_flight(Flight& f) {
   } else {
     std::vector<Req> rest;
     for (uint32_t i : f.dels) rest.push_back(std::move(f.reqs[i]));
+    for (uint32_t i : f.touches) rest.push_back(std::move(f.reqs[i]));
     for (uint32_t i : f.ctls) rest.push_back(std::move(f.reqs[i]));
     fail_requests(rest, false);
   }
   f.got = true;
   f.gets.clear();
   f.dels.clear();
+  f.touches.clear();
   f.ctls.clear();
   f.active = false;
 }
@@ -2440,6 +2617,7 @@ void HbmBackend::stats(StatList* out) {
     t.get_ops += c.get_ops; t.get_hits += c.get_hits; t.set_ops += c.set_ops;
     t.set_bytes += c.set_bytes; t.set_evicted += c.set_evicted; t.del_ops += c.del_ops;
     t.reinserted += c.reinserted; t.reinsert_bytes += c.reinsert_bytes;
+    t.touched += c.touched;
     hbm += d->cache->hbm_bytes();
   }
   out->emplace_back("cache_get_ops", t.get_ops);
@@ -2491,6 +2669,9 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_purges", purge_started_.load());
   out->emplace_back("hbm_purged_objects", sum(&Dev::purged_objects));
   out->emplace_back("hbm_purged_bytes", sum(&Dev::purged_bytes));
+  // touch requests taken, and the entries the shards' kernels updated (replicas included)
+  out->emplace_back("hbm_touches", sum(&Dev::touch_reqs));
+  out->emplace_back("hbm_touched", t.touched);
   out->emplace_back("hbm_no_shard_misses", no_shard_misses_.load());
   // per-shard GET routing (the load hot-object spreading evens out) and the hot set
   for (size_t i = 0; i < devs_.size(); ++i)

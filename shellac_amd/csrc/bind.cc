@@ -41,6 +41,7 @@ py::dict counters_dict(const CacheCounters& c) {
   d["reinsert_bytes"] = c.reinsert_bytes;
   d["reinsert_lost"] = c.reinsert_lost;
   d["purged"] = c.purged;
+  d["touched"] = c.touched;
   return d;
 }
 
@@ -231,6 +232,16 @@ PYBIND11_MODULE(_shellac_core, m) {
         py::gil_scoped_release nogil;
         c.remove_keyed_prefix(P<const uint8_t>(image), plen, now, P<uint64_t>(out), S(s));
       }, py::arg("image"), py::arg("plen"), py::arg("now"), py::arg("out"), py::arg("stream"))
+      // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
+      .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
+                       uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
+                       uint32_t now, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.touch(P<const Digest>(keys), P<const uint32_t>(expire), P<const uint32_t>(flags),
+                P<const uint8_t>(key_bytes), P<const int64_t>(key_offs), n, P<uint8_t>(hit), now,
+                S(s));
+      }, py::arg("keys"), py::arg("expire"), py::arg("flags"), py::arg("key_bytes"),
+         py::arg("key_offs"), py::arg("n"), py::arg("hit"), py::arg("now"), py::arg("stream"))
       .def("sweep", [](HbmCache& c, uint32_t now, uintptr_t s) {
         uint64_t live = 0, bytes = 0;
         {
@@ -438,6 +449,14 @@ PYBIND11_MODULE(_shellac_core, m) {
                               out);
         return py::make_tuple(out[0], out[1]);
       }, py::arg("prefix"), py::arg("now"))
+      .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
+                       uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
+                       uint32_t now) {
+        py::gil_scoped_release nogil;
+        c.touch(P<const Digest>(keys), P<const uint32_t>(expire), P<const uint32_t>(flags),
+                P<const uint8_t>(key_bytes), P<const int64_t>(key_offs), n, P<uint8_t>(hit), now);
+      }, py::arg("keys"), py::arg("expire"), py::arg("flags"), py::arg("key_bytes"),
+         py::arg("key_offs"), py::arg("n"), py::arg("hit"), py::arg("now"))
       .def("sweep", [](HostCache& c, uint32_t now) {
         uint64_t live = 0, bytes = 0;
         c.sweep(now, &live, &bytes);

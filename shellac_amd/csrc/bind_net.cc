@@ -71,6 +71,31 @@ bool blocking_del(CacheBackend* be, const std::string& key) {
   return found;
 }
 
+// A touch's answer, waited for after whatever the caller queues behind it.
+struct TouchWait {
+  std::mutex mu;
+  std::condition_variable cv;
+  bool done = false;
+  int status = -2;
+  int wait() {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return done; });
+    return status;
+  }
+};
+
+std::shared_ptr<TouchWait> start_touch(CacheBackend* be, const std::string& key, const Digest& d,
+                                       uint32_t ttl, const uint32_t* flags) {
+  auto w = std::make_shared<TouchWait>();
+  be->touch(key, d, ttl, flags, &g_inline, [w](int st) {
+    std::lock_guard<std::mutex> lk(w->mu);
+    w->status = st;
+    w->done = true;
+    w->cv.notify_all();
+  });
+  return w;
+}
+
 int64_t blocking_purge(CacheBackend* be, const std::string& prefix) {
   std::mutex mu;
   std::condition_variable cv;
@@ -192,6 +217,58 @@ void bind_net(py::module_& m) {
       .def("purge_prefix", [](BackendHandle& h, py::bytes prefix) {
         return blocking_purge(h.be.get(), prefix);
       }, py::arg("prefix"))
+      // in-place touch (blocking): 1 touched, 0 not found, -1 the tier cannot. `flags` None
+      // keeps the object's flags; `digest_of`: look the key up under another key's digest (a
+      // forged collision)
+      .def("touch", [](BackendHandle& h, py::bytes key, uint32_t ttl, py::object flags,
+                       py::object digest_of) {
+        const std::string k = key, o = digest_of.is_none() ? k : digest_of.cast<std::string>();
+        const bool has = !flags.is_none();
+        const uint32_t fl = has ? flags.cast<uint32_t>() : 0u;
+        py::gil_scoped_release nogil;
+        const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(o.data()), o.size());
+        return start_touch(h.be.get(), k, d, ttl, has ? &fl : nullptr)->wait();
+      }, py::arg("key"), py::arg("ttl"), py::arg("flags") = py::none(),
+         py::arg("digest_of") = py::none())
+      // SET, touch, SET of one key issued back to back (nothing waited for in between), then
+      // the touch's answer: the tier must keep them in that order
+      .def("set_touch_set", [](BackendHandle& h, py::bytes key, py::bytes v1, uint32_t ttl1,
+                               uint32_t touch_ttl, py::bytes v2, uint32_t ttl2) {
+        const std::string k = key;
+        auto a = std::make_shared<const std::string>(std::string(v1));
+        auto b = std::make_shared<const std::string>(std::string(v2));
+        py::gil_scoped_release nogil;
+        const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(k.data()), k.size());
+        h.be->set(k, d, a, 0, ttl1);
+        auto w = start_touch(h.be.get(), k, d, touch_ttl, nullptr);
+        h.be->set(k, d, b, 0, ttl2);
+        return w->wait();
+      }, py::arg("key"), py::arg("value1"), py::arg("ttl1"), py::arg("touch_ttl"),
+         py::arg("value2"), py::arg("ttl2"))
+      // (value, flags, seconds of life left: -1 unknown, 0 never expires) or None
+      .def("get_ttl", [](BackendHandle& h, py::bytes key) -> py::object {
+        const std::string k = key;
+        std::mutex mu;
+        std::condition_variable cv;
+        bool done = false, hit = false;
+        CacheValue val;
+        {
+          py::gil_scoped_release nogil;
+          const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(k.data()), k.size());
+          h.be->get(k, d, &g_inline, [&](bool ht, CacheValue v) {
+            std::lock_guard<std::mutex> lk(mu);
+            hit = ht;
+            val = std::move(v);
+            done = true;
+            cv.notify_all();
+          });
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return done; });
+        }
+        if (!hit || !val.data) return py::none();
+        return py::make_tuple(py::bytes(val.data->data(), val.data->size()), val.flags,
+                              val.ttl_left);
+      })
       .def("get_many", [](BackendHandle& h, std::vector<std::string> keys) {
         // every GET issued at once (one batch stream, as concurrent clients would), then
         // waited for: [(value, flags) or None]
@@ -379,8 +456,10 @@ void bind_net(py::module_& m) {
                        uint64_t stream_high_water, const std::string& health_path,
                        int health_interval_ms, int health_timeout_ms, int health_fails,
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
-                       uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge) {
+                       uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge,
+                       uint32_t grace) {
              ProxyConfig c;
+             c.grace = grace;
              SH_CHECK(purge == "off" || purge == "loopback" || purge == "any",
                       "purge must be off, loopback or any");
              c.purge = purge;
@@ -434,7 +513,7 @@ void bind_net(py::module_& m) {
            py::arg("cpus") = std::vector<int>{}, py::arg("spin_us") = 0,
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
            py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
-           py::arg("purge") = "off")
+           py::arg("purge") = "off", py::arg("grace") = 0)
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)

@@ -260,6 +260,26 @@ class HbmCache {
   // whatever happens to parse as a matching keyed record.
   void remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t now, uint64_t* out,
                            hipStream_t s);
+  // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
+  // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
+  // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte
+  // moves. hit[i] = 1 iff a live entry matched and was updated (counted as `touched`).
+  // `key_bytes` + `key_offs` (nullable together; the packed layout of digest_keys: key i =
+  // key_bytes[key_offs[i] .. key_offs[i + 1])): the row only matches a record whose stored
+  // keyed value ([u16 klen | key | payload], keyed.h) carries exactly that key, so a digest
+  // collision cannot change another object's life. Without them the digest decides. Either
+  // way the record must be the entry's own (digest, vlen, magic), else the row is a miss.
+  // Empty, locked, expired, overwritten and deleted entries are misses and stay as they are;
+  // an expiry that is non-zero and <= now kills the object (and is a hit). Rows that repeat
+  // a digest: which one wins is unspecified.
+  // All arrays are device pointers or mapped pinned memory. Asynchronous and ordered on `s`
+  // like remove(): no allocation, no synchronisation. Exact when ordered against whole SET
+  // chains (StoreOpts::phase == 0); refused while a phase-1 batch waits for its phase 2 (a
+  // detached hand's move rewrites the expiry it staged). See k_touch for what holds beside a
+  // SET chain on another stream.
+  void touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
+             const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
+             uint32_t now, hipStream_t s);
   // Reclaim index slots whose items expired or were overwritten. Synchronises;
   // returns {live entries, live item bytes}.
   void sweep(uint32_t now, hipStream_t s, uint64_t* live_entries, uint64_t* live_bytes);

@@ -35,6 +35,10 @@
 //   k_purge_prefix one lane per index slot (k_sweep's traversal): a live entry's record is
 //                  read from the log and the entry removed if its stored key starts with
 //                  the pattern (16-B granules against a host-prepared, shifted image).
+//   k_touch        16 lanes per key (k_delete's probe): the newest live entry's expiry is
+//                  replaced in place by a CAS that keeps the CLOCK bit, and the record
+//                  header's expiry / flags with it; with key bytes only a record whose
+//                  stored key is exactly the row's (16-B granules, one per lane).
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -3116,6 +3120,188 @@ __global__ __launch_bounds__(kBlock) void k_purge_prefix(
   }
 }
 
+// Touch: change an object's expiry (and optionally its flags) in place. 16 lanes per key,
+// as k_delete: the group reads the digest's two buckets (two 128-B lines), pair-lane
+// shuffles join the entry halves and a max-reduce keeps the newest live match (what a GET
+// finds). The entry's record header is then read (32 B) and, when key bytes are given, its
+// stored key compared in 16-B granules, one granule per lane (k_purge_prefix's checks); a row
+// moves two index lines, the record header and the key's granules, and writes 8 + 4 (+ 4)
+// bytes — no value byte is read or written.
+//
+// What it relies on. Exactness (every row whose object was stored before the call and is
+// live is updated, nothing else) comes from stream order against whole SET chains
+// (StoreOpts::phase == 0): the backends queue it between them. Beside a SET chain on another
+// stream it stays memory-safe and never changes an entry of another key: liveness is judged
+// at the furthest byte the queued appends have claimed (a record about to be overwritten is
+// a miss and its bytes are not written), the record must carry the entry's digest, vlen and
+// the magic word, every read stays inside [record, record + item_bytes(vlen)) with vlen <=
+// max_item, and the expiry goes in by a CAS of the very {vlen | expire} word that was read
+// with the digest and the loc (only kRefBit, which a GET hit sets meanwhile, may differ and
+// is kept). The word does not hold the digest, so the slot is read again after the CAS: if an
+// insert re-claimed it for another entry with an equal word in between, the same CAS puts
+// the old expiry back. After the header store the entry's loc is read once more and the row
+// repeated against the new record if it moved (kTouchRounds in all). A detached CLOCK hand
+// rewrites the word from the value it staged: HbmCache::touch refuses while one is pending.
+constexpr int kTouchRounds = 4;    // probes of a row whose entry changed under it
+constexpr int kTouchCasTries = 8;  // CAS attempts against GET hits setting kRefBit
+
+// The u32 at value offset p (a multiple of 4) of the keyed image [u16 klen | key] of the
+// packed key kb[0..klen); bytes past the key read as 0.
+__device__ __forceinline__ uint32_t touch_key_word(const uint8_t* __restrict__ kb, uint32_t klen,
+                                                   uint32_t p) {
+  if (p >= 4 && p + 2 <= klen) {  // key bytes p - 2 .. p + 1
+    uint32_t w;
+    __builtin_memcpy(&w, kb + (p - 2), 4);
+    return w;
+  }
+  uint32_t w = 0;
+#pragma unroll
+  for (uint32_t b = 0; b < 4; ++b) {
+    const uint32_t q = p + b;
+    const uint32_t byte = q < 2 ? (klen >> (8 * q)) & 0xffu : (q - 2 < klen ? kb[q - 2] : 0u);
+    w |= byte << (8 * b);
+  }
+  return w;
+}
+// The bytes of that word that belong to the image (2 + klen bytes in all).
+__device__ __forceinline__ uint32_t touch_word_mask(uint32_t klen, uint32_t p) {
+  const uint32_t end = (uint32_t)kKeyedPrefix + klen;
+  return p + 4 <= end ? ~0u : (p >= end ? 0u : (1u << (8 * (end - p))) - 1u);
+}
+
+__global__ __launch_bounds__(kBlock) void k_touch(
+    const Digest* __restrict__ keys, int64_t n, const uint32_t* __restrict__ expire,
+    const uint32_t* __restrict__ flags, const uint8_t* __restrict__ kbytes,
+    const int64_t* __restrict__ koffs, Entry* __restrict__ index, uint64_t mask,
+    uint8_t* __restrict__ log, const uint64_t* __restrict__ head_ptr,
+    const uint64_t* __restrict__ claim_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    uint8_t* __restrict__ hit, CacheCounters* __restrict__ ctr) {
+  const int l16 = threadIdx.x & 15;
+  const int gbase = threadIdx.x & 48;  // this group's first lane within the wave
+  const bool even = (l16 & 1) == 0;
+  // the head the queued appends reach (equal to the head slot once they have run)
+  const uint64_t hs = *head_ptr, hc = *claim_ptr;
+  const uint64_t head = hc > hs ? hc : hs;
+  const int64_t ngroups = ((int64_t)gridDim.x * kBlock) >> 4;
+  unsigned long long touched = 0;
+  for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 4; i < n; i += ngroups) {
+    const Digest d = keys[i];
+    const uint32_t nexp = expire[i];
+    const uint64_t b = (l16 < 8) ? bucket1(d, mask) : bucket2(d, mask);
+    Entry* const bucket = index + b * kEntriesPerBucket;
+    int f = 0;  // uniform in the group
+    for (int round = 0; round < kTouchRounds; ++round) {
+      uint64_t a, c;
+      if (round == 0) {
+        const uint4 v = reinterpret_cast<const uint4*>(bucket)[l16 & 7];
+        a = pack2(v.x, v.y);
+        c = pack2(v.z, v.w);
+      } else {  // agent-scope loads: a repeat must see what changed the entry, not stale L1
+        const uint64_t* const q = reinterpret_cast<const uint64_t*>(bucket) + 2 * (l16 & 7);
+        a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        c = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      // even lane: d0, d1 | odd lane: loc, vlen | expire << 32
+      const uint64_t pa = __shfl_xor(a, 1), pc = __shfl_xor(c, 1);
+      const bool live = even && a == d.lo && c == d.hi &&
+                        entry_live(pa, (uint32_t)(pc >> 32), head, cap, now);
+      // max-reduce over all 16 lanes (the odd ones start empty and take their partner's in
+      // the first step), ties to the lower lane: hl, hw end uniform in the group
+      uint64_t hl = live ? pa : 0;
+      int hw = l16;
+#pragma unroll
+      for (int sh = 1; sh < 16; sh <<= 1) {
+        const uint64_t ol = __shfl_xor(hl, sh);
+        const int ow = __shfl_xor(hw, sh);
+        if (ol > hl || (ol == hl && ow < hw)) {
+          hl = ol;
+          hw = ow;
+        }
+      }
+      if (hl == 0) break;  // no live entry
+      const uint64_t ve = __shfl(pc, gbase + hw);  // the winner's {vlen | expire} word
+      const uint32_t vlen = entry_vlen((uint32_t)ve);
+      // (vlen <= max_item and an aligned loc hold for every stored entry: they keep the
+      // reads and the header store of an entry debug_set_entry made up inside the log's slack)
+      if (vlen > max_item || ((hl - 1) & 15)) break;
+      uint8_t* const recb = log + (hl - 1) % cap;
+      const uint4* const rec = reinterpret_cast<const uint4*>(recb);
+      const uint4 ha = rec[0], hb = rec[1];
+      // the entry's own record: digest, vlen and magic (ItemHeader's words)
+      if (pack2(ha.x, ha.y) != d.lo || pack2(ha.z, ha.w) != d.hi || hb.x != vlen ||
+          hb.w != kItemMagic)
+        break;
+      if (kbytes) {
+        const int64_t k0 = koffs[i], klen64 = koffs[i + 1] - k0;
+        if (klen64 < 0 || klen64 > (int64_t)kMaxKeyedKey || kKeyedPrefix + klen64 > vlen) break;
+        const uint32_t klen = (uint32_t)klen64;
+        const uint8_t* const kb = kbytes + k0;
+        const uint32_t ngran = (uint32_t)((kKeyedPrefix + klen + 15) >> 4);
+        bool eq = true;
+        for (uint32_t g = l16; g < ngran && eq; g += 16) {
+          const uint4 v = rec[2 + g];
+          const uint32_t p = g * 16;
+          eq = (((v.x ^ touch_key_word(kb, klen, p)) & touch_word_mask(klen, p)) |
+                ((v.y ^ touch_key_word(kb, klen, p + 4)) & touch_word_mask(klen, p + 4)) |
+                ((v.z ^ touch_key_word(kb, klen, p + 8)) & touch_word_mask(klen, p + 8)) |
+                ((v.w ^ touch_key_word(kb, klen, p + 12)) & touch_word_mask(klen, p + 12))) == 0u;
+        }
+        if ((__ballot(!eq) >> gbase) & 0xffffull) break;  // another key's record (or no keyed one)
+      }
+      Entry* const slot = index + (hw < 8 ? bucket1(d, mask) : bucket2(d, mask)) * kEntriesPerBucket +
+                          ((hw & 7) >> 1);
+      int st = 0;  // 0: the entry changed under the row, 1: done, 2: updated, but it moved
+      if (l16 == 0) {
+        unsigned long long* const w = reinterpret_cast<unsigned long long*>(&slot->vlen);
+        unsigned long long expect = ve, want = 0;
+        for (int t = 0; t < kTouchCasTries; ++t) {
+          want = (expect & 0xffffffffull) | ((unsigned long long)nexp << 32);
+          const unsigned long long prev = atomicCAS(w, expect, want);
+          if (prev == expect) {
+            st = 1;
+            break;
+          }
+          if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
+          expect = prev;
+        }
+        if (st) {
+          const uint64_t* const q = reinterpret_cast<const uint64_t*>(slot);
+          const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (e0 != d.lo || e1 != d.hi || e2 != hl) {
+            // the slot passed to another entry with an equal word: put its expiry back
+            unsigned long long cur = want;
+            for (int t = 0; t < 2; ++t) {
+              const unsigned long long prev =
+                  atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
+              if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
+              cur = prev;
+            }
+            st = 0;
+          }
+        }
+        if (st) {
+          ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
+          h->expire = nexp;
+          if (flags) h->flags = flags[i];
+          const uint64_t l2 = __hip_atomic_load(reinterpret_cast<const uint64_t*>(slot) + 2,
+                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (l2 != hl) st = 2;
+        }
+      }
+      st = __shfl(st, gbase);
+      f |= st != 0;
+      if (st == 1) break;
+    }
+    if (l16 == 0) {
+      touched += f;
+      if (hit) hit[i] = (uint8_t)f;
+    }
+  }
+  block_count(ctr, touched, &CacheCounters::touched);
+}
+
 // Export the digests of all live entries (rebalancing / warm restore). One atomic
 // per workgroup per pass reserves the output range; lanes write in block order.
 __global__ __launch_bounds__(kBlock) void k_export(const Entry* __restrict__ index, uint64_t nslots,
@@ -4266,6 +4452,24 @@ void HbmCache::remove(const Digest* keys, int64_t n, uint8_t* found, uint32_t no
   DeviceGuard g(cfg_.device);
   hipLaunchKernelGGL(k_delete, dim3(grid_for(n * 16, kBlock, kMaxGrid)), dim3(kBlock), 0, s, keys, n,
                      index_, cfg_.nbuckets - 1, cur_head(), cfg_.log_bytes, now, found, ctr_);
+  HIP_OK(hipGetLastError());
+}
+
+void HbmCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
+                     const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
+                     uint32_t now, hipStream_t s) {
+  TraceRange tr("hbm.touch");
+  if (n <= 0) return;
+  SH_CHECK(keys && expire, "touch needs digests and expiries");
+  SH_CHECK((key_bytes == nullptr) == (key_offs == nullptr),
+           "touch takes key bytes and their offsets together");
+  std::lock_guard<std::mutex> lk(mu_);
+  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
+  SH_CHECK(!pend_.active, "touch while a phase-1 SET batch is pending");
+  DeviceGuard g(cfg_.device);
+  hipLaunchKernelGGL(k_touch, dim3(grid_for(n * 16, kBlock, kMaxGrid)), dim3(kBlock), 0, s, keys,
+                     n, expire, flags, key_bytes, key_offs, index_, cfg_.nbuckets - 1, log_,
+                     cur_head(), claim_ptr(), cfg_.log_bytes, cfg_.max_item, now, hit, ctr_);
   HIP_OK(hipGetLastError());
 }
 

@@ -408,6 +408,50 @@ void HostCache::remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32
   }
 }
 
+void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
+                      const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
+                      uint32_t now) {
+  SH_CHECK(n <= 0 || (keys && expire), "touch needs digests and expiries");
+  SH_CHECK((key_bytes == nullptr) == (key_offs == nullptr),
+           "touch takes key bytes and their offsets together");
+  std::lock_guard<std::mutex> lk(mu_);
+  for (int64_t i = 0; i < n; ++i) {
+    const Digest& d = keys[i];
+    if (hit) hit[i] = 0;
+    // the newest live entry of the digest (what a GET finds)
+    Entry* e = nullptr;
+    for (uint64_t b : {bucket1(d, mask_), bucket2(d, mask_)})
+      for (uint32_t k = 0; k < kEntriesPerBucket; ++k) {
+        Entry& x = index_[b * kEntriesPerBucket + k];
+        if (x.d0 == d.lo && x.d1 == d.hi && entry_live(x.loc, x.expire, head_, log_bytes_, now) &&
+            (!e || x.loc > e->loc))
+          e = &x;
+      }
+    if (!e) continue;
+    const uint32_t vlen = entry_vlen(e->vlen);
+    if (vlen > max_item_ || ((e->loc - 1) & 15)) continue;
+    uint8_t* const rec = log_ + (e->loc - 1) % log_bytes_;
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    if (h.magic != kItemMagic || h.d0 != e->d0 || h.d1 != e->d1 || h.vlen != vlen) continue;
+    if (key_bytes) {
+      const int64_t klen = key_offs[i + 1] - key_offs[i];
+      if (klen < 0 || klen > (int64_t)kMaxKeyedKey || kKeyedPrefix + (uint64_t)klen > vlen) continue;
+      const uint8_t* const v = rec + kItemHeaderBytes;
+      uint16_t kl;
+      std::memcpy(&kl, v, kKeyedPrefix);
+      if (kl != klen || (klen && std::memcmp(v + kKeyedPrefix, key_bytes + key_offs[i], (size_t)klen)))
+        continue;
+    }
+    e->expire = expire[i];  // (vlen, and kRefBit in it, stay)
+    h.expire = expire[i];
+    if (flags) h.flags = flags[i];
+    std::memcpy(rec, &h, sizeof(h));
+    ctr_.touched++;
+    if (hit) hit[i] = 1;
+  }
+}
+
 uint64_t HostCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now) {
   std::lock_guard<std::mutex> lk(mu_);
   uint64_t m = 0;

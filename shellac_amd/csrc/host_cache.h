@@ -36,6 +36,13 @@ class HostCache {
   // whose stored key starts with prefix[0..plen), 1 <= plen <= 65535;
   // out = {entries removed, their item bytes}, also counted as `purged`.
   void remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now, uint64_t out[2]);
+  // In-place change of expiry (and flags, nullable) of each row's live entry, in the index
+  // and in the record header (HbmCache::touch, whose semantic reference this is). With key
+  // bytes (nullable with their offsets) a row only matches a keyed record of exactly that key.
+  // hit[i] = 1 iff a live entry was updated, also counted as `touched`.
+  void touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
+             const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
+             uint32_t now);
   void flush();
   // Tests: see HbmCache::debug_bucket / debug_set_entry.
   std::vector<uint64_t> debug_bucket(uint64_t b);

@@ -166,7 +166,7 @@ struct CacheCounters {
   // landed after the hand read the index): their log bytes are dead on arrival
   unsigned long long reinsert_lost;
   unsigned long long purged;        // live entries removed by remove_keyed_prefix()
-  unsigned long long reserved[1];
+  unsigned long long touched;       // live entries whose expiry touch() changed in place
 };
 static_assert(sizeof(CacheCounters) == 128, "CacheCounters layout");
 

@@ -22,6 +22,8 @@ enum Op : uint8_t {
   DECREMENT = 0x06, QUIT = 0x07, FLUSH = 0x08, GETQ = 0x09, NOOP = 0x0a, VERSION = 0x0b,
   GETK = 0x0c, GETKQ = 0x0d, APPEND = 0x0e, PREPEND = 0x0f, STAT = 0x10, SETQ = 0x11,
   ADDQ = 0x12, REPLACEQ = 0x13, DELETEQ = 0x14, QUITQ = 0x17, FLUSHQ = 0x18, TOUCH = 0x1c,
+  // get-and-touch (extras: exptime): answered as GET / GETQ / GETK / GETKQ
+  GAT = 0x1d, GATQ = 0x1e, GATK = 0x23, GATKQ = 0x24,
 };
 
 enum Status : uint16_t {

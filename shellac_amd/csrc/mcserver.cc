@@ -315,14 +315,60 @@ void McReactor::handle(McClient* c, const mc::Frame& f) {
     }
     case mc::TOUCH: {
       const uint32_t ttl = f.h.extlen >= 4 ? mc::exptime_to_relative(mc::get32(f.extras), unix_now()) : 0;
-      be->get(key, d, this, [this, be, cid, s, key, d, ttl, reply](bool hit, CacheValue v) {
-        finish(cid, s, [&](McSlot* sl) {
-          if (!hit || !v.data) {
-            reply(sl, mc::KEY_ENOENT, "", "", "Not found");
-            return;
-          }
-          be->set(key, d, v.data, v.flags, ttl);
-          reply(sl, mc::OK, "", "", "");
+      // in place where the tier can (1 / 0); a tier that cannot (-1) gets the object read
+      // and stored again
+      be->touch(key, d, ttl, nullptr, this, [this, be, cid, s, key, d, ttl, reply](int st) {
+        if (st >= 0) {
+          finish(cid, s, [&](McSlot* sl) {
+            if (st) reply(sl, mc::OK, "", "", "");
+            else reply(sl, mc::KEY_ENOENT, "", "", "Not found");
+          });
+          return;
+        }
+        be->get(key, d, this, [this, be, cid, s, key, d, ttl, reply](bool hit, CacheValue v) {
+          finish(cid, s, [&](McSlot* sl) {
+            if (!hit || !v.data) {
+              reply(sl, mc::KEY_ENOENT, "", "", "Not found");
+              return;
+            }
+            be->set(key, d, v.data, v.flags, ttl);
+            reply(sl, mc::OK, "", "", "");
+          });
+        });
+      });
+      return;
+    }
+    case mc::GAT: case mc::GATQ: case mc::GATK: case mc::GATKQ: {
+      // touch, then GET (ordered on the tier: the GET is issued behind the touch); the reply
+      // is a GET's. Where the tier cannot touch: GET, then SET with the new expiry.
+      if (f.h.extlen < 4) {
+        reply(s, mc::INVALID_ARGS, "", "", "Invalid arguments");
+        s->ready = true;
+        return;
+      }
+      const uint32_t ttl = mc::exptime_to_relative(mc::get32(f.extras), unix_now());
+      const bool quiet = op == mc::GATQ || op == mc::GATKQ;
+      const bool withkey = op == mc::GATK || op == mc::GATKQ;
+      be->touch(key, d, ttl, nullptr, this,
+                [this, be, cid, s, quiet, withkey, key, d, ttl, reply](int st) {
+        if (st == 0) {
+          finish(cid, s, [&](McSlot* sl) {
+            if (!quiet) reply(sl, mc::KEY_ENOENT, withkey ? key : std::string(), "", "Not found");
+          });
+          return;
+        }
+        be->get(key, d, this, [this, be, cid, s, quiet, withkey, key, d, ttl, st, reply](
+                                  bool hit, CacheValue v) {
+          finish(cid, s, [&](McSlot* sl) {
+            if (hit && v.data) {
+              if (st < 0) be->set(key, d, v.data, v.flags, ttl);
+              std::string ex;
+              mc::put32(ex, v.flags);
+              reply(sl, mc::OK, withkey ? key : std::string(), ex, v.data.str());
+            } else if (!quiet) {
+              reply(sl, mc::KEY_ENOENT, withkey ? key : std::string(), "", "Not found");
+            }
+          });
         });
       });
       return;

@@ -196,6 +196,27 @@ bool ObjectCache::del(const std::string& key, const Digest& d, uint32_t now) {
   return true;
 }
 
+bool ObjectCache::touch(const std::string& key, const Digest& d, uint32_t expire,
+                        const uint32_t* flags, uint32_t now) {
+  Stripe& s = stripe(d);
+  std::vector<std::shared_ptr<const std::string>> dead;
+  std::lock_guard<std::mutex> lk(s.mu);
+  int32_t* pos = find(s, d);
+  if (!pos) return false;
+  Obj& o = s.slots[(size_t)*pos];
+  if (o.expire && o.expire <= now) {
+    erase_slot(s, pos, &dead);
+    s.st.expired++;
+    return false;
+  }
+  size_t po = 0;
+  if (!keyed_match(o.data->data(), o.data->size(), key, &po)) return false;
+  o.expire = expire;
+  if (flags) o.flags = *flags;
+  s.st.touched++;
+  return true;
+}
+
 uint64_t ObjectCache::purge_prefix(const std::string& prefix, uint32_t now) {
   uint64_t removed = 0;
   for (auto& sp : stripes_) {
@@ -246,6 +267,7 @@ ObjectCacheStats ObjectCache::stats() const {
     t.evictions += s.st.evictions;
     t.expired += s.st.expired;
     t.key_mismatch += s.st.key_mismatch;
+    t.touched += s.st.touched;
     t.objects += s.live;
     t.bytes += s.bytes;
   }

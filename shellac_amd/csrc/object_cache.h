@@ -28,6 +28,7 @@ namespace shellac {
 
 struct ObjectCacheStats {
   uint64_t gets = 0, hits = 0, sets = 0, evictions = 0, expired = 0, key_mismatch = 0;
+  uint64_t touched = 0;
   uint64_t objects = 0, bytes = 0;
 };
 
@@ -41,6 +42,11 @@ class ObjectCache {
   void set(const std::string& key, const Digest& d, const char* payload, size_t n,
            uint32_t flags, uint32_t expire, uint32_t now);
   bool del(const std::string& key, const Digest& d, uint32_t now);
+  // In place, under the stripe lock: the live object of exactly `key` gets the absolute
+  // expiry `expire` (0 = never) and, when `flags` is not null, new flags. False on a miss
+  // (absent, expired, or another key's object under a colliding digest: left alone).
+  bool touch(const std::string& key, const Digest& d, uint32_t expire, const uint32_t* flags,
+             uint32_t now);
   // Drops every live object whose stored key starts with `prefix` (a walk of every stripe
   // under its lock); returns how many.
   uint64_t purge_prefix(const std::string& prefix, uint32_t now);

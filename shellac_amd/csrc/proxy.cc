@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstdio>
+#include <ctime>
 #include <deque>
 #include <random>
 #include <sstream>
@@ -56,6 +57,43 @@ long cc_max_age(const std::string* cc) {
     }
   }
   return best;
+}
+
+// A Cache-Control directive `name=N` (seconds; `name` lower case with its '='), -1 if absent.
+long cc_seconds(const std::string* cc, const char* name) {
+  if (!cc) return -1;
+  const std::string s = to_lower(*cc);
+  const size_t p = s.find(name);
+  if (p == std::string::npos) return -1;
+  return std::strtol(s.c_str() + p + std::strlen(name), nullptr, 10);
+}
+
+uint32_t unix_now() { return (uint32_t)time(nullptr); }
+
+// The value of header `lname` ("etag:", lower case with its colon) in a serialized
+// response's head, trimmed; empty if the head has none.
+std::string object_header(std::string_view ov, std::string_view lname) {
+  const size_t eoh = ov.find("\r\n\r\n");
+  if (eoh == std::string_view::npos) return std::string();
+  size_t pos = ov.find("\r\n");
+  while (pos != std::string_view::npos && pos < eoh) {
+    const size_t ls = pos + 2;
+    const size_t le = ov.find("\r\n", ls);
+    const std::string_view line = ov.substr(ls, le - ls);
+    if (line.size() > lname.size()) {
+      bool match = true;
+      for (size_t i = 0; i < lname.size() && match; ++i)
+        match = (char)std::tolower((unsigned char)line[i]) == lname[i];
+      if (match) {
+        size_t a = lname.size(), b = line.size();
+        while (a < b && (line[a] == ' ' || line[a] == '\t')) ++a;
+        while (b > a && (line[b - 1] == ' ' || line[b - 1] == '\t')) --b;
+        return std::string(line.substr(a, b - a));
+      }
+    }
+    pos = le;
+  }
+  return std::string();
 }
 
 // ---- content negotiation + Vary (policy "rfc") ----------------------------------------
@@ -188,6 +226,7 @@ struct Slot {
   bool vary_probe = false;  // `key` is a variant key (second lookup after a marker)
   // request headers, kept for the miss path when a response may Vary (policy rfc)
   std::shared_ptr<const std::vector<Header>> req_headers;
+  Bytes vary_marker;  // --grace: the URL's marker a variant lookup went through
   int attempts = 0;
   double t0 = 0;
 };
@@ -224,6 +263,10 @@ struct Pend {
   std::string base_key;
   std::shared_ptr<const std::vector<Header>> req_headers;
   uint64_t purge_gen = 0;  // Proxy::purge_generation() when the fetch was forwarded
+  // A background revalidation (--grace): no client slot (client_id 0); `stale` is the object
+  // that was served stale, `marker` its URL's Vary marker (null: the key is the URL's).
+  bool reval = false;
+  Bytes stale, marker;
 };
 
 struct Upstream : Conn {
@@ -259,6 +302,10 @@ class Reactor : public Executor {
       streamed{0}, stream_pauses{0}, gzip_gpu_bodies{0}, gzip_gpu_inflated{0}, identity_decoded{0},
       vary_stored{0},
       vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0};
+  // --grace: stale hits served, background revalidations started, their 304s, the objects
+  // those extended in place / stored again, and revalidations the origin failed
+  std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
+      revalidate_touched{0}, revalidate_restored{0}, revalidate_errors{0};
   // event-loop health: the longest iteration (events handled between two epoll_waits)
   // and how many took over 10 ms — a reactor that stalls stops accepting connections
   std::atomic<uint64_t> loop_max_us{0}, loop_slow{0}, client_resets{0};
@@ -294,7 +341,15 @@ class Reactor : public Executor {
   void resume_stream(uint64_t up_id);
   void stream_out(Upstream* u, std::string data, bool last);
   Upstream* pick_upstream(Client* c);
+  Upstream* connect_upstream();  // a new connection to a server in rotation (no owner yet)
   int choose_server();
+  // --grace (ProxyConfig::grace)
+  uint32_t grace_for(const HttpParser& r) const;
+  void revalidate(Slot* s, const Bytes& stale);
+  void revalidation_answered(HttpParser& r, const Pend& p);
+  void revalidation_failed(const Pend& p);
+  // keys whose revalidation failed: no new attempt before this time (upstream_retry_s)
+  std::unordered_map<std::string, double> reval_retry_at_;
   void flush_client(Client* c);
   void flush_upstream(Upstream* u);
   void complete_slot(Client* c, Slot* s, Bytes data);
@@ -719,6 +774,7 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
       s->key = vary_key(s->base_key, marker_names(v.data->view()), s->req->headers());
       s->d = digest_bytes(reinterpret_cast<const uint8_t*>(s->key.data()), s->key.size());
       s->vary_probe = true;
+      if (cfg_.grace) s->vary_marker = v.data;
       px_->backend_->get(s->key, s->d, this, [this, cid, seq](bool h2, CacheValue v2) {
         on_cache(cid, seq, h2, std::move(v2));
       });
@@ -729,6 +785,12 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
   if (hit && v.data) {
     hits++;
     if (s->vary_probe) vary_hits++;
+    // --grace: past its freshness time (the flags word) the object is served stale, and
+    // revalidated in the background (before deliver(): that gives the parsed request back)
+    if (cfg_.grace && v.flags && unix_now() >= v.flags) {
+      stale_served++;
+      revalidate(s, v.data);
+    }
     deliver(c, s, v.data);
     return;
   }
@@ -951,6 +1013,16 @@ Upstream* Reactor::pick_upstream(Client* c) {
       return u;
     }
   }
+  Upstream* u = connect_upstream();
+  if (u) {
+    u->owner = c;
+    c->up = u;
+  }
+  return u;
+}
+
+Upstream* Reactor::connect_upstream() {
+  const double t = now_s();
   for (int attempt = 0; attempt < (int)cfg_.upstreams.size() + 1; ++attempt) {
     const int srv = choose_server();
     if (srv < 0) return nullptr;
@@ -975,8 +1047,6 @@ Upstream* Reactor::pick_upstream(Client* c) {
     epoll_ctl(epfd_, EPOLL_CTL_ADD, fd, &ev);
     u->out_armed = true;
     upstreams++;
-    u->owner = c;
-    c->up = u;
     return u;
   }
   return nullptr;
@@ -1027,6 +1097,121 @@ void Reactor::forward(Client* c, Slot* s) {
   flush_upstream(u);
 }
 
+// ---- grace and revalidation (ProxyConfig::grace) --------------------------------------
+// Seconds a response may be served past its TTL: the configured grace, or under policy rfc
+// the response's own stale-while-revalidate / stale-if-error (the larger; 0: none).
+uint32_t Reactor::grace_for(const HttpParser& r) const {
+  if (!cfg_.grace) return 0;
+  if (cfg_.policy != "rfc") return cfg_.grace;
+  const std::string* cc = r.header("cache-control");
+  const long swr = cc_seconds(cc, "stale-while-revalidate="), sie = cc_seconds(cc, "stale-if-error=");
+  if (swr < 0 && sie < 0) return cfg_.grace;
+  return (uint32_t)std::max<long>(std::max(swr, sie), 0);
+}
+
+// A stale hit starts the key's background revalidation unless one (or a miss's fetch) is
+// already under way on this reactor — the waiters table collapses them, and later stale
+// hits are simply served stale — or the last one failed less than upstream_retry_s ago.
+// The request is the client's own (so a Vary'd variant is asked for with its headers), made
+// conditional on the stored object's validators; it holds no client slot.
+void Reactor::revalidate(Slot* s, const Bytes& stale) {
+  if (!s->req || s->req->method() != "GET" || inflight_.count(s->key)) return;
+  const double t = now_s();
+  const auto back = reval_retry_at_.find(s->key);
+  if (back != reval_retry_at_.end()) {
+    if (t < back->second) return;
+    reval_retry_at_.erase(back);
+  }
+  HttpParser& q = *s->req;
+  Pend p{0, 0, s->key, s->d, true, false, true, s->base_key, nullptr, px_->purge_generation()};
+  if (cfg_.policy == "rfc")
+    p.req_headers = std::make_shared<const std::vector<Header>>(q.headers());
+  p.reval = true;
+  p.stale = stale;
+  p.marker = s->vary_marker;
+  // the stored validators replace whatever conditions the client sent
+  for (const char* h : {"if-none-match", "if-modified-since", "if-match", "if-unmodified-since",
+                        "if-range", "range"})
+    q.remove_header(h);
+  const std::string etag = object_header(stale->view(), "etag:");
+  const std::string lm = object_header(stale->view(), "last-modified:");
+  if (!etag.empty()) q.set_header("if-none-match", etag);
+  if (!lm.empty()) q.set_header("if-modified-since", lm);
+  const std::string fwd = upstream_request(q);
+  revalidations++;
+  Upstream* u = nullptr;
+  for (Upstream* x : pool_)  // an idle pooled connection, else a new one
+    if (!x->owner && x->pend.empty() && !x->dead && px_->upstream_healthy(x->server) &&
+        px_->upstream_up(x->server, t) && x->count < x->ka_max &&
+        (x->ka_timeout < 0 || t - x->atime < x->ka_timeout)) {
+      u = x;
+      break;
+    }
+  if (!u) u = connect_upstream();
+  if (!u) {
+    revalidation_failed(p);
+    return;
+  }
+  inflight_[s->key];  // misses of the key that arrive meanwhile wait for the answer
+  u->out.write(fwd);
+  u->pend.push_back(std::move(p));
+  u->count++;
+  upstream_reqs++;
+  flush_upstream(u);
+}
+
+// The origin failed the revalidation (no upstream, connect failure, a dead connection or a
+// 5xx): nothing is stored, the stale object stays servable until its hard expiry
+// (stale-if-error), and the key is not tried again for upstream_retry_s.
+void Reactor::revalidation_failed(const Pend& p) {
+  revalidate_errors++;
+  if (reval_retry_at_.size() > 4096) reval_retry_at_.clear();
+  reval_retry_at_[p.key] = now_s() + cfg_.upstream_retry_s;
+  release_waiters(p.key, nullptr);  // misses that queued behind it fetch for themselves
+}
+
+// 304: the stored object is good for another (ttl, grace) — from the 304's Cache-Control
+// when it has one — and is extended in place; a tier that cannot touch (memcached), or that
+// lost the object meanwhile, gets the stale object stored again. The stored headers are not
+// rewritten from the 304. A PURGE of the key since the request left wins: nothing is touched.
+// 5xx: a failure.
+void Reactor::revalidation_answered(HttpParser& r, const Pend& p) {
+  if (r.status() != 304) {
+    revalidation_failed(p);
+    return;
+  }
+  revalidated_304++;
+  if (px_->purged_since(p.purge_gen, p.key, p.base_key)) {
+    fills_purged++;
+    release_waiters(p.key, nullptr);
+    return;
+  }
+  uint32_t ttl = cfg_.ttl;
+  const long ma = cfg_.policy == "rfc" ? cc_max_age(r.header("cache-control")) : -1;
+  if (ma > 0) ttl = (uint32_t)ma;
+  const uint32_t grace = grace_for(r), hard = ttl + grace;
+  const uint32_t fresh_until = grace ? unix_now() + ttl : 0;
+  CacheBackend* be = px_->backend_.get();
+  const auto extend = [this, be, hard, fresh_until](const std::string& key, const Digest& d,
+                                                     const Bytes& obj, bool count) {
+    be->touch(key, d, hard, &fresh_until, this, [this, be, key, d, obj, hard, fresh_until,
+                                                  count](int st) {
+      if (st == 1) {
+        if (count) revalidate_touched++;
+        return;
+      }
+      be->set(key, d, obj, fresh_until, hard);
+      if (count) revalidate_restored++;
+    });
+  };
+  if (p.marker && p.key != p.base_key)
+    extend(p.base_key, digest_bytes(reinterpret_cast<const uint8_t*>(p.base_key.data()),
+                                    p.base_key.size()), p.marker, false);
+  extend(p.key, p.d, p.stale, true);
+  reval_retry_at_.erase(p.key);
+  release_waiters(p.key, p.stale);
+}
+
 void Reactor::flush_upstream(Upstream* u) {
   if (u->dead) return;
   if (!u->connected) {
@@ -1073,6 +1258,10 @@ void Reactor::release_waiters(const std::string& key, Bytes obj) {
 }
 
 void Reactor::fail_pend(Pend& p, int code, const char* reason) {
+  if (p.reval) {  // no client to answer and no retry: the next stale hit tries again
+    revalidation_failed(p);
+    return;
+  }
   if (p.lookup && code != 502) release_waiters(p.key, nullptr);
   Client* c = find_client(p.client_id);
   if (!c) {
@@ -1202,6 +1391,19 @@ void Reactor::on_upstream_response(Upstream* u) {
     u->ka_max = kap.second;
     return;
   }
+  if (p.reval && (r.status() == 304 || r.status() >= 500)) {
+    // a background revalidation's 304 or failure (any other answer is a fill like a miss's)
+    revalidation_answered(r, p);
+    if (!ka) {
+      server_nka_[u->server] = 1;
+      close_upstream(u);
+      return;
+    }
+    server_nka_[u->server] = 0;
+    u->ka_timeout = kap.first;
+    u->ka_max = kap.second;
+    return;
+  }
   rewrite_response_headers(r);
   const std::string* ce = r.header("content-encoding");
   bool deferred = false;
@@ -1272,6 +1474,10 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
   uint32_t ttl = cfg_.ttl;
   bool cached = false, waiters_share = true;
   if (p.lookup && !p.head && cacheable_response(r, &ttl)) {
+    // --grace: kept `grace` seconds past the TTL, the flags word says when it stops being
+    // fresh (0 with grace off: stored exactly as without the option)
+    const uint32_t grace = grace_for(r), hard_ttl = ttl + grace;
+    const uint32_t fresh_until = grace ? unix_now() + ttl : 0;
     if (px_->purged_since(p.purge_gen, p.key, p.base_key)) {
       // fetched before a purge of this key: delivered (the collapsed waiters share it as
       // they would have), not stored
@@ -1282,7 +1488,8 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
                         p.key == vary_key(p.base_key, vnames, *p.req_headers);
     } else if (vnames.empty()) {
       cached = true;
-      px_->backend_->set(p.key, p.d, obj, 0, ttl);  // Server.py:432 mc.set(key, obj, time=ttl)
+      // Server.py:432 mc.set(key, obj, time=ttl)
+      px_->backend_->set(p.key, p.d, obj, fresh_until, hard_ttl);
       cache_sets++;
     } else if (vnames[0] != "*" && p.req_headers) {
       // Vary: marker under the URL key, the object under this request's variant key
@@ -1292,9 +1499,9 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
       const Digest bd = digest_bytes(reinterpret_cast<const uint8_t*>(p.base_key.data()),
                                      p.base_key.size());
       const Digest vd = digest_bytes(reinterpret_cast<const uint8_t*>(vk.data()), vk.size());
-      px_->backend_->set(p.base_key, bd, std::make_shared<const std::string>(std::move(marker)), 0,
-                         ttl);
-      px_->backend_->set(vk, vd, obj, 0, ttl);
+      px_->backend_->set(p.base_key, bd, std::make_shared<const std::string>(std::move(marker)),
+                         fresh_until, hard_ttl);
+      px_->backend_->set(vk, vd, obj, fresh_until, hard_ttl);
       cache_sets++;
       vary_stored++;
       cached = true;
@@ -1323,7 +1530,7 @@ bool Reactor::maybe_stream(Upstream* u) {
   if (u->streaming) return true;
   HttpParser& r = *u->resp;
   const Pend& p = u->pend.front();
-  if (p.head || r.body_decoded()) return false;
+  if (p.head || p.reval || r.body_decoded()) return false;  // (a revalidation has no client)
   const int64_t cl = r.content_length();
   const bool big = (!r.chunked() && cl >= 0 && (uint64_t)cl > cfg_.stream_bytes) ||
                    r.body().size() > cfg_.stream_bytes;
@@ -1688,6 +1895,7 @@ std::string Proxy::stats_json() {
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0;
   uint64_t pmax[5] = {}, crst = 0;
+  uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
   for (auto& r : reactors_) {
     req += r->requests; hit += r->hits; miss += r->misses; ur += r->upstream_reqs;
@@ -1703,6 +1911,9 @@ std::string Proxy::stats_json() {
     vh += r->vary_hits;
     prq += r->purge_requests; pob += r->purged_objects; pdn += r->purge_denied;
     fpg += r->fills_purged;
+    gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
+    gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
+    gr[5] += r->revalidate_errors;
     for (int k = 0; k < 5; ++k) pmax[k] = std::max<uint64_t>(pmax[k], r->phase_max_us[k]);
     for (int b = 0; b < kHistBuckets; ++b) h[b] += r->hist[b];
   }
@@ -1730,6 +1941,9 @@ std::string Proxy::stats_json() {
     << ",\"vary_stored\":" << vst << ",\"vary_hits\":" << vh
     << ",\"purge_requests\":" << prq << ",\"purged_objects\":" << pob
     << ",\"purge_denied\":" << pdn << ",\"fills_not_cached_purged\":" << fpg
+    << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
+    << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
+    << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]
     << ",\"loop_max_us\":" << lmax << ",\"loop_slow\":" << lslow
     << ",\"loop_phase_max_us\":{\"accept\":" << pmax[0] << ",\"client\":" << pmax[1]
     << ",\"upstream\":" << pmax[2] << ",\"posted\":" << pmax[3] << ",\"timer\":" << pmax[4]

@@ -42,6 +42,14 @@ struct ProxyConfig {
   // (a dedicated core: no wake-up IPI or idle-state exit per request under load)
   int spin_us = 0;
   uint32_t ttl = 170;                 // -t (Server.py:514)
+  // --grace S (0 = off): a cacheable response is kept for ttl + S seconds and its flags word
+  // holds the unix time at which it stops being fresh. A hit past that time is served stale
+  // at once while one background request per key revalidates it upstream (If-None-Match /
+  // If-Modified-Since from the stored head): a 304 extends the object in place
+  // (CacheBackend::touch), any other cacheable answer replaces it, and an origin that fails
+  // leaves the stale object servable until its hard expiry (RFC 5861; under policy rfc a
+  // response's own stale-while-revalidate / stale-if-error replace S for that object).
+  uint32_t grace = 0;
   bool compress = false;              // -z: gzip uncompressed text before caching
   // >= 0: that GPU does the -z compression, batched across reactors (deflate.h
   // GzipService, one window of gzip_batch_us; the binding installs it with

@@ -606,6 +606,63 @@ class CacheShard:
             self._impl.remove(keys.data_ptr(), n, found.data_ptr(), now)
         return found.bool()
 
+    def touch(self, keys: torch.Tensor, expire: torch.Tensor,
+              flags: Optional[torch.Tensor] = None, key_bytes=None,
+              now: Optional[int] = None) -> torch.Tensor:
+        """Change the expiry of live objects in place (``k_touch`` on a GPU shard): row i's
+        object gets the absolute expiry ``expire[i]`` (int32, 0 = never; a value <= ``now``
+        kills it) and, with ``flags`` (int32 [n]), new flags. The value's bytes do not move.
+        ``key_bytes``: ``(uint8 buffer, int64 offsets[n+1])`` tensors as ``pack_bytes`` lays
+        keys out; then a row only matches a *keyed* value (``keyed(key, payload)``) that
+        carries exactly that key, so a digest collision cannot touch another object.
+        Returns ``hit`` (uint8 [n]): 1 where a live object was updated (also counted in
+        ``counters()["touched"]``). Asynchronous on the current stream, like ``remove``;
+        which of several rows with one digest wins is unspecified."""
+        self._check(keys, "keys")
+        self._check(expire, "expire")
+        n = keys.shape[0]
+        if expire.dtype != torch.int32 or expire.numel() != n:
+            raise TypeError("expire must be int32 [n]")
+        fp = 0
+        if flags is not None:
+            self._check(flags, "flags")
+            if flags.dtype != torch.int32 or flags.numel() != n:
+                raise TypeError("flags must be int32 [n]")
+            fp = flags.data_ptr()
+        kb = ko = 0
+        if key_bytes is not None:
+            buf, offs = key_bytes
+            self._check(buf, "key bytes")
+            self._check(offs, "key offsets")
+            if buf.dtype != torch.uint8 or offs.dtype != torch.int64 or offs.numel() != n + 1:
+                raise TypeError("key_bytes must be (uint8 buffer, int64 offsets[n + 1])")
+            kb, ko = buf.data_ptr(), offs.data_ptr()
+        hit = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        if n == 0:
+            return hit
+        now = self.now() if now is None else now
+        args = (keys.data_ptr(), expire.data_ptr(), fp, kb, ko, n, hit.data_ptr(), now)
+        if self.is_gpu:
+            self._impl.touch(*args, self._s())
+        else:
+            self._impl.touch(*args)
+        return hit
+
+    def touch_many(self, keys: Sequence[bytes], ttl: int, keyed: bool = True) -> list:
+        """``touch`` for byte-string keys, as ``set_many`` / ``get_many``: a new TTL from now
+        (<= 0: never expires). ``keyed``: the objects are keyed values and only exact keys
+        match. Returns one bool per key."""
+        keys = list(keys)
+        d = digest_strings(keys, self.device)
+        ex = torch.full((len(keys),), self.expire_at(ttl), dtype=torch.int32, device=self.device)
+        kb = None
+        if keyed:
+            buf, offs = pack_bytes(keys)
+            buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, np.uint8)
+            kb = (torch.from_numpy(buf.copy()).to(self.device),
+                  torch.from_numpy(offs).to(self.device))
+        return [bool(x) for x in self.touch(d, ex, key_bytes=kb).tolist()]
+
     def remove_keyed_prefix(self, prefix: bytes, now: Optional[int] = None) -> tuple[int, int]:
         """Prefix purge: remove every live object whose stored key starts with ``prefix``
         (1..65535 bytes; an empty prefix is ``flush``). Returns (objects removed, their

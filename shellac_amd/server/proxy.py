@@ -155,8 +155,14 @@ class Server:
                  health_timeout_ms: int = 500, health_fails: int = 2,
                  cpus: Sequence[int] = (), spin_us: int = 0, gzip_gpu: int = -1,
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
-                 max_inflate_bytes: int = 64 << 20, purge: str = "off", **backend_opts):
-        """``purge``: who may invalidate with the ``PURGE`` method — ``"off"`` (default: a
+                 max_inflate_bytes: int = 64 << 20, purge: str = "off", grace: int = 0,
+                 **backend_opts):
+        """``grace`` (seconds, 0 = off): keep cached objects that long past their TTL; a hit
+        in that window is served stale at once while one background request per key
+        revalidates it upstream (``If-None-Match`` / ``If-Modified-Since``) — a 304 extends
+        the object in place, an origin that is down leaves it servable until the grace ends.
+
+        ``purge``: who may invalidate with the ``PURGE`` method — ``"off"`` (default: a
         ``PURGE`` request is forwarded upstream like any other method), ``"loopback"``
         (clients on 127.0.0.0/8; others get 403) or ``"any"``. ``PURGE <url>`` removes the
         URL's object and all its Vary variants; with ``X-Purge-Mode: prefix`` every object
@@ -182,7 +188,7 @@ class Server:
             health_fails=health_fails, cpus=[int(c) for c in cpus], spin_us=int(spin_us),
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
             max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
-            purge=purge)
+            purge=purge, grace=int(grace))
         self._started = False
 
     @property
@@ -287,6 +293,12 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "forwarded upstream), loopback (127.0.0.0/8 only, others get 403) or "
                         "any. 'PURGE /url' drops the URL and its Vary variants; with the header "
                         "'X-Purge-Mode: prefix' everything under that URL prefix")
+    p.add_argument("--grace", type=int, default=0, metavar="S",
+                   help="serve cached objects up to S seconds past their TTL while one "
+                        "background request per key revalidates them upstream (If-None-Match / "
+                        "If-Modified-Since; a 304 extends the object in place), and when the "
+                        "origin is down (stale-if-error). With --policy rfc a response's own "
+                        "stale-while-revalidate / stale-if-error replace S. Default 0: off")
     p.add_argument("--fault", default="",
                    help="fault injection on the cache tier, e.g. get_miss=0.1,set_drop=0.5,"
                         "delay_us=500, down, or gpu_down=K (eject GPU shard K; drills; "
@@ -338,6 +350,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  cpus=parse_cpus(args.cpus), spin_us=args.spin_us,
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
                  max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
+                 grace=args.grace,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,

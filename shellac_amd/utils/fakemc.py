@@ -20,6 +20,7 @@ HDR = struct.Struct(">BBHBBHIIQ")
 GET, SET, ADD, REPLACE, DELETE, INCR, DECR, QUIT, FLUSH, GETQ, NOOP, VERSION, GETK, GETKQ = (
     0x00, 0x01, 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x08, 0x09, 0x0A, 0x0B, 0x0C, 0x0D)
 APPEND, PREPEND, STAT, SETQ, DELETEQ, TOUCH = 0x0E, 0x0F, 0x10, 0x11, 0x14, 0x1C
+GAT, GATQ, GATK, GATKQ = 0x1D, 0x1E, 0x23, 0x24   # get-and-touch (extras: exptime)
 
 
 def frame(magic, op, key=b"", extras=b"", value=b"", status=0, opaque=0, cas=0) -> bytes:
@@ -80,16 +81,21 @@ class FakeMemcached:
         now = time.time()
         with self.lock:
             self.ops += 1
-            if op in (GET, GETQ, GETK, GETKQ):
+            if op in (GET, GETQ, GETK, GETKQ, TOUCH, GAT, GATQ, GATK, GATKQ):
                 item = self.data.get(key)
                 if item and item[2] and item[2] < now:
                     del self.data[key]
                     item = None
-                k = key if op in (GETK, GETKQ) else b""
+                if item and op not in (GET, GETQ, GETK, GETKQ):   # the new expiry
+                    exp = struct.unpack(">I", extras[:4])[0]
+                    item = self.data[key] = (item[0], item[1], (now + exp) if exp else 0)
+                if op == TOUCH:
+                    return frame(0x81, op, status=0 if item else 1, opaque=opaque)
+                k = key if op in (GETK, GETKQ, GATK, GATKQ) else b""
                 if item:
                     return frame(0x81, op, k, struct.pack(">I", item[1]), item[0], opaque=opaque)
-                return b"" if op in (GETQ, GETKQ) else frame(0x81, op, k, value=b"Not found",
-                                                             status=1, opaque=opaque)
+                return b"" if op in (GETQ, GETKQ, GATQ, GATKQ) else frame(
+                    0x81, op, k, value=b"Not found", status=1, opaque=opaque)
             if op in (SET, SETQ, ADD):
                 flags, exp = struct.unpack(">II", extras[:8])
                 if op == ADD and key in self.data:
@@ -161,6 +167,29 @@ class MemcacheClient:
 
     def touch(self, key: bytes, exptime: int) -> int:
         return self._rpc(TOUCH, key, struct.pack(">I", exptime))[1]
+
+    def gat(self, key: bytes, exptime: int, with_key: bool = False):
+        """Get-and-touch (GAT, or GATK): (value, flags) or None; GATK also checks the key."""
+        _, status, _, _, extras, k, value = self._rpc(GATK if with_key else GAT, key,
+                                                      struct.pack(">I", exptime))
+        if status:
+            return None
+        if with_key and k != key:
+            raise ValueError(f"GATK answered for {k!r}")
+        return value, struct.unpack(">I", extras)[0] if extras else 0
+
+    def gat_multi(self, keys, exptime: int) -> dict:
+        """GATQ x n + NOOP: misses are silent; {opaque index: value} of the hits."""
+        ex = struct.pack(">I", exptime)
+        buf = b"".join(frame(0x80, GATQ, k, ex, opaque=i + 1) for i, k in enumerate(keys))
+        self.sock.sendall(buf + frame(0x80, NOOP, opaque=0xFFFF))
+        out = {}
+        while True:
+            op, status, opaque, _, _, _, value = read_frame(self.sock)
+            if op == NOOP:
+                return out
+            if status == 0:
+                out[opaque - 1] = value
 
     def version(self) -> bytes:
         return self._rpc(VERSION)[6]
