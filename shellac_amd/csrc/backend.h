@@ -9,7 +9,10 @@
 //                     fast path, no GPU needed;
 //   HbmBackend        one HBM shard per local MI355X (csrc/hbm_cache.hip), fed by a
 //                     batcher thread that coalesces the GETs/SETs of all reactors
-//                     into one kernel pipeline per GPU per tick;
+//                     into one kernel pipeline per GPU per tick (csrc/backend_hbm.cc the
+//                     request API and routing, hbm_batcher.cc the batcher, hbm_direct.cc
+//                     reactor-direct GETs, hbm_hot.cc hot-object spreading; their shared
+//                     types in hbm_backend_impl.h, host-only decisions in hbm_flight_plan.h);
 //   MemcachedBackend  memcached binary protocol over TCP to remote nodes (real
 //                     memcached or `shellac-cached`), ketama-routed, pipelined on
 //                     persistent connections, with node ejection + retry.
@@ -245,6 +248,26 @@ struct HbmBackendConfig {
   double hot_spray_above = 0;  // 0: 1 / (4 * shards)
 };
 
+// What an HbmBackend request asks of its shard's batcher. A flight runs its requests by kind,
+// in this order: GETs, SETs, DELETEs, touches, hot-replica fills, prefix purges (a barrier
+// only reports that its flight has finished).
+enum class ReqKind : uint8_t { Get, Set, Del, Barrier, Fill, Purge, Touch };
+// changes a key's object: ordered against the key's other requests, counted as pending
+constexpr bool is_write(ReqKind k) {
+  return k == ReqKind::Set || k == ReqKind::Del || k == ReqKind::Touch;
+}
+// names no key and answers through Req::ccb on the batcher thread
+constexpr bool is_ctl(ReqKind k) {
+  return k == ReqKind::Barrier || k == ReqKind::Fill || k == ReqKind::Purge;
+}
+
+struct DigestHash {
+  size_t operator()(const Digest& d) const { return (size_t)(d.lo ^ (d.hi * 0x9E3779B97F4A7C15ull)); }
+};
+struct DigestEq {
+  bool operator()(const Digest& a, const Digest& b) const { return a.lo == b.lo && a.hi == b.hi; }
+};
+
 // One HBM shard per local MI355X. Each GPU has its own batcher thread: requests are
 // routed to their shard's queue by the digest ring, and the batcher keeps up to `depth`
 // batches in flight on its stream — GETs as one edge-GET launch that writes hits
@@ -277,7 +300,8 @@ class HbmBackend : public CacheBackend {
   void direct_detach() override;
 
   struct HotFill;
-  // One purge_prefix call fanned out over the shards: each shard's kind-5 request adds what
+  struct HotRefresh;  // one refresh's state and its steps (hbm_hot.cc)
+  // One purge_prefix call fanned out over the shards: each shard's Purge request adds what
   // its scan removed when its flight is reaped; the last one to finish (or fail) answers.
   struct Purge {
     std::atomic<int> left{0};
@@ -286,21 +310,21 @@ class HbmBackend : public CacheBackend {
     PurgeCallback cb;
   };
   struct Req {
-    int kind;  // 0 get, 1 set, 2 del, 3 barrier, 4 hot-replica fill, 5 prefix purge, 6 touch
+    ReqKind kind = ReqKind::Get;
     Digest d;
     std::string key;
     Bytes value;
     uint32_t flags = 0, ttl = 0;
-    bool has_flags = false;  // kind 6: `flags` replaces the object's (else they stay)
+    bool has_flags = false;  // Touch: `flags` replaces the object's (else they stay)
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
     TouchCallback tcb;
-    // kinds 3 / 4: runs on the batcher thread once the request's flight has finished on
-    // the GPU (ok) or was failed
+    // control requests (is_ctl): runs on the batcher thread once the request's flight has
+    // finished on the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
     std::shared_ptr<HotFill> fill;
-    std::shared_ptr<Purge> purge;  // kind 5 (`key` holds the prefix)
+    std::shared_ptr<Purge> purge;  // Purge (`key` holds the prefix)
   };
   struct Dev;
   struct Direct;
@@ -329,6 +353,11 @@ class HbmBackend : public CacheBackend {
   StatList hot_refresh_locked();
   void enqueue(int dev, Req r);
   void enqueue_many(int dev, std::vector<Req>& rs);
+  // set / del / touch: queues the write `r` on its owner, then (a hot object) on every other
+  // shard in service; false if no shard is in service. `arm(copy, copies, is_owner)` gives
+  // each copy its callback.
+  template <typename Arm>
+  bool route_write(Req r, Arm&& arm);
   uint32_t now() const;
   // SETs / DELETEs accepted and not yet finished on the GPU, counted per digest hash: a
   // reactor-direct GET of such a key goes through the batcher (ordered after them)
@@ -372,12 +401,6 @@ class HbmBackend : public CacheBackend {
   std::unique_ptr<SampleStripe[]> samples_;
   std::mutex hot_mu_;  // one refresh at a time; guards the refresh state below
   std::function<void()> before_fill_;  // debug_before_fill
-  struct DigestHash {
-    size_t operator()(const Digest& d) const { return (size_t)(d.lo ^ (d.hi * 0x9E3779B97F4A7C15ull)); }
-  };
-  struct DigestEq {
-    bool operator()(const Digest& a, const Digest& b) const { return a.lo == b.lo && a.hi == b.hi; }
-  };
   std::unordered_map<Digest, uint64_t, DigestHash, DigestEq> hot_counts_;
   std::vector<Digest> hot_set_;     // the published hot set, hottest first
   std::vector<int32_t> hot_rank_;   // its designated ranks (-1: sprayed)

@@ -28,6 +28,7 @@
 
 #include "backend.h"
 #include "digest.h"
+#include "hbm_flight_plan.h"
 #include "host_cache.h"
 #include "host_router.h"
 #include "http.h"
@@ -417,6 +418,194 @@ void test_proxy_over_memcached_node() {
   node.stop();
 }
 
+// ---------------------------------------------------------------------------------
+// HbmBackend's host-only decisions (hbm_flight_plan.h)
+using Req = HbmBackend::Req;
+
+Req hreq(ReqKind kind, uint64_t digest = 0) {
+  Req r;
+  r.kind = kind;
+  r.d = Digest{digest, digest * 7 + 1};
+  return r;
+}
+
+// the flight rules restated: a flight runs GETs, then SETs / DELETEs, then touches, then one
+// fill or purge
+size_t model_take(const std::vector<Req>& q, int max_batch) {
+  const size_t cap = std::min(q.size(), (size_t)std::max(max_batch, 1));
+  std::map<uint64_t, bool> written;  // digest -> touched
+  for (size_t i = 0; i < cap; ++i) {
+    const ReqKind k = q[i].kind;
+    const auto w = written.find(q[i].d.lo);
+    if (k == ReqKind::Get && w != written.end()) return i;
+    if ((k == ReqKind::Set || k == ReqKind::Del) && w != written.end() && w->second) return i;
+    if (k == ReqKind::Set || k == ReqKind::Del) written.emplace(q[i].d.lo, false);
+    if (k == ReqKind::Touch) written[q[i].d.lo] = true;
+    if (k == ReqKind::Fill || k == ReqKind::Purge) return i + 1;
+  }
+  return cap;
+}
+
+void test_hbm_plan_take() {
+  using K = ReqKind;
+  const uint64_t a = 1, b = 2;
+  struct Case {
+    std::vector<Req> q;
+    int max_batch;
+    size_t take;
+  };
+  const Case cases[] = {
+      {{hreq(K::Set, a), hreq(K::Get, a)}, 64, 1},
+      {{hreq(K::Get, a), hreq(K::Set, a), hreq(K::Get, b)}, 64, 3},
+      {{hreq(K::Set, a), hreq(K::Del, a)}, 64, 2},
+      {{hreq(K::Touch, a), hreq(K::Set, a)}, 64, 1},
+      {{hreq(K::Touch, a), hreq(K::Del, a)}, 64, 1},
+      {{hreq(K::Set, a), hreq(K::Touch, a)}, 64, 2},
+      {{hreq(K::Touch, a), hreq(K::Touch, a)}, 64, 2},
+      {{hreq(K::Touch, a), hreq(K::Get, a)}, 64, 1},
+      {{hreq(K::Touch, a), hreq(K::Set, b)}, 64, 2},
+      {{hreq(K::Set, a), hreq(K::Purge), hreq(K::Set, b)}, 64, 2},
+      {{hreq(K::Fill), hreq(K::Get, a)}, 64, 1},
+      {{hreq(K::Barrier), hreq(K::Set, a), hreq(K::Get, a)}, 64, 2},
+      {{hreq(K::Get, a), hreq(K::Get, b), hreq(K::Get, 3)}, 2, 2},
+      {{hreq(K::Get, a), hreq(K::Get, b), hreq(K::Get, 3)}, 0, 1},
+  };
+  for (const Case& c : cases) CHECK(plan_take(c.q, c.max_batch) == c.take);
+  CHECK(plan_take({}, 64) == 0);
+  std::mt19937 rng(7);
+  TakeScratch scratch;  // reused, as the batcher does
+  for (int trial = 0; trial < 2000; ++trial) {
+    std::vector<Req> q(1 + rng() % 12);
+    for (Req& r : q) r = hreq((ReqKind)(rng() % 7), 1 + rng() % 3);
+    const int max_batch = (int)(rng() % 14);
+    const size_t take = plan_take(q, max_batch, scratch);
+    CHECK(take >= 1);
+    CHECK(take == model_take(q, max_batch));
+  }
+}
+
+void test_hbm_touch_rows() {
+  const auto touch = [](const std::string& key, uint32_t ttl, int flags, uint64_t digest) {
+    Req r = hreq(ReqKind::Touch, digest);
+    r.key = key;
+    r.ttl = ttl;
+    r.has_flags = flags >= 0;
+    r.flags = flags >= 0 ? (uint32_t)flags : 0;
+    return r;
+  };
+  // the plan's rows as (key, carried request) and both launches' offsets checked against kbytes
+  const auto consistent = [](const TouchPlan& p, const std::vector<Req>& reqs,
+                             const std::vector<uint32_t>& touches) {
+    CHECK(p.offs.size() == p.rows() + 2 && p.nkeep <= p.rows());
+    std::string packed;
+    for (size_t row = 0; row < p.rows(); ++row) {
+      const Req& r = reqs[touches[p.src[row]]];
+      const bool keep = row < p.nkeep;
+      CHECK(r.has_flags == !keep);
+      const int64_t* o = keep ? p.offs_keep() + row : p.offs_replace() + (row - p.nkeep);
+      CHECK(o[0] == (int64_t)packed.size() && o[1] == (int64_t)(packed.size() + r.key.size()));
+      packed += r.key;
+    }
+    CHECK(packed == p.kbytes);
+    CHECK(p.offs_replace() == p.offs_keep() + p.nkeep + 1);
+    for (size_t j = 0; j < touches.size(); ++j) {  // every request answers from its pair's row
+      const Req &r = reqs[touches[j]], &c = reqs[touches[p.src[p.trow[j]]]];
+      CHECK(r.key == c.key && r.d.lo == c.d.lo && r.d.hi == c.d.hi);
+    }
+  };
+  {
+    // (a GET between them: the plan goes by `touches`, not by request index)
+    const std::vector<Req> reqs = {touch("k1", 10, -1, 1), hreq(ReqKind::Get, 9),
+                                   touch("k2", 5, 7, 2), touch("k1", 20, 3, 1),
+                                   touch("k3", 1, -1, 3)};
+    const std::vector<uint32_t> touches = {0, 2, 3, 4};
+    const TouchPlan p = plan_touch_rows(reqs, touches);
+    CHECK(p.rows() == 3 && p.nkeep == 1);
+    CHECK((p.src == std::vector<uint32_t>{3, 2, 1}));  // rows [k3, k1 (its last request), k2]
+    CHECK(reqs[touches[p.src[1]]].ttl == 20 && reqs[touches[p.src[1]]].flags == 3);
+    CHECK((p.trow == std::vector<uint32_t>{1, 2, 1, 0}));
+    CHECK(p.kbytes == "k3k1k2");
+    CHECK((p.offs == std::vector<int64_t>{0, 2, 2, 4, 6}));
+    consistent(p, reqs, touches);
+  }
+  {  // the same key text under two digests: two rows
+    const std::vector<Req> reqs = {touch("k", 1, -1, 1), touch("k", 2, -1, 2)};
+    const TouchPlan p = plan_touch_rows(reqs, {0, 1});
+    CHECK(p.rows() == 2 && p.nkeep == 2);
+    CHECK((p.trow == std::vector<uint32_t>{0, 1}));
+    consistent(p, reqs, {0, 1});
+  }
+  {  // all keep: the second launch is empty
+    const std::vector<Req> reqs = {touch("a", 1, -1, 1), touch("bb", 2, -1, 2), touch("a", 3, -1, 1)};
+    const TouchPlan p = plan_touch_rows(reqs, {0, 1, 2});
+    CHECK(p.rows() == 2 && p.nkeep == 2);
+    CHECK(p.offs_keep()[2] == 3);
+    consistent(p, reqs, {0, 1, 2});
+  }
+  {  // all replace: the first launch is empty
+    const std::vector<Req> reqs = {touch("a", 1, 4, 1), touch("bb", 2, 5, 2)};
+    const TouchPlan p = plan_touch_rows(reqs, {0, 1});
+    CHECK(p.rows() == 2 && p.nkeep == 0);
+    CHECK(p.offs_replace() == p.offs.data() + 1);
+    CHECK(p.offs_replace()[0] == 0 && p.offs_replace()[1] == 1 && p.offs_replace()[2] == 3);
+    consistent(p, reqs, {0, 1});
+  }
+}
+
+void test_hbm_write_targets_and_coalescing() {
+  const auto list = [](const WriteTargets& t) { return std::vector<int>(t.begin(), t.end()); };
+  CHECK((list(write_targets(2, false, 0b1111, 4)) == std::vector<int>{2}));
+  CHECK((list(write_targets(1, true, 0b1011, 4)) == std::vector<int>{1, 0, 3}));
+  CHECK((list(write_targets(1, true, 0b0010, 4)) == std::vector<int>{1}));
+  // GETs of digests [a, b, a, c, b] (a SET between them is not a row)
+  const uint64_t a = 11, b = 12, c = 13;
+  const std::vector<Req> reqs = {hreq(ReqKind::Get, a), hreq(ReqKind::Get, b), hreq(ReqKind::Set, c),
+                                 hreq(ReqKind::Get, a), hreq(ReqKind::Get, c), hreq(ReqKind::Get, b)};
+  const std::vector<uint32_t> gets = {0, 1, 3, 4, 5};
+  std::vector<int32_t> tab;
+  std::vector<Digest> rows(gets.size());
+  std::vector<uint32_t> urow(gets.size());
+  CHECK(coalesce_gets(reqs, gets, tab, rows.data(), urow.data()) == 3);
+  CHECK(rows[0].lo == a && rows[1].lo == b && rows[2].lo == c);
+  CHECK((urow == std::vector<uint32_t>{0, 1, 0, 2, 1}));
+  // equal low words, different high words: two rows
+  std::vector<Req> two = {hreq(ReqKind::Get, a), hreq(ReqKind::Get, a)};
+  two[1].d.hi ^= 1;
+  CHECK(coalesce_gets(two, {0, 1}, tab, rows.data(), urow.data()) == 2);
+}
+
+// Three copies answer from three threads: one callback, with the rule's result.
+void test_hbm_fan_in() {
+  for (int round = 0; round < 200; ++round) {
+    std::atomic<int> fired{0}, found{-1}, status{-1};
+    auto del = std::make_shared<FanIn<bool>>(3, false, fan_any, [&](bool f) {
+      found = f;
+      ++fired;
+    });
+    auto touch = std::make_shared<FanIn<int>>(3, 0, fan_owner, [&](int st) {
+      status = st;
+      ++fired;
+    });
+    const bool any = round % 2 == 0;
+    std::vector<std::thread> th;
+    for (int copy = 0; copy < 3; ++copy) {
+      // the second copy finds the object; the first is the owner, whose touch answers `any`
+      auto dcb = FanIn<bool>::arm(del, copy == 0);
+      auto tcb = FanIn<int>::arm(touch, copy == 0);
+      th.emplace_back([=] {
+        dcb(any && copy == 1);
+        tcb(copy == 0 ? (any ? 1 : 0) : (any ? 0 : 1));
+      });
+    }
+    del.reset();
+    touch.reset();
+    for (auto& t : th) t.join();
+    CHECK(fired == 2);
+    CHECK(found == (any ? 1 : 0));
+    CHECK(status == (any ? 1 : 0));
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -434,6 +623,10 @@ int main(int argc, char** argv) {
       {"proxy_threads_dram", [] { test_proxy_threads_dram(nullptr); }},
       {"proxy_threads_fault", [] { test_proxy_threads_dram("get_miss=0.3,set_drop=0.3,delay_us=200"); }},
       {"proxy_memcached_node", test_proxy_over_memcached_node},
+      {"hbm_plan_take", test_hbm_plan_take},
+      {"hbm_touch_rows", test_hbm_touch_rows},
+      {"hbm_targets_coalescing", test_hbm_write_targets_and_coalescing},
+      {"hbm_fan_in", test_hbm_fan_in},
   };
   for (auto& c : cases) {
     if (!only.empty() && only != c.name) continue;
