@@ -13,6 +13,12 @@ URL-shaped keys of 40-80 bytes over 16 path families `/f00/` .. `/f15/`), for N 
 Each: median, min, max of the runs, the bytes the kernel must touch (32 B per index slot,
 one 64-B read per live entry scanned, the further 16-B key granules of matching records)
 and the bandwidth that implies. Prints one JSON line per N.
+
+--soft: the soft purge (k_soften_prefix, soften_keyed_prefix with an expiry cap, so that a
+match costs the entry's CAS and both header stores) is measured first on the same filled
+shard, with the same shapes: it removes nothing, so every family run scans the full shard.
+Its line ("op": "soft", the same fields; purge_match_removed holds the objects softened)
+is printed before the hard purge's ("op": "hard").
 """
 from __future__ import annotations
 
@@ -88,7 +94,7 @@ def summary(ts, nbytes):
             "gb_per_s": round(nbytes / med / 1e3, 1)}
 
 
-def run(n: int, iters: int, dev) -> dict:
+def run(n: int, iters: int, dev, soft: bool = False) -> list:
     nb = 1
     while nb * 2 < n:       # <= 50 % slot load
         nb *= 2
@@ -112,51 +118,64 @@ def run(n: int, iters: int, dev) -> dict:
     def image(prefix: bytes):
         return torch.from_numpy(np.frombuffer(c.keyed_prefix_image(prefix), np.uint8).copy()).to(dev)
 
-    def purge(img, plen):
+    def hard(img, plen):
         shard._impl.remove_keyed_prefix(img.data_ptr(), plen, now, out.data_ptr(), stream)
 
-    live0 = shard.sweep(now)[0]
+    def soften(img, plen):
+        shard._impl.soften_keyed_prefix(img.data_ptr(), plen, False, 0x5EEDF00D, now + 3600, now,
+                                        out.data_ptr(), stream)
+
     nomatch = image(b"/zzz/")
-    for _ in range(3):      # warm-up: code objects, caches
-        shard._impl.sweep(now, stream)
-        purge(nomatch, 5)
-    torch.cuda.synchronize(dev)
-    t_sweep = [timed(lambda: shard._impl.sweep(now, stream), dev)[0] for _ in range(iters)]
-    t_nomatch = [timed(lambda: purge(nomatch, 5), dev)[0] for _ in range(iters)]
-    assert int(out[0]) == 0
-    t_match, removed, live = [], [], live0
-    match_bytes = []
-    for f in range(min(FAMILIES - 4, max(iters, 10))):
-        pre = b"/f%02d/" % f
-        img = image(pre)
-        t_match.append(timed(lambda: purge(img, len(pre)), dev)[0])
-        removed.append(int(out[0]))
-        match_bytes.append(nslots * 32 + live * 64)   # (a 5-byte prefix ends in granule 0)
-        live -= removed[-1]
-    res = {
-        "objects": n, "live": int(live0), "index_slots": nslots, "log_bytes": log_bytes,
-        "sweep": summary(t_sweep, nslots * 32),
-        "purge_nomatch": summary(t_nomatch, nslots * 32 + live0 * 64),
-        "purge_match": summary(t_match, float(np.median(match_bytes))),
-        "purge_match_first_us": round(t_match[0], 1),
-        "purge_match_removed": removed,
-        "purged_counter": shard.counters()["purged"],
-    }
-    res["nomatch_over_sweep"] = round(res["purge_nomatch"]["median_us"] / res["sweep"]["median_us"], 2)
-    res["match_over_sweep"] = round(res["purge_match"]["median_us"] / res["sweep"]["median_us"], 2)
-    return res
+
+    def measure(op: str, purge) -> dict:
+        live0 = shard.sweep(now)[0]
+        for _ in range(3):      # warm-up: code objects, caches
+            shard._impl.sweep(now, stream)
+            purge(nomatch, 5)
+        torch.cuda.synchronize(dev)
+        t_sweep = [timed(lambda: shard._impl.sweep(now, stream), dev)[0] for _ in range(iters)]
+        t_nomatch = [timed(lambda: purge(nomatch, 5), dev)[0] for _ in range(iters)]
+        assert int(out[0]) == 0
+        t_match, removed, live = [], [], live0
+        match_bytes = []
+        for f in range(min(FAMILIES - 4, max(iters, 10))):
+            pre = b"/f%02d/" % f
+            img = image(pre)
+            t_match.append(timed(lambda: purge(img, len(pre)), dev)[0])
+            removed.append(int(out[0]))
+            match_bytes.append(nslots * 32 + live * 64)   # (a 5-byte prefix ends in granule 0)
+            if op == "hard":
+                live -= removed[-1]
+        res = {
+            "op": op,
+            "objects": n, "live": int(live0), "index_slots": nslots, "log_bytes": log_bytes,
+            "sweep": summary(t_sweep, nslots * 32),
+            "purge_nomatch": summary(t_nomatch, nslots * 32 + live0 * 64),
+            "purge_match": summary(t_match, float(np.median(match_bytes))),
+            "purge_match_first_us": round(t_match[0], 1),
+            "purge_match_removed": removed,
+            "purged_counter": shard.counters()["purged"],
+        }
+        res["nomatch_over_sweep"] = round(res["purge_nomatch"]["median_us"] / res["sweep"]["median_us"], 2)
+        res["match_over_sweep"] = round(res["purge_match"]["median_us"] / res["sweep"]["median_us"], 2)
+        return res
+
+    return ([measure("soft", soften)] if soft else []) + [measure("hard", hard)]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=str, default="1048576,8388608")
     ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--soft", action="store_true",
+                    help="also measure the soft purge, on the same shard, before the hard one")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("purge_bench.py needs a GPU")
     dev = torch.device("cuda", 0)
     for n in (int(x) for x in a.objects.split(",")):
-        print(json.dumps(run(n, a.iters, dev)), flush=True)
+        for res in run(n, a.iters, dev, a.soft):
+            print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 
 

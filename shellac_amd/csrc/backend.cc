@@ -98,6 +98,15 @@ void DramBackend::purge_prefix(const std::string& prefix, Executor*, PurgeCallba
   if (done) done(n);
 }
 
+void DramBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                                uint32_t keep_s, Executor*, PurgeCallback done) {
+  const uint32_t n = now();
+  const int64_t c = pattern.empty() ? -1
+                                    : (int64_t)cache_.soften_prefix(pattern, exact, stale_at,
+                                                                    keep_s ? n + keep_s : 0, n);
+  if (done) done(c);
+}
+
 void DramBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
                         const uint32_t* flags, Executor*, TouchCallback done) {
   const uint32_t n = now();
@@ -212,6 +221,20 @@ void TieredBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeC
     // the pass below
     move_purge_epoch();
     l1_->purge_prefix(prefix, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
+    });
+  });
+}
+
+void TieredBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                                  uint32_t keep_s, Executor* ex, PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->soften_prefix(pattern, exact, stale_at, keep_s, ex,
+                     [this, pattern, exact, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
+    // L2's copies are stale now: a GET that hit a fresh one earlier has its promotion
+    // dropped, or landed it in L1 before the pass below, which softens it
+    move_purge_epoch();
+    l1_->soften_prefix(pattern, exact, stale_at, keep_s, ex, [done, n2](int64_t n1) {
       if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });

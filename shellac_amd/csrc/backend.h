@@ -107,6 +107,23 @@ class CacheBackend {
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
   }
+  // Soft purge: end the freshness of every live object whose key starts with `pattern`
+  // (`exact`: equals it) and keep the object: its flags word (the proxy's freshness time)
+  // becomes `stale_at`, and with keep_s != 0 an object that never expires or expires later
+  // than keep_s seconds from now expires then — a life is only shortened; keep_s == 0 leaves
+  // expiries alone. `done` as for purge_prefix: the number of live matching objects (whether
+  // or not their words changed), or -1 where the tier cannot do it (the default) and for an
+  // empty pattern.
+  virtual void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                             uint32_t keep_s, Executor* ex, PurgeCallback done) {
+    (void)pattern;
+    (void)exact;
+    (void)stale_at;
+    (void)keep_s;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
   // Touch: give the live object of exactly `key` the TTL `ttl_s` from now (0 = never expires)
   // and, when `flags` is not null (read before the call returns), new flags, without moving
   // its bytes. A write: ordered with
@@ -172,6 +189,8 @@ class DramBackend : public CacheBackend {
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
+                     Executor* ex, PurgeCallback done) override;
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override;
   void flush() override;
@@ -284,6 +303,11 @@ class HbmBackend : public CacheBackend {
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  // To this tier a soft purge is a purge: the same ReqKind::Purge request carrying the soft
+  // fields, so it is queued to every shard in service behind the writes queued before it, hot
+  // replicas and refresh fills included, and marks shards out of service purge_dirty.
+  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
+                     Executor* ex, PurgeCallback done) override;
   // Routed like del(): to the owner, and for a hot object written through to every shard in
   // service (the answer is the owner's). Queued on the shard's stream behind the writes
   // queued before it; a flight's touches are one key-exact HbmCache::touch launch.
@@ -316,6 +340,9 @@ class HbmBackend : public CacheBackend {
     Bytes value;
     uint32_t flags = 0, ttl = 0;
     bool has_flags = false;  // Touch: `flags` replaces the object's (else they stay)
+    // Purge: a soft one (soften_prefix) keeps the objects; `flags` holds stale_at and `ttl`
+    // keep_s; `exact`: the key must equal the pattern
+    bool soft = false, exact = false;
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
@@ -324,7 +351,7 @@ class HbmBackend : public CacheBackend {
     // finished on the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
     std::shared_ptr<HotFill> fill;
-    std::shared_ptr<Purge> purge;  // Purge (`key` holds the prefix)
+    std::shared_ptr<Purge> purge;  // Purge (`key` holds the pattern)
   };
   struct Dev;
   struct Direct;
@@ -387,7 +414,11 @@ class HbmBackend : public CacheBackend {
   // purge_prefix calls begun / answered: a warm restore that overlapped one may have copied
   // objects a peer had not purged yet, and flushes the restored shard again
   std::atomic<uint64_t> purge_started_{0}, purge_done_{0};
+  std::atomic<uint64_t> soft_purges_{0};
   void purge_finish(const std::shared_ptr<Purge>& p);
+  // purge_prefix and soften_prefix: `proto` (kind Purge, the pattern and the soft fields) goes
+  // to every shard in service
+  void purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done);
   // ---- hot-object spreading (hot_refresh_locked documents the protocol)
   std::unique_ptr<HostRouter> router_;  // ketama owners + the published hot table
   bool hot_on_ = false;
@@ -438,6 +469,11 @@ class TieredBackend : public CacheBackend {
   // the purge does not promote its object into L1 after L1 was purged (purge_epoch_; del()
   // does the same for one key).
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
+  // L2 first, then L1, with the purge epoch moved in between, exactly as purge_prefix: a
+  // promotion read before the soft purge would put a fresh copy into L1. The sum, or -1 if
+  // either level cannot.
+  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
+                     Executor* ex, PurgeCallback done) override;
   // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
   // writes both levels). A promotion that straddles the touch is dropped, as for del(): it
   // would carry the pre-touch TTL and flags into L1.
@@ -500,6 +536,10 @@ class FaultBackend : public CacheBackend {
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override {
     inner_->purge_prefix(prefix, ex, std::move(done));
+  }
+  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
+                     Executor* ex, PurgeCallback done) override {
+    inner_->soften_prefix(pattern, exact, stale_at, keep_s, ex, std::move(done));
   }
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override {

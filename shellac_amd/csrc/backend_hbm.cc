@@ -372,7 +372,32 @@ void HbmBackend::purge_finish(const std::shared_ptr<Purge>& p) {
 // stream behind the writes queued before it. A shard that is out of service, or fails the
 // purge, is marked so that its restore flushes it.
 void HbmBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
-  if (prefix.empty() || prefix.size() > kMaxKeyedKey) {
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  proto.key = prefix;
+  purge_fan_out(proto, ex, std::move(done));
+}
+
+// A soft purge is a purge to this tier: the same request, fan-out, ordering, hot-replica and
+// restore handling; only the launch differs (Dev::launch_purges).
+void HbmBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                               uint32_t keep_s, Executor* ex, PurgeCallback done) {
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  proto.key = pattern;
+  proto.soft = true;
+  proto.exact = exact;
+  proto.flags = stale_at;
+  proto.ttl = keep_s;
+  if (!pattern.empty() && pattern.size() <= kMaxKeyedKey)
+    soft_purges_.fetch_add(1, std::memory_order_relaxed);
+  purge_fan_out(proto, ex, std::move(done));
+}
+
+void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done) {
+  if (proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
     if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
     return;
   }
@@ -394,10 +419,7 @@ void HbmBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCall
         continue;
       }
     }
-    Req r;
-    r.kind = ReqKind::Purge;
-    r.d = Digest{0, 0};
-    r.key = prefix;
+    Req r = proto;
     r.purge = p;
     r.ccb = [this, p, dv](bool ok) {
       if (!ok) dv->purge_dirty.store(true, std::memory_order_release);
@@ -518,6 +540,8 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_purges", purge_started_.load());
   out->emplace_back("hbm_purged_objects", sum(&Dev::purged_objects));
   out->emplace_back("hbm_purged_bytes", sum(&Dev::purged_bytes));
+  out->emplace_back("hbm_soft_purges", soft_purges_.load());
+  out->emplace_back("hbm_softened_objects", sum(&Dev::softened_objects));
   // touch requests taken, and the entries the shards' kernels updated (replicas included)
   out->emplace_back("hbm_touches", sum(&Dev::touch_reqs));
   out->emplace_back("hbm_touched", t.touched);

@@ -232,6 +232,15 @@ PYBIND11_MODULE(_shellac_core, m) {
         py::gil_scoped_release nogil;
         c.remove_keyed_prefix(P<const uint8_t>(image), plen, now, P<uint64_t>(out), S(s));
       }, py::arg("image"), py::arg("plen"), py::arg("now"), py::arg("out"), py::arg("stream"))
+      // image as above; out: 1 word; asynchronous on the stream
+      .def("soften_keyed_prefix", [](HbmCache& c, uintptr_t image, uint32_t plen, bool exact,
+                                     uint32_t stale_at, uint32_t expire_cap, uint32_t now,
+                                     uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.soften_keyed_prefix(P<const uint8_t>(image), plen, exact, stale_at, expire_cap, now,
+                              P<uint64_t>(out), S(s));
+      }, py::arg("image"), py::arg("plen"), py::arg("exact"), py::arg("stale_at"),
+         py::arg("expire_cap"), py::arg("now"), py::arg("out"), py::arg("stream"))
       // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
       .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
@@ -449,6 +458,13 @@ PYBIND11_MODULE(_shellac_core, m) {
                               out);
         return py::make_tuple(out[0], out[1]);
       }, py::arg("prefix"), py::arg("now"))
+      .def("soften_keyed_prefix", [](HostCache& c, py::bytes prefix, bool exact, uint32_t stale_at,
+                                     uint32_t expire_cap, uint32_t now) {
+        const std::string p = prefix;
+        return c.soften_keyed_prefix(reinterpret_cast<const uint8_t*>(p.data()),
+                                     (uint32_t)p.size(), exact, stale_at, expire_cap, now);
+      }, py::arg("prefix"), py::arg("exact"), py::arg("stale_at"), py::arg("expire_cap"),
+         py::arg("now"))
       .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
                        uint32_t now) {

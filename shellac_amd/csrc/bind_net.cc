@@ -96,13 +96,14 @@ std::shared_ptr<TouchWait> start_touch(CacheBackend* be, const std::string& key,
   return w;
 }
 
-int64_t blocking_purge(CacheBackend* be, const std::string& prefix) {
+// `call(cb)`: one purge_prefix / soften_prefix call answering through cb
+int64_t blocking_purge(const std::function<void(PurgeCallback)>& call) {
   std::mutex mu;
   std::condition_variable cv;
   bool done = false;
   int64_t removed = -1;
   py::gil_scoped_release nogil;
-  be->purge_prefix(prefix, &g_inline, [&](int64_t n) {
+  call([&](int64_t n) {
     std::lock_guard<std::mutex> lk(mu);
     removed = n;
     done = true;
@@ -111,6 +112,45 @@ int64_t blocking_purge(CacheBackend* be, const std::string& prefix) {
   std::unique_lock<std::mutex> lk(mu);
   cv.wait(lk, [&] { return done; });
   return removed;
+}
+
+// Tests: one hot-set refresh with `call(hb, cb)` (a purge or a soft purge) queued in its
+// middle, after the owners' records were snapshot and before the replica fills are queued;
+// returns (the refresh's counts, the call's answer).
+py::tuple hot_refresh_with(BackendHandle& h,
+                           std::function<void(HbmBackend*, PurgeCallback)> call) {
+  auto* hb = dynamic_cast<HbmBackend*>(h.be.get());
+  if (!hb) throw Error("not an HBM backend");
+  struct State {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool queued = false, done = false;
+    int64_t removed = -1;
+  };
+  auto st = std::make_shared<State>();
+  StatList out;
+  {
+    py::gil_scoped_release nogil;
+    hb->debug_before_fill([hb, call, st] {
+      {
+        std::lock_guard<std::mutex> lk(st->mu);
+        st->queued = true;
+      }
+      call(hb, [st](int64_t n) {
+        std::lock_guard<std::mutex> lk(st->mu);
+        st->removed = n;
+        st->done = true;
+        st->cv.notify_all();
+      });
+    });
+    out = hb->hot_refresh();
+    hb->debug_before_fill(nullptr);
+    std::unique_lock<std::mutex> lk(st->mu);
+    if (st->queued) st->cv.wait(lk, [&] { return st->done; });
+  }
+  py::dict d;
+  for (auto& kv : out) d[py::str(kv.first)] = kv.second;
+  return py::make_tuple(d, st->queued ? py::object(py::int_(st->removed)) : py::object(py::none()));
 }
 
 }  // namespace
@@ -207,16 +247,32 @@ void bind_net(py::module_& m) {
         return blocking_get(h.be.get(), key, &d);
       })
       .def("set", [](BackendHandle& h, py::bytes key, py::bytes value, uint32_t flags,
-                     uint32_t ttl) {
+                     uint32_t ttl, py::object digest_of) {
+        // `digest_of`: store `key` under another key's digest (a forged collision)
         std::string k = key;
-        const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(k.data()), k.size());
+        const std::string o = digest_of.is_none() ? k : digest_of.cast<std::string>();
+        const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(o.data()), o.size());
         h.be->set(k, d, std::make_shared<const std::string>(std::string(value)), flags, ttl);
-      }, py::arg("key"), py::arg("value"), py::arg("flags") = 0, py::arg("ttl") = 0)
+      }, py::arg("key"), py::arg("value"), py::arg("flags") = 0, py::arg("ttl") = 0,
+         py::arg("digest_of") = py::none())
       .def("delete", [](BackendHandle& h, py::bytes key) { return blocking_del(h.be.get(), key); })
       // objects whose key starts with `prefix` removed (blocking); -1: the tier cannot scan
       .def("purge_prefix", [](BackendHandle& h, py::bytes prefix) {
-        return blocking_purge(h.be.get(), prefix);
+        const std::string pre = prefix;
+        CacheBackend* be = h.be.get();
+        return blocking_purge(
+            [&](PurgeCallback cb) { be->purge_prefix(pre, &g_inline, std::move(cb)); });
       }, py::arg("prefix"))
+      // soft purge (blocking): live matching objects made stale at `stale_at` and, with keep_s,
+      // expiring at most keep_s seconds from now; -1: the tier cannot
+      .def("soften_prefix", [](BackendHandle& h, py::bytes pattern, uint32_t stale_at,
+                               uint32_t keep_s, bool exact) {
+        const std::string pat = pattern;
+        CacheBackend* be = h.be.get();
+        return blocking_purge([&](PurgeCallback cb) {
+          be->soften_prefix(pat, exact, stale_at, keep_s, &g_inline, std::move(cb));
+        });
+      }, py::arg("pattern"), py::arg("stale_at"), py::arg("keep_s") = 0, py::arg("exact") = false)
       // in-place touch (blocking): 1 touched, 0 not found, -1 the tier cannot. `flags` None
       // keeps the object's flags; `digest_of`: look the key up under another key's digest (a
       // forged collision)
@@ -393,44 +449,21 @@ void bind_net(py::module_& m) {
     for (auto& kv : st) d[py::str(kv.first)] = kv.second;
     return d;
   }, py::arg("backend"));
-  // Tests: one hot-set refresh with a prefix purge queued in its middle, after the owners'
-  // records were snapshot and before the replica fills are queued; returns (the refresh's
-  // counts, objects the purge removed).
+  // Tests: hot_refresh_with a prefix purge / a soft prefix purge; returns (the refresh's
+  // counts, objects the purge removed / softened).
   m.def("hot_refresh_purging", [](BackendHandle& h, py::bytes prefix) {
-    auto* hb = dynamic_cast<HbmBackend*>(h.be.get());
-    if (!hb) throw Error("not an HBM backend");
     const std::string pre = prefix;
-    struct State {
-      std::mutex mu;
-      std::condition_variable cv;
-      bool queued = false, done = false;
-      int64_t removed = -1;
-    };
-    auto st = std::make_shared<State>();
-    StatList out;
-    {
-      py::gil_scoped_release nogil;
-      hb->debug_before_fill([hb, pre, st] {
-        {
-          std::lock_guard<std::mutex> lk(st->mu);
-          st->queued = true;
-        }
-        hb->purge_prefix(pre, nullptr, [st](int64_t n) {
-          std::lock_guard<std::mutex> lk(st->mu);
-          st->removed = n;
-          st->done = true;
-          st->cv.notify_all();
-        });
-      });
-      out = hb->hot_refresh();
-      hb->debug_before_fill(nullptr);
-      std::unique_lock<std::mutex> lk(st->mu);
-      if (st->queued) st->cv.wait(lk, [&] { return st->done; });
-    }
-    py::dict d;
-    for (auto& kv : out) d[py::str(kv.first)] = kv.second;
-    return py::make_tuple(d, st->queued ? py::object(py::int_(st->removed)) : py::object(py::none()));
+    return hot_refresh_with(h, [pre](HbmBackend* hb, PurgeCallback cb) {
+      hb->purge_prefix(pre, nullptr, std::move(cb));
+    });
   }, py::arg("backend"), py::arg("prefix"));
+  m.def("hot_refresh_softening", [](BackendHandle& h, py::bytes prefix, uint32_t stale_at,
+                                    uint32_t keep_s) {
+    const std::string pre = prefix;
+    return hot_refresh_with(h, [pre, stale_at, keep_s](HbmBackend* hb, PurgeCallback cb) {
+      hb->soften_prefix(pre, false, stale_at, keep_s, nullptr, std::move(cb));
+    });
+  }, py::arg("backend"), py::arg("prefix"), py::arg("stale_at"), py::arg("keep_s") = 0);
   m.def("inject_shard_down", [](BackendHandle& h, int shard, bool down) {
     return h.be->inject_shard_down(shard, down);
   }, py::arg("backend"), py::arg("shard"), py::arg("down") = true);

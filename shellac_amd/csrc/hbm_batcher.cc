@@ -403,8 +403,13 @@ void HbmBackend::Dev::launch_purges(Flight& f) {
                              reinterpret_cast<const uint8_t*>(r.key.data()), r.key.size());
     uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * j;
     res[0] = res[1] = 0;
-    cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
-                               f.tnow, f.purge_out.dev<uint64_t>() + 2 * j, stream);
+    if (r.soft)  // (flags: stale_at, ttl: keep_s; the flight's SET chains are whole ones)
+      cache->soften_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
+                                 r.exact, r.flags, r.ttl ? f.tnow + r.ttl : 0, f.tnow,
+                                 f.purge_out.dev<uint64_t>() + 2 * j, stream);
+    else
+      cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
+                                 f.tnow, f.purge_out.dev<uint64_t>() + 2 * j, stream);
     off += keyed_prefix_image_bytes(r.key.size());
     ++j;
   }
@@ -479,8 +484,12 @@ void HbmBackend::Dev::finish_ctls(Flight& f) {
     Req& r = f.reqs[i];
     if (r.kind == ReqKind::Purge) {
       const uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * pj++;
-      purged_objects += res[0];
-      purged_bytes += res[1];
+      if (r.soft) {
+        softened_objects += res[0];
+      } else {
+        purged_objects += res[0];
+        purged_bytes += res[1];
+      }
       if (r.purge) r.purge->removed.fetch_add((int64_t)res[0], std::memory_order_relaxed);
     }
     if (r.ccb) r.ccb(true);

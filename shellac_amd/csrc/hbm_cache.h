@@ -260,6 +260,18 @@ class HbmCache {
   // whatever happens to parse as a matching keyed record.
   void remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t now, uint64_t* out,
                            hipStream_t s);
+  // Soft purge of keyed values: every live entry whose stored key starts with the pattern
+  // (`exact`: equals it) gets flags = stale_at and, where expire_cap != 0 and the entry never
+  // expires or expires after it, expire = expire_cap (a life is only shortened) — in place,
+  // in the index entry and the record's ItemHeader; the value, loc, vlen and the CLOCK
+  // reference bit stay, and so do the ring and the head. `image`, `plen`, the streams and the
+  // memory kinds are remove_keyed_prefix's; expire_cap is 0 or > now. `out` (1 word) receives
+  // the number of live matching entries, whether or not their words changed. Uses scratch
+  // words of its own (one soft purge at a time per shard). Exact when ordered against whole
+  // SET chains; refused while a phase-1 batch waits for its phase 2, as touch(). See
+  // k_soften_prefix for what holds beside a SET chain on another stream.
+  void soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exact, uint32_t stale_at,
+                           uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
   // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
   // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
   // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte

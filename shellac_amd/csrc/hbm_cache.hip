@@ -39,6 +39,10 @@
 //                  replaced in place by a CAS that keeps the CLOCK bit, and the record
 //                  header's expiry / flags with it; with key bytes only a record whose
 //                  stored key is exactly the row's (16-B granules, one per lane).
+//   k_soften_prefix k_purge_prefix's scan and matcher (by prefix or exact key), k_touch's
+//                  action: a matching live entry is kept, its record's flags become the
+//                  given freshness time and its expiry is capped (never extended), by a CAS
+//                  that keeps the CLOCK bit and stores into the record header.
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -3302,6 +3306,129 @@ __global__ __launch_bounds__(kBlock) void k_touch(
   block_count(ctr, touched, &CacheCounters::touched);
 }
 
+// Soft purge: end the freshness of every live entry whose stored keyed value has a key that
+// starts with (exact: equals) the pattern, and keep the object. k_purge_prefix's traversal
+// and matcher (one lane per index slot, the pattern image staged in LDS, the first granule
+// rejecting; `exact` costs one more compare on klen, the image is the same), k_touch's
+// action by the lane that owns the slot: the record's flags become `stale_at`, and where
+// `expire_cap` != 0 and the entry never expires or expires after it, the expiry becomes
+// expire_cap — in the entry by a CAS of the {vlen | expire} word that keeps kRefBit, then in
+// the record's ItemHeader (the CLOCK hand rebuilds a re-appended entry from the header, so
+// both places must agree). A life is only ever shortened. No value byte, loc or vlen
+// changes; the item-start ring and the log head are untouched. out[0] counts the live
+// matching entries, whether or not their words changed.
+//
+// What it relies on. Exactness (every matching object stored before the call and live is
+// softened, nothing else) comes from stream order against whole SET chains (StoreOpts::phase
+// == 0): the backend queues it between them. Beside a SET chain on another stream it stays
+// memory-safe and never changes the entry or the record of a non-matching object: it writes
+// into the log, so liveness is judged at the furthest byte the queued appends have claimed
+// (k_touch's max(head, claim): a record about to be overwritten is neither written nor
+// counted), the record must carry the entry's digest, vlen and the magic word, every access
+// stays inside [record, record + item_bytes(vlen)) with vlen <= max_item, and the expiry goes
+// in by a CAS of the very word that was read with the digest and the loc (only kRefBit may
+// differ and is kept). The word does not hold the digest, so the slot is read again after the
+// CAS: if it passed to another entry with an equal word in between, the same CAS puts the
+// old expiry back and the slot is neither written further nor counted. A detached CLOCK hand
+// rewrites the word from the value it staged: HbmCache::soften_keyed_prefix refuses while
+// one is pending.
+__global__ __launch_bounds__(kBlock) void k_soften_prefix(
+    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
+    uint32_t max_item, uint32_t now, const uint4* __restrict__ img, uint32_t plen, uint32_t ngran,
+    uint32_t exact, uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
+  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
+  const uint4* const s_pat = s_img + 2;
+  const uint4* const pat = img + 2;
+  for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
+    s_img[g] = img[g];
+  __syncthreads();
+  const uint4 m0 = s_img[0], mlast = s_img[1], p0 = s_pat[0];
+  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+  // the head the queued appends reach (equal to the head slot once they have run)
+  const uint64_t hs = *head_ptr, hc = *claim_ptr;
+  const uint64_t head = hc > hs ? hc : hs;
+  unsigned long long softened = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < kKeyedPrefix + plen || vlen > max_item || ((loc - 1) & 15)) continue;
+    uint8_t* const recb = log + (loc - 1) % cap;
+    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    const uint4 v0 = rec[2];
+    const uint32_t klen = v0.x & 0xffffu;
+    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
+    if (exact && klen != plen) continue;
+    if (!purge_granule_eq(v0, m0, p0)) continue;
+    bool eq = true;
+    for (uint32_t g = 1; g < ngran; ++g) {
+      const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_pat[g] : pat[g];
+      const uint4 v = rec[2 + g];
+      if (!purge_granule_eq(v, g + 1 == ngran ? mlast : ones, p)) {
+        eq = false;
+        break;
+      }
+    }
+    if (!eq) continue;
+    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
+    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
+      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
+      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
+      bool done = false;
+      for (int t = 0; t < kTouchCasTries; ++t) {
+        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
+        const unsigned long long prev = atomicCAS(w, expect, want);
+        if (prev == expect) {
+          done = true;
+          break;
+        }
+        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
+        expect = prev;
+      }
+      if (!done) continue;
+      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
+      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
+        // the slot passed to another entry with an equal word: put its expiry back
+        unsigned long long cur = want;
+        for (int t = 0; t < 2; ++t) {
+          const unsigned long long prev =
+              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
+          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
+          cur = prev;
+        }
+        continue;
+      }
+      h->expire = expire_cap;
+    }
+    h->flags = stale_at;
+    ++softened;
+  }
+  // the result word: one add per workgroup, after its whole grid-stride loop (k_purge_prefix)
+  __shared__ unsigned long long s_res[kBlock / 64];
+  softened = wave_sum(softened);
+  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
+    if (t0) atomicAdd(&out[0], t0);
+  }
+}
+
 // Export the digests of all live entries (rebalancing / warm restore). One atomic
 // per workgroup per pass reserves the output range; lanes write in block order.
 __global__ __launch_bounds__(kBlock) void k_export(const Entry* __restrict__ index, uint64_t nslots,
@@ -4505,6 +4632,29 @@ void HbmCache::remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t
                      (uint32_t)keyed_prefix_granules(plen), acc, ctr_);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exact,
+                                   uint32_t stale_at, uint32_t expire_cap, uint32_t now,
+                                   uint64_t* out, hipStream_t s) {
+  TraceRange tr("hbm.soften_prefix");
+  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+  SH_CHECK(image && out, "purge needs a pattern image and a result buffer");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
+  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 6;  // (0..1: sweep, export; 4..5: purge)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_soften_prefix, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
+                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
+                     cfg_.max_item, now, reinterpret_cast<const uint4*>(image), plen,
+                     (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u, stale_at, expire_cap,
+                     acc);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
 }
 
 uint64_t HbmCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now, hipStream_t s) {

@@ -408,6 +408,39 @@ void HostCache::remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32
   }
 }
 
+uint64_t HostCache::soften_keyed_prefix(const uint8_t* prefix, uint32_t plen, bool exact,
+                                        uint32_t stale_at, uint32_t expire_cap, uint32_t now) {
+  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t softened = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    Entry& e = index_[k];
+    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
+    const uint32_t vlen = entry_vlen(e.vlen);
+    if (vlen < kKeyedPrefix + plen || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
+    uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
+    const uint8_t* const v = rec + kItemHeaderBytes;
+    uint16_t klen;
+    std::memcpy(&klen, v, kKeyedPrefix);
+    if ((exact ? klen != plen : klen < plen) || kKeyedPrefix + klen > vlen) continue;
+    if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
+    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
+    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
+      e.expire = expire_cap;
+      h.expire = expire_cap;
+    }
+    h.flags = stale_at;
+    std::memcpy(rec, &h, sizeof(h));
+    ++softened;
+  }
+  return softened;
+}
+
 void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
                       const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
                       uint32_t now) {

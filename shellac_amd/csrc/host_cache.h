@@ -36,6 +36,13 @@ class HostCache {
   // whose stored key starts with prefix[0..plen), 1 <= plen <= 65535;
   // out = {entries removed, their item bytes}, also counted as `purged`.
   void remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now, uint64_t out[2]);
+  // Soft purge of keyed values (HbmCache::soften_keyed_prefix, whose semantic reference this
+  // is): every live entry whose record is its own and whose stored key starts with (exact:
+  // equals) prefix[0..plen) gets flags = stale_at and, where expire_cap != 0 and the entry
+  // never expires or expires after it, expire = expire_cap — in the index and the record
+  // header; nothing else changes. expire_cap is 0 or > now. Returns the live matches.
+  uint64_t soften_keyed_prefix(const uint8_t* prefix, uint32_t plen, bool exact, uint32_t stale_at,
+                               uint32_t expire_cap, uint32_t now);
   // In-place change of expiry (and flags, nullable) of each row's live entry, in the index
   // and in the record header (HbmCache::touch, whose semantic reference this is). With key
   // bytes (nullable with their offsets) a row only matches a keyed record of exactly that key.

@@ -241,6 +241,30 @@ uint64_t ObjectCache::purge_prefix(const std::string& prefix, uint32_t now) {
   return removed;
 }
 
+uint64_t ObjectCache::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                                    uint32_t expire_cap, uint32_t now) {
+  uint64_t softened = 0;
+  for (auto& sp : stripes_) {
+    Stripe& s = *sp;
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (size_t id = 0; id < s.slots.size(); ++id) {
+      Obj& o = s.slots[id];
+      if (!o.data || (o.expire && o.expire <= now)) continue;
+      const std::string& v = *o.data;
+      if (v.size() < kKeyedPrefix + pattern.size()) continue;
+      uint16_t kl;
+      std::memcpy(&kl, v.data(), kKeyedPrefix);
+      if ((exact ? kl != pattern.size() : kl < pattern.size()) || v.size() < kKeyedPrefix + kl)
+        continue;
+      if (std::memcmp(v.data() + kKeyedPrefix, pattern.data(), pattern.size()) != 0) continue;
+      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
+      o.flags = stale_at;
+      ++softened;
+    }
+  }
+  return softened;
+}
+
 void ObjectCache::clear() {
   for (auto& sp : stripes_) {
     Stripe& s = *sp;

@@ -50,6 +50,12 @@ class ObjectCache {
   // Drops every live object whose stored key starts with `prefix` (a walk of every stripe
   // under its lock); returns how many.
   uint64_t purge_prefix(const std::string& prefix, uint32_t now);
+  // Soft purge, in place under each stripe's lock (as touch): every live object whose stored
+  // key starts with `pattern` (`exact`: equals it) gets flags = stale_at and, where
+  // expire_cap != 0 and the object never expires or expires after it, expire = expire_cap.
+  // Returns the live matching objects, whether or not their words changed.
+  uint64_t soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
+                         uint32_t expire_cap, uint32_t now);
   void clear();
   ObjectCacheStats stats() const;
 

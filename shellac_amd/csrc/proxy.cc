@@ -301,7 +301,8 @@ class Reactor : public Executor {
       cache_sets{0}, bad_requests{0}, upstream_failures{0}, retries{0}, collapsed{0},
       streamed{0}, stream_pauses{0}, gzip_gpu_bodies{0}, gzip_gpu_inflated{0}, identity_decoded{0},
       vary_stored{0},
-      vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0};
+      vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0},
+      soft_purge_requests{0}, softened_objects{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -323,7 +324,9 @@ class Reactor : public Executor {
   void on_client(Client* c, uint32_t ev);
   void on_upstream(Upstream* u, uint32_t ev);
   void on_request(Client* c);
-  void on_purge(Client* c, Slot* s, const std::string& key, bool prefix);
+  void on_purge(Client* c, Slot* s, const std::string& key, bool prefix, bool soft);
+  void hard_purge(uint64_t cid, uint64_t seq, const std::string& key, bool prefix,
+                  bool soft_asked);
   void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                     const std::string& body);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
@@ -682,8 +685,9 @@ void Reactor::on_request(Client* c) {
     const std::string key = cfg_.key_host && host ? *host + url : url;  // as a GET's
     const std::string* mode = q.header("x-purge-mode");
     const bool prefix = mode && to_lower(*mode) == "prefix";
+    const std::string* soft = q.header("x-purge-soft");
     c->slots.push_back(std::move(s));
-    on_purge(c, sp, key, prefix);
+    on_purge(c, sp, key, prefix, soft && *soft == "1");
     return;
   }
   s->head = method == "HEAD";
@@ -714,7 +718,16 @@ void Reactor::on_request(Client* c) {
 //           deleting only the marker would make them reachable again once a new marker is
 //           stored;
 //   prefix: every object whose key starts with the URL's key.
-void Reactor::on_purge(Client* c, Slot* s, const std::string& key, bool prefix) {
+// X-Purge-Soft: 1 (with --grace): the same objects are kept and made stale now
+// (CacheBackend::soften_prefix: freshness time = now, life capped at now + grace), so the next
+// request is answered from the stale copy and revalidated in the background. note_purge is
+// called all the same: a fill or a revalidation that left before the soft purge must not make
+// the object fresh again (purged_since drops it; the object stays stale and the next hit
+// revalidates). Exact mode is two scans, the key itself and its variants; a Vary marker at
+// the base key is softened like any object (a marker's freshness is never tested). Without
+// --grace, or where the tier answers -1, the request is carried out as a hard purge and
+// answered with "soft":false.
+void Reactor::on_purge(Client* c, Slot* s, const std::string& key, bool prefix, bool soft) {
   const uint64_t cid = c->id, seq = s->seq;
   if (!purge_allowed(cfg_.purge, c->loopback)) {
     purge_denied++;
@@ -728,25 +741,65 @@ void Reactor::on_purge(Client* c, Slot* s, const std::string& key, bool prefix) 
     return;
   }
   px_->note_purge(key, prefix);  // before the tier is touched: fills in flight are refused
+  if (!soft || !cfg_.grace) {  // (without --grace staleness has no meaning)
+    hard_purge(cid, seq, key, prefix, soft);
+    return;
+  }
+  const uint32_t stale_at = unix_now(), keep = cfg_.grace;
   if (prefix) {
-    be->purge_prefix(key, this, [this, cid, seq](int64_t n) {
+    be->soften_prefix(key, false, stale_at, keep, this, [this, cid, seq, key](int64_t n) {
+      if (n < 0) {
+        hard_purge(cid, seq, key, true, true);
+        return;
+      }
+      soft_purge_requests++;
+      softened_objects += (uint64_t)n;
+      answer_purge(cid, seq, 200, "OK",
+                   "{\"mode\":\"prefix\",\"soft\":true,\"softened\":" + std::to_string(n) + "}");
+    });
+    return;
+  }
+  be->soften_prefix(key, true, stale_at, keep, this,
+                    [this, be, key, cid, seq, stale_at, keep](int64_t n) {
+    if (n < 0) {
+      hard_purge(cid, seq, key, false, true);
+      return;
+    }
+    be->soften_prefix(key + '\x1f', false, stale_at, keep, this, [this, cid, seq, n](int64_t m) {
+      soft_purge_requests++;
+      softened_objects += (uint64_t)n + (uint64_t)(m > 0 ? m : 0);
+      answer_purge(cid, seq, 200, "OK",
+                   "{\"mode\":\"exact\",\"soft\":true,\"softened\":" + std::to_string(n) +
+                       ",\"variants\":" + std::to_string(m < 0 ? -1 : m) + "}");
+    });
+  });
+}
+
+// The hard purge; `soft_asked`: the request asked for a soft one that cannot be had, which the
+// answer says ("soft":false). Without it the answers are what they always were.
+void Reactor::hard_purge(uint64_t cid, uint64_t seq, const std::string& key, bool prefix,
+                         bool soft_asked) {
+  CacheBackend* be = px_->backend_.get();
+  const std::string mode = std::string("{\"mode\":\"") + (prefix ? "prefix" : "exact") + "\"," +
+                           (soft_asked ? "\"soft\":false," : "");
+  if (prefix) {
+    be->purge_prefix(key, this, [this, cid, seq, mode](int64_t n) {
       if (n < 0) {
         answer_purge(cid, seq, 501, "Not Implemented",
-                     "{\"mode\":\"prefix\",\"error\":\"the cache tier cannot scan its keys\"}");
+                     mode + "\"error\":\"the cache tier cannot scan its keys\"}");
         return;
       }
       purged_objects += (uint64_t)n;
-      answer_purge(cid, seq, 200, "OK",
-                   "{\"mode\":\"prefix\",\"purged\":" + std::to_string(n) + "}");
+      answer_purge(cid, seq, 200, "OK", mode + "\"purged\":" + std::to_string(n) + "}");
     });
     return;
   }
   const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(key.data()), key.size());
-  be->del(key, d, this, [this, be, key, cid, seq](bool found) {
-    be->purge_prefix(key + '\x1f', this, [this, cid, seq, found](int64_t n) {
+  be->del(key, d, this, [this, be, key, cid, seq, mode](bool found) {
+    be->purge_prefix(key + '\x1f', this, [this, cid, seq, found, mode](int64_t n) {
       purged_objects += (found ? 1 : 0) + (uint64_t)(n > 0 ? n : 0);
       answer_purge(cid, seq, 200, "OK",
-                   std::string("{\"mode\":\"exact\",\"found\":") + (found ? "true" : "false") +
+                   mode + "\"found\":" + (found ? "true" : "false") +
                        ",\"variants\":" + std::to_string(n < 0 ? -1 : n) + "}");
     });
   });
@@ -1893,7 +1946,8 @@ bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string
 std::string Proxy::stats_json() {
   uint64_t req = 0, hit = 0, miss = 0, ur = 0, resp = 0, bo = 0, err = 0, cl = 0, up = 0, acc = 0,
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
-           lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0;
+           lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
+           sob = 0;
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -1911,6 +1965,7 @@ std::string Proxy::stats_json() {
     vh += r->vary_hits;
     prq += r->purge_requests; pob += r->purged_objects; pdn += r->purge_denied;
     fpg += r->fills_purged;
+    spr += r->soft_purge_requests; sob += r->softened_objects;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -1941,6 +1996,7 @@ std::string Proxy::stats_json() {
     << ",\"vary_stored\":" << vst << ",\"vary_hits\":" << vh
     << ",\"purge_requests\":" << prq << ",\"purged_objects\":" << pob
     << ",\"purge_denied\":" << pdn << ",\"fills_not_cached_purged\":" << fpg
+    << ",\"soft_purge_requests\":" << spr << ",\"softened_objects\":" << sob
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
     << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]

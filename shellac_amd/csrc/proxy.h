@@ -63,7 +63,10 @@ struct ProxyConfig {
   // The PURGE method (cache invalidation): "off" (a PURGE request is handled like any other
   // method: forwarded upstream), "loopback" (clients on 127/8 only, others get 403), "any".
   // `PURGE <url>` removes the URL's object and all its Vary variants; with the header
-  // `X-Purge-Mode: prefix` every object whose key starts with the URL's key.
+  // `X-Purge-Mode: prefix` every object whose key starts with the URL's key. With the header
+  // `X-Purge-Soft: 1` and grace != 0 the same objects are kept and made stale now instead
+  // (CacheBackend::soften_prefix; their lives capped at now + grace, never extended);
+  // without grace, or where the tier cannot, it is a hard purge answered with "soft":false.
   std::string purge = "off";
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.

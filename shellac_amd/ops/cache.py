@@ -687,6 +687,32 @@ class CacheShard:
         removed, nbytes = out.tolist()  # (waits for the stream)
         return int(removed), int(nbytes)
 
+    def soften_keyed_prefix(self, prefix: bytes, stale_at: int, expire_cap: int = 0,
+                            exact: bool = False, now: Optional[int] = None) -> int:
+        """Soft purge: every live object whose stored key starts with ``prefix`` (``exact``:
+        equals it) gets ``flags = stale_at`` and, where ``expire_cap`` is non-zero and the
+        object never expires or expires after it, ``expire = expire_cap`` (absolute, in the
+        shard's clock, and after ``now``): a life is only shortened. The value, its place and
+        the CLOCK reference bit stay. Returns the number of live matching objects, whether
+        or not their words changed. Synchronises, like ``remove_keyed_prefix``; on a GPU
+        shard ``k_soften_prefix`` does the scan. Defined for keyed values only."""
+        prefix = bytes(prefix)
+        if not 1 <= len(prefix) <= 0xFFFF:
+            raise ValueError("purge prefix must hold 1..65535 bytes")
+        now = self.now() if now is None else now
+        stale_at, expire_cap = int(stale_at) & 0xFFFFFFFF, int(expire_cap)
+        if expire_cap and expire_cap <= now:
+            raise ValueError("soft purge: the expiry cap must lie after now")
+        if not self.is_gpu:
+            return int(self._impl.soften_keyed_prefix(prefix, bool(exact), stale_at, expire_cap,
+                                                      now))
+        img = np.frombuffer(core().keyed_prefix_image(prefix), dtype=np.uint8)
+        image = torch.from_numpy(img.copy()).to(self.device)
+        out = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._impl.soften_keyed_prefix(image.data_ptr(), len(prefix), bool(exact), stale_at,
+                                       expire_cap, now, out.data_ptr(), self._s())
+        return int(out.item())  # (waits for the stream)
+
     def sweep(self, now: Optional[int] = None) -> tuple[int, int]:
         now = self.now() if now is None else now
         return tuple(self._impl.sweep(now, self._s()) if self.is_gpu else self._impl.sweep(now))

@@ -166,7 +166,12 @@ class Server:
         ``PURGE`` request is forwarded upstream like any other method), ``"loopback"``
         (clients on 127.0.0.0/8; others get 403) or ``"any"``. ``PURGE <url>`` removes the
         URL's object and all its Vary variants; with ``X-Purge-Mode: prefix`` every object
-        whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU)."""
+        whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU). With
+        ``X-Purge-Soft: 1`` and ``grace`` the same objects are kept and made stale instead:
+        the next request is served from the stale copy and revalidated in the background,
+        and their lives are capped at ``grace`` seconds from now (never extended). Without
+        ``grace``, or on a tier that cannot (memcached), it is a hard purge and the answer
+        says ``"soft":false``."""
         if purge not in ("off", "loopback", "any"):
             raise ValueError("purge must be 'off', 'loopback' or 'any'")
         if not servers:
@@ -292,7 +297,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    help="who may invalidate with the PURGE method: off (default; PURGE is "
                         "forwarded upstream), loopback (127.0.0.0/8 only, others get 403) or "
                         "any. 'PURGE /url' drops the URL and its Vary variants; with the header "
-                        "'X-Purge-Mode: prefix' everything under that URL prefix")
+                        "'X-Purge-Mode: prefix' everything under that URL prefix; with "
+                        "'X-Purge-Soft: 1' and --grace the objects are kept and made stale "
+                        "instead (served at once, revalidated in the background, gone at most "
+                        "--grace seconds later)")
     p.add_argument("--grace", type=int, default=0, metavar="S",
                    help="serve cached objects up to S seconds past their TTL while one "
                         "background request per key revalidates them upstream (If-None-Match / "

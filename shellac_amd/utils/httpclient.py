@@ -9,9 +9,14 @@ from ..server.http import HttpParser
 
 class HttpClient:
     def __init__(self, host: str = "127.0.0.1", port: int = 8080, timeout: float = 10.0):
-        self.sock = socket.create_connection((host, port), timeout=timeout)
+        self._addr, self._timeout = (host, port), timeout
+        self._connect()
+
+    def _connect(self) -> None:
+        self.sock = socket.create_connection(self._addr, timeout=self._timeout)
         self.sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
         self._buf = b""
+        self._last_said_close = False
 
     @staticmethod
     def request_bytes(path: str, method: str = "GET", headers: Optional[dict] = None,
@@ -43,8 +48,15 @@ class HttpClient:
 
     def get(self, path: str, **kw) -> HttpParser:
         head = kw.get("method", "GET") == "HEAD"
+        if self._last_said_close and not self._buf:
+            # the server announced the close with its last response (a proxy does after
+            # client_max_reqs requests on a connection): go on over a new connection
+            self.close()
+            self._connect()
         self.send(self.request_bytes(path, **kw))
-        return self.read_response(head=head)
+        r = self.read_response(head=head)
+        self._last_said_close = not r.keep_alive()
+        return r
 
     def pipeline(self, paths: Sequence[str], **kw) -> List[HttpParser]:
         self.send(b"".join(self.request_bytes(p, **kw) for p in paths))
