@@ -19,6 +19,16 @@ match costs the entry's CAS and both header stores) is measured first on the sam
 shard, with the same shapes: it removes nothing, so every family run scans the full shard.
 Its line ("op": "soft", the same fields; purge_match_removed holds the objects softened)
 is printed before the hard purge's ("op": "hard").
+
+--tags: every object carries a tag block of 4 tags between its key and its payload (keyed.h:
+[0x02 | 4 | 4 x u64]; one hash names the object's family, three are its own), and the purge by
+tag (k_purge_tags / k_soften_tags) is measured beside the prefix purge on the same shard:
+"op": "soft-tags" (it removes nothing) and "hard-tags", with the same fields. A tag purge of
+one family's hash matches the same 1/16 of the objects as the prefix purge of that family; a
+list of one hash no object carries matches nothing. All no-match runs, of every op, are timed
+on the full shard before anything is removed; the hard tag purge then removes the first six
+families and the hard prefix purge the next six ("match_live_first": the live objects when
+its first matching run began). The yardstick of a tag op is the prefix op's line of the same N.
 """
 from __future__ import annotations
 
@@ -38,12 +48,20 @@ from shellac_amd.ops.cache import CacheShard, digest_packed, item_bytes  # noqa:
 FAMILIES = 16
 KEY_MIN, KEY_MAX = 40, 80
 PAYLOAD = 1024
-STRIDE = (2 + KEY_MAX + PAYLOAD + 15) // 16 * 16
+TAGS = 4
+TAG_BLOCK = 2 + 8 * TAGS
+STRIDE = (2 + KEY_MAX + TAG_BLOCK + PAYLOAD + 15) // 16 * 16
+FAM_HASH = 0x0123456789ABCDEF      # family f's tag hash: (f + 1) * FAM_HASH; -1: nobody's
 
 
-def make_batch(ids: torch.Tensor):
+def fam_hash(f: int) -> int:
+    return (f + 1) * FAM_HASH
+
+
+def make_batch(ids: torch.Tensor, tags: bool = False):
     """Keyed values for object ids (on the ids' device): key = /fXX/<12 decimal digits of the
-    id>/ then 'x' up to its length (40 + id % 41), payload of 1 KiB after it."""
+    id>/ then 'x' up to its length (40 + id % 41), payload of 1 KiB after it. `tags`: a tag
+    block of TAGS hashes between the two: the family's at place id % TAGS, the others unique."""
     dev = ids.device
     n = ids.numel()
     klen = KEY_MIN + (ids * 2654435761 >> 7) % (KEY_MAX - KEY_MIN + 1)
@@ -71,6 +89,17 @@ def make_batch(ids: torch.Tensor):
     torch.cumsum(klen, 0, out=offs[1:])
     digests = digest_packed(packed.contiguous(), offs)
     vlen = (2 + klen + PAYLOAD).to(torch.int32)
+    if tags:
+        own = ids[:, None] * TAGS + torch.arange(TAGS, device=dev)[None, :] + 1
+        h = own * -0x61C8864680B583EB                    # (wraps: 64 well-mixed bits)
+        h[torch.arange(n, device=dev), ids % TAGS] = (fam + 1) * FAM_HASH
+        blk = torch.empty((n, TAG_BLOCK), dtype=torch.uint8, device=dev)
+        blk[:, 0] = 2
+        blk[:, 1] = TAGS
+        blk[:, 2:] = h.contiguous().view(torch.uint8).reshape(n, 8 * TAGS)
+        at = (2 + klen)[:, None] + torch.arange(TAG_BLOCK, device=dev)[None, :]
+        rows[torch.arange(n, device=dev)[:, None], at] = blk
+        vlen = (2 + klen + TAG_BLOCK + PAYLOAD).to(torch.int32)
     val_off = torch.arange(n, dtype=torch.int64, device=dev) * STRIDE
     values = torch.cat([rows.reshape(-1), torch.zeros(16, dtype=torch.uint8, device=dev)])
     return digests, values, val_off, vlen
@@ -94,18 +123,18 @@ def summary(ts, nbytes):
             "gb_per_s": round(nbytes / med / 1e3, 1)}
 
 
-def run(n: int, iters: int, dev, soft: bool = False) -> list:
+def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False) -> list:
     nb = 1
     while nb * 2 < n:       # <= 50 % slot load
         nb *= 2
-    avg_item = item_bytes(2 + (KEY_MIN + KEY_MAX) // 2 + PAYLOAD)
+    avg_item = item_bytes(2 + (KEY_MIN + KEY_MAX) // 2 + PAYLOAD + (TAG_BLOCK if tags else 0))
     log_bytes = (int(n * avg_item * 1.1) + (64 << 20)) // 16 * 16
     shard = CacheShard(log_bytes, nb, 1 << 16, dev)
     step = 1 << 17
     shard.reserve(step)
     for s in range(0, n, step):
         ids = torch.arange(s, min(s + step, n), dtype=torch.int64, device=dev)
-        d, v, vo, vl = make_batch(ids)
+        d, v, vo, vl = make_batch(ids, tags)
         shard.store(d, v, vo, vl)
     torch.cuda.synchronize(dev)
     assert shard.head() < log_bytes, "the log wrapped: objects were overwritten"
@@ -125,42 +154,76 @@ def run(n: int, iters: int, dev, soft: bool = False) -> list:
         shard._impl.soften_keyed_prefix(img.data_ptr(), plen, False, 0x5EEDF00D, now + 3600, now,
                                         out.data_ptr(), stream)
 
-    nomatch = image(b"/zzz/")
+    def tag_list(h: int):
+        return torch.tensor([h], dtype=torch.int64, device=dev)
 
-    def measure(op: str, purge) -> dict:
+    def hard_tags(lst, nlist):
+        shard._impl.remove_keyed_tags(lst.data_ptr(), nlist, now, out.data_ptr(), stream)
+
+    def soften_tags(lst, nlist):
+        shard._impl.soften_keyed_tags(lst.data_ptr(), nlist, 0x5EEDF00D, now + 3600, now,
+                                      out.data_ptr(), stream)
+
+    # what an op is called with: (pattern in device memory, its length) of a family / of nothing
+    # and the record bytes a live entry costs: header + value granule 0 (a 5-byte prefix ends
+    # there); the tag matcher reads the block's 34 bytes behind the key as well, one or two
+    # more 32-B sectors, counted as 64 B
+    by_prefix = (lambda f: (image(b"/f%02d/" % f), 5), (image(b"/zzz/"), 5), 64)
+    by_tag = (lambda f: (tag_list(fam_hash(f)), 1), (tag_list(-1), 1), 128)
+
+    def no_match(op: str, purge, args) -> dict:
+        nomatch = args[1]
         live0 = shard.sweep(now)[0]
         for _ in range(3):      # warm-up: code objects, caches
             shard._impl.sweep(now, stream)
-            purge(nomatch, 5)
+            purge(*nomatch)
         torch.cuda.synchronize(dev)
         t_sweep = [timed(lambda: shard._impl.sweep(now, stream), dev)[0] for _ in range(iters)]
-        t_nomatch = [timed(lambda: purge(nomatch, 5), dev)[0] for _ in range(iters)]
+        t_nomatch = [timed(lambda: purge(*nomatch), dev)[0] for _ in range(iters)]
         assert int(out[0]) == 0
-        t_match, removed, live = [], [], live0
-        match_bytes = []
-        for f in range(min(FAMILIES - 4, max(iters, 10))):
-            pre = b"/f%02d/" % f
-            img = image(pre)
-            t_match.append(timed(lambda: purge(img, len(pre)), dev)[0])
-            removed.append(int(out[0]))
-            match_bytes.append(nslots * 32 + live * 64)   # (a 5-byte prefix ends in granule 0)
-            if op == "hard":
-                live -= removed[-1]
-        res = {
+        return {
             "op": op,
             "objects": n, "live": int(live0), "index_slots": nslots, "log_bytes": log_bytes,
             "sweep": summary(t_sweep, nslots * 32),
-            "purge_nomatch": summary(t_nomatch, nslots * 32 + live0 * 64),
+            "purge_nomatch": summary(t_nomatch, nslots * 32 + live0 * args[2]),
+        }
+
+    def match(res: dict, purge, args, families) -> dict:
+        op = res["op"]
+        live = live_first = shard.sweep(now)[0]
+        t_match, removed, match_bytes = [], [], []
+        for f in families:
+            pat = args[0](f)
+            t_match.append(timed(lambda: purge(*pat), dev)[0])
+            removed.append(int(out[0]))
+            match_bytes.append(nslots * 32 + live * args[2])
+            if op.startswith("hard"):
+                live -= removed[-1]
+        res.update({
+            "match_live_first": int(live_first),
             "purge_match": summary(t_match, float(np.median(match_bytes))),
             "purge_match_first_us": round(t_match[0], 1),
             "purge_match_removed": removed,
             "purged_counter": shard.counters()["purged"],
-        }
+        })
         res["nomatch_over_sweep"] = round(res["purge_nomatch"]["median_us"] / res["sweep"]["median_us"], 2)
         res["match_over_sweep"] = round(res["purge_match"]["median_us"] / res["sweep"]["median_us"], 2)
         return res
 
-    return ([measure("soft", soften)] if soft else []) + [measure("hard", hard)]
+    fams = list(range(min(FAMILIES - 4, max(iters, 10))))
+    results = []
+    # the soft ops remove nothing: each sees the full shard throughout
+    for op, purge, args, on in (("soft", soften, by_prefix, soft),
+                                ("soft-tags", soften_tags, by_tag, tags)):
+        if on:
+            results.append(match(no_match(op, purge, args), purge, args, fams))
+    hard_ops = ([("hard-tags", hard_tags, by_tag)] if tags else []) + [("hard", hard, by_prefix)]
+    # every hard op's no-match runs first, on the full shard; then the families are shared out
+    pending = [(no_match(op, purge, args), purge, args) for op, purge, args in hard_ops]
+    share = len(fams) // len(pending)
+    for j, (res, purge, args) in enumerate(pending):
+        results.append(match(res, purge, args, fams[j * share:(j + 1) * share]))
+    return results
 
 
 def main():
@@ -169,12 +232,15 @@ def main():
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--soft", action="store_true",
                     help="also measure the soft purge, on the same shard, before the hard one")
+    ap.add_argument("--tags", action="store_true",
+                    help="store every object with 4 tags and measure the purge by tag (soft and "
+                         "hard) beside the prefix purge, on the same shard")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("purge_bench.py needs a GPU")
     dev = torch.device("cuda", 0)
     for n in (int(x) for x in a.objects.split(",")):
-        for res in run(n, a.iters, dev, a.soft):
+        for res in run(n, a.iters, dev, a.soft, a.tags):
             print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 

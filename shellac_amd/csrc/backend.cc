@@ -107,6 +107,21 @@ void DramBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t
   if (done) done(c);
 }
 
+void DramBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor*, PurgeCallback done) {
+  const bool ok = !hashes.empty() && hashes.size() <= kMaxPurgeTags;
+  const int64_t n = ok ? (int64_t)cache_.purge_tags(hashes, now()) : -1;
+  if (done) done(n);
+}
+
+void DramBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
+                              uint32_t keep_s, Executor*, PurgeCallback done) {
+  const uint32_t n = now();
+  const bool ok = !hashes.empty() && hashes.size() <= kMaxPurgeTags;
+  const int64_t c = ok ? (int64_t)cache_.soften_tags(hashes, stale_at, keep_s ? n + keep_s : 0, n)
+                       : -1;
+  if (done) done(c);
+}
+
 void DramBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
                         const uint32_t* flags, Executor*, TouchCallback done) {
   const uint32_t n = now();
@@ -235,6 +250,30 @@ void TieredBackend::soften_prefix(const std::string& pattern, bool exact, uint32
     // dropped, or landed it in L1 before the pass below, which softens it
     move_purge_epoch();
     l1_->soften_prefix(pattern, exact, stale_at, keep_s, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
+    });
+  });
+}
+
+void TieredBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor* ex,
+                               PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->purge_tags(hashes, ex, [this, hashes, ex, done = std::move(done)](int64_t n2) {
+    // as purge_prefix: L2 is clean from here on, promotions read before it are dropped
+    move_purge_epoch();
+    l1_->purge_tags(hashes, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
+    });
+  });
+}
+
+void TieredBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
+                                uint32_t keep_s, Executor* ex, PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->soften_tags(hashes, stale_at, keep_s, ex,
+                   [this, hashes, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
+    move_purge_epoch();
+    l1_->soften_tags(hashes, stale_at, keep_s, ex, [done, n2](int64_t n1) {
       if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });

@@ -124,6 +124,26 @@ class CacheBackend {
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
   }
+  // Purge by surrogate key: drop every live object whose stored value carries a tag block
+  // (keyed.h) holding one of `hashes` (tag_hash of each tag; at most kMaxPurgeTags), or the
+  // overflow block. Ordered and answered as purge_prefix: the objects removed, or -1 where
+  // the tier cannot do it (the default), for an empty list and for one that is too long.
+  virtual void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) {
+    (void)hashes;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
+  // Soft purge by surrogate key: purge_tags' matcher, soften_prefix's action and answer.
+  virtual void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
+                           uint32_t keep_s, Executor* ex, PurgeCallback done) {
+    (void)hashes;
+    (void)stale_at;
+    (void)keep_s;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
   // Touch: give the live object of exactly `key` the TTL `ttl_s` from now (0 = never expires)
   // and, when `flags` is not null (read before the call returns), new flags, without moving
   // its bytes. A write: ordered with
@@ -191,6 +211,9 @@ class DramBackend : public CacheBackend {
   void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
   void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
                      Executor* ex, PurgeCallback done) override;
+  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
+                   Executor* ex, PurgeCallback done) override;
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override;
   void flush() override;
@@ -308,6 +331,11 @@ class HbmBackend : public CacheBackend {
   // replicas and refresh fills included, and marks shards out of service purge_dirty.
   void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
                      Executor* ex, PurgeCallback done) override;
+  // The same ReqKind::Purge request carrying a tag list instead of a pattern: ordering,
+  // fan-out, hot replicas, refresh fills and purge_dirty are purge_prefix's.
+  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
+                   Executor* ex, PurgeCallback done) override;
   // Routed like del(): to the owner, and for a hot object written through to every shard in
   // service (the answer is the owner's). Queued on the shard's stream behind the writes
   // queued before it; a flight's touches are one key-exact HbmCache::touch launch.
@@ -343,6 +371,8 @@ class HbmBackend : public CacheBackend {
     // Purge: a soft one (soften_prefix) keeps the objects; `flags` holds stale_at and `ttl`
     // keep_s; `exact`: the key must equal the pattern
     bool soft = false, exact = false;
+    // Purge by tag (purge_tags / soften_tags): the hash list; `key` is empty then
+    std::shared_ptr<const std::vector<uint64_t>> tags;
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
@@ -415,6 +445,9 @@ class HbmBackend : public CacheBackend {
   // objects a peer had not purged yet, and flushes the restored shard again
   std::atomic<uint64_t> purge_started_{0}, purge_done_{0};
   std::atomic<uint64_t> soft_purges_{0};
+  // purge_tags and soften_tags calls taken (they count in purge_started_ / purge_done_ for
+  // the restore's overlap check, and are taken out of the `hbm_purges` figure)
+  std::atomic<uint64_t> tag_purges_{0};
   void purge_finish(const std::shared_ptr<Purge>& p);
   // purge_prefix and soften_prefix: `proto` (kind Purge, the pattern and the soft fields) goes
   // to every shard in service
@@ -474,6 +507,10 @@ class TieredBackend : public CacheBackend {
   // either level cannot.
   void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
                      Executor* ex, PurgeCallback done) override;
+  // L2 then L1 with the purge epoch moved in between, as the prefix forms.
+  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
+                   Executor* ex, PurgeCallback done) override;
   // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
   // writes both levels). A promotion that straddles the touch is dropped, as for del(): it
   // would carry the pre-touch TTL and flags into L1.
@@ -540,6 +577,13 @@ class FaultBackend : public CacheBackend {
   void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
                      Executor* ex, PurgeCallback done) override {
     inner_->soften_prefix(pattern, exact, stale_at, keep_s, ex, std::move(done));
+  }
+  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override {
+    inner_->purge_tags(hashes, ex, std::move(done));
+  }
+  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
+                   Executor* ex, PurgeCallback done) override {
+    inner_->soften_tags(hashes, stale_at, keep_s, ex, std::move(done));
   }
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override {

@@ -396,11 +396,35 @@ void HbmBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t 
   purge_fan_out(proto, ex, std::move(done));
 }
 
+// A tag purge is the same request with a hash list in place of the pattern.
+void HbmBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor* ex,
+                            PurgeCallback done) {
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  proto.tags = std::make_shared<const std::vector<uint64_t>>(hashes);
+  purge_fan_out(proto, ex, std::move(done));
+}
+
+void HbmBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
+                             uint32_t keep_s, Executor* ex, PurgeCallback done) {
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  proto.tags = std::make_shared<const std::vector<uint64_t>>(hashes);
+  proto.soft = true;
+  proto.flags = stale_at;
+  proto.ttl = keep_s;
+  purge_fan_out(proto, ex, std::move(done));
+}
+
 void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done) {
-  if (proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
+  if (proto.tags ? proto.tags->empty() || proto.tags->size() > kMaxPurgeTags
+                 : proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
     if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
     return;
   }
+  if (proto.tags) tag_purges_.fetch_add(1, std::memory_order_acq_rel);  // (before started)
   purge_started_.fetch_add(1, std::memory_order_acq_rel);
   auto p = std::make_shared<Purge>();
   p->ex = ex;
@@ -537,11 +561,16 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_migrated", sum(&Dev::migrated));
   out->emplace_back("hbm_migrate_ns", sum(&Dev::migrate_ns));
   out->emplace_back("hbm_dropped_sets", sum(&Dev::dropped));
-  out->emplace_back("hbm_purges", purge_started_.load());
+  // (prefix purges, hard and soft: the tag purges among the calls begun are counted apart)
+  const uint64_t begun = purge_started_.load(), by_tag = tag_purges_.load();
+  out->emplace_back("hbm_purges", begun - (by_tag < begun ? by_tag : begun));
   out->emplace_back("hbm_purged_objects", sum(&Dev::purged_objects));
   out->emplace_back("hbm_purged_bytes", sum(&Dev::purged_bytes));
   out->emplace_back("hbm_soft_purges", soft_purges_.load());
   out->emplace_back("hbm_softened_objects", sum(&Dev::softened_objects));
+  out->emplace_back("hbm_tag_purges", by_tag);
+  out->emplace_back("hbm_tag_purged_objects", sum(&Dev::tag_purged_objects));
+  out->emplace_back("hbm_tag_softened_objects", sum(&Dev::tag_softened_objects));
   // touch requests taken, and the entries the shards' kernels updated (replicas included)
   out->emplace_back("hbm_touches", sum(&Dev::touch_reqs));
   out->emplace_back("hbm_touched", t.touched);

@@ -80,6 +80,25 @@ PYBIND11_MODULE(_shellac_core, m) {
                              reinterpret_cast<const uint8_t*>(p.data()), p.size());
     return py::bytes(img);
   }, "pattern image of a purge prefix for HbmCache.remove_keyed_prefix");
+  m.def("tag_hash", [](py::bytes tag) {
+    const std::string t = tag;
+    return tag_hash(t);
+  }, "hash of one surrogate key (tag): the low word of its digest");
+  m.def("tag_block", [](const std::vector<uint64_t>& hashes) {
+    std::string b(tag_block_size(hashes.size()), '\0');
+    write_tag_block(reinterpret_cast<uint8_t*>(&b[0]), hashes.data(), hashes.size());
+    return py::bytes(b);
+  }, "the tag block [0x02 | ntags | hashes] for distinct hashes (more than 32: overflow)");
+  m.def("parse_tag_block", [](py::bytes payload) {
+    const std::string p = payload;
+    const uint64_t* hs;
+    unsigned nt;
+    bool over;
+    const size_t strip = parse_tag_block(p.data(), p.size(), &hs, &nt, &over);
+    std::vector<uint64_t> out;
+    for (unsigned i = 0; i < nt; ++i) out.push_back(tag_block_hash(hs, i));
+    return py::make_tuple(strip, out, over);
+  }, "(bytes to strip, hashes, overflow) of the tag block at the start of a payload");
   m.def("bucket_pair", [](uint64_t lo, uint64_t hi, uint64_t nbuckets) {
     const Digest d{lo, hi};
     return std::vector<uint64_t>{bucket1(d, nbuckets - 1), bucket2(d, nbuckets - 1)};
@@ -241,6 +260,20 @@ PYBIND11_MODULE(_shellac_core, m) {
                               P<uint64_t>(out), S(s));
       }, py::arg("image"), py::arg("plen"), py::arg("exact"), py::arg("stale_at"),
          py::arg("expire_cap"), py::arg("now"), py::arg("out"), py::arg("stream"))
+      // tags: ntags u64 hashes (device or mapped host memory); out: 2 words; asynchronous
+      .def("remove_keyed_tags", [](HbmCache& c, uintptr_t tags, uint32_t ntags, uint32_t now,
+                                   uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.remove_keyed_tags(P<const uint64_t>(tags), ntags, now, P<uint64_t>(out), S(s));
+      }, py::arg("tags"), py::arg("ntags"), py::arg("now"), py::arg("out"), py::arg("stream"))
+      // out: 1 word; asynchronous on the stream
+      .def("soften_keyed_tags", [](HbmCache& c, uintptr_t tags, uint32_t ntags, uint32_t stale_at,
+                                   uint32_t expire_cap, uint32_t now, uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.soften_keyed_tags(P<const uint64_t>(tags), ntags, stale_at, expire_cap, now,
+                            P<uint64_t>(out), S(s));
+      }, py::arg("tags"), py::arg("ntags"), py::arg("stale_at"), py::arg("expire_cap"),
+         py::arg("now"), py::arg("out"), py::arg("stream"))
       // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
       .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
@@ -465,6 +498,15 @@ PYBIND11_MODULE(_shellac_core, m) {
                                      (uint32_t)p.size(), exact, stale_at, expire_cap, now);
       }, py::arg("prefix"), py::arg("exact"), py::arg("stale_at"), py::arg("expire_cap"),
          py::arg("now"))
+      .def("remove_keyed_tags", [](HostCache& c, std::vector<uint64_t> tags, uint32_t now) {
+        uint64_t out[2] = {0, 0};
+        c.remove_keyed_tags(tags.data(), (uint32_t)tags.size(), now, out);
+        return py::make_tuple(out[0], out[1]);
+      }, py::arg("tags"), py::arg("now"))
+      .def("soften_keyed_tags", [](HostCache& c, std::vector<uint64_t> tags, uint32_t stale_at,
+                                   uint32_t expire_cap, uint32_t now) {
+        return c.soften_keyed_tags(tags.data(), (uint32_t)tags.size(), stale_at, expire_cap, now);
+      }, py::arg("tags"), py::arg("stale_at"), py::arg("expire_cap"), py::arg("now"))
       .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
                        uint32_t now) {

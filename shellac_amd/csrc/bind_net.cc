@@ -8,6 +8,7 @@
 #include "backend.h"
 #include "bind_parts.h"
 #include "ketama.h"
+#include "keyed.h"
 #include "loadgen.h"
 #include <pybind11/numpy.h>
 #include "mcserver.h"
@@ -273,6 +274,23 @@ void bind_net(py::module_& m) {
           be->soften_prefix(pat, exact, stale_at, keep_s, &g_inline, std::move(cb));
         });
       }, py::arg("pattern"), py::arg("stale_at"), py::arg("keep_s") = 0, py::arg("exact") = false)
+      // purge / soft purge by surrogate key (blocking): `tags` are the tag byte strings
+      .def("purge_tags", [](BackendHandle& h, const std::vector<std::string>& tags) {
+        std::vector<uint64_t> hs;
+        for (const std::string& t : tags) hs.push_back(tag_hash(t));
+        CacheBackend* be = h.be.get();
+        return blocking_purge(
+            [&](PurgeCallback cb) { be->purge_tags(hs, &g_inline, std::move(cb)); });
+      }, py::arg("tags"))
+      .def("soften_tags", [](BackendHandle& h, const std::vector<std::string>& tags,
+                             uint32_t stale_at, uint32_t keep_s) {
+        std::vector<uint64_t> hs;
+        for (const std::string& t : tags) hs.push_back(tag_hash(t));
+        CacheBackend* be = h.be.get();
+        return blocking_purge([&](PurgeCallback cb) {
+          be->soften_tags(hs, stale_at, keep_s, &g_inline, std::move(cb));
+        });
+      }, py::arg("tags"), py::arg("stale_at"), py::arg("keep_s") = 0)
       // in-place touch (blocking): 1 touched, 0 not found, -1 the tier cannot. `flags` None
       // keeps the object's flags; `digest_of`: look the key up under another key's digest (a
       // forged collision)
@@ -490,9 +508,10 @@ void bind_net(py::module_& m) {
                        int health_interval_ms, int health_timeout_ms, int health_fails,
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
                        uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge,
-                       uint32_t grace) {
+                       uint32_t grace, const std::string& tag_header) {
              ProxyConfig c;
              c.grace = grace;
+             c.tag_header = tag_header;
              SH_CHECK(purge == "off" || purge == "loopback" || purge == "any",
                       "purge must be off, loopback or any");
              c.purge = purge;
@@ -546,7 +565,7 @@ void bind_net(py::module_& m) {
            py::arg("cpus") = std::vector<int>{}, py::arg("spin_us") = 0,
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
            py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
-           py::arg("purge") = "off", py::arg("grace") = 0)
+           py::arg("purge") = "off", py::arg("grace") = 0, py::arg("tag_header") = "")
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)

@@ -226,7 +226,7 @@ struct Flight {
   // their packed key bytes; trow maps a touch request to its row (the last request of a key wins)
   Mapped touch_rows, touch_kbytes;
   // launch_purges: pattern images (keyed.h) and {removed, bytes} word pairs, one per purge (a
-  // soft purge fills the first word: the objects softened)
+  // soft purge fills the first word: the objects softened); a tag purge's image is its hash list
   Mapped purge_img, purge_out;
   void release_mapped() {
     for (Mapped* m : {&keys, &offs, &set_keys, &set_vals, &set_voff, &set_meta, &del_keys,
@@ -367,7 +367,8 @@ struct HbmBackend::Dev {
       dropped{0}, staged_copies{0}, served_batches{0}, ordered_gets{0},
       migrated{0}, migrate_ns{0}, direct_jobs{0}, direct_reqs{0}, direct_fallbacks{0},
       direct_overflows{0}, direct_timeouts{0}, direct_ns{0}, purged_objects{0},
-      purged_bytes{0}, touch_reqs{0}, softened_objects{0};
+      purged_bytes{0}, touch_reqs{0}, softened_objects{0}, tag_purged_objects{0},
+      tag_softened_objects{0};
 
   void loop();
   bool take_batch(std::vector<Req>* out, bool* do_flush, bool* rebuilding);

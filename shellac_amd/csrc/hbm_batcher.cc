@@ -386,11 +386,16 @@ void HbmBackend::Dev::launch_fills(Flight& f) {
 // Prefix purges: after the SETs and DELETEs queued before them (a purge is its flight's last
 // request); pattern image and result words in mapped memory
 void HbmBackend::Dev::launch_purges(Flight& f) {
+  // a request's bytes in purge_img: the pattern image, or the tag list (kept 16-B aligned)
+  const auto img_size = [](const Req& r) {
+    return r.tags ? (r.tags->size() * sizeof(uint64_t) + 15) & ~(size_t)15
+                  : keyed_prefix_image_bytes(r.key.size());
+  };
   size_t np = 0, img_bytes = 0;
   for (uint32_t i : f.ctls)
     if (f.reqs[i].kind == ReqKind::Purge) {
       ++np;
-      img_bytes += keyed_prefix_image_bytes(f.reqs[i].key.size());
+      img_bytes += img_size(f.reqs[i]);
     }
   if (!np) return;
   f.purge_img.ensure(img_bytes);
@@ -399,18 +404,28 @@ void HbmBackend::Dev::launch_purges(Flight& f) {
   for (uint32_t i : f.ctls) {
     const Req& r = f.reqs[i];
     if (r.kind != ReqKind::Purge) continue;
-    write_keyed_prefix_image(f.purge_img.host<uint8_t>() + off,
-                             reinterpret_cast<const uint8_t*>(r.key.data()), r.key.size());
     uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * j;
     res[0] = res[1] = 0;
-    if (r.soft)  // (flags: stale_at, ttl: keep_s; the flight's SET chains are whole ones)
-      cache->soften_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
-                                 r.exact, r.flags, r.ttl ? f.tnow + r.ttl : 0, f.tnow,
-                                 f.purge_out.dev<uint64_t>() + 2 * j, stream);
-    else
-      cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
-                                 f.tnow, f.purge_out.dev<uint64_t>() + 2 * j, stream);
-    off += keyed_prefix_image_bytes(r.key.size());
+    uint64_t* const out = f.purge_out.dev<uint64_t>() + 2 * j;
+    const uint32_t cap = r.ttl ? f.tnow + r.ttl : 0;  // (soft: flags is stale_at, ttl keep_s)
+    if (r.tags) {
+      const uint32_t nt = (uint32_t)r.tags->size();
+      std::memcpy(f.purge_img.host<uint8_t>() + off, r.tags->data(), nt * sizeof(uint64_t));
+      const uint64_t* const list =
+          reinterpret_cast<const uint64_t*>(f.purge_img.dev<uint8_t>() + off);
+      if (r.soft) cache->soften_keyed_tags(list, nt, r.flags, cap, f.tnow, out, stream);
+      else cache->remove_keyed_tags(list, nt, f.tnow, out, stream);
+    } else {
+      write_keyed_prefix_image(f.purge_img.host<uint8_t>() + off,
+                               reinterpret_cast<const uint8_t*>(r.key.data()), r.key.size());
+      if (r.soft)  // (the flight's SET chains are whole ones)
+        cache->soften_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
+                                   r.exact, r.flags, cap, f.tnow, out, stream);
+      else
+        cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
+                                   f.tnow, out, stream);
+    }
+    off += img_size(r);
     ++j;
   }
 }
@@ -484,7 +499,9 @@ void HbmBackend::Dev::finish_ctls(Flight& f) {
     Req& r = f.reqs[i];
     if (r.kind == ReqKind::Purge) {
       const uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * pj++;
-      if (r.soft) {
+      if (r.tags) {
+        (r.soft ? tag_softened_objects : tag_purged_objects) += res[0];
+      } else if (r.soft) {
         softened_objects += res[0];
       } else {
         purged_objects += res[0];

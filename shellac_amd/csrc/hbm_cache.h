@@ -272,6 +272,18 @@ class HbmCache {
   // k_soften_prefix for what holds beside a SET chain on another stream.
   void soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exact, uint32_t stale_at,
                            uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
+  // Tag purge of keyed values: removes every live entry whose stored value carries, at value
+  // byte 2 + klen, a tag block (keyed.h) holding one of tags[0..ntags), 1 <= ntags <= 64, or
+  // the overflow block. `tags` holds u64 tag hashes, 8-byte aligned, in device or mapped host
+  // memory, and stays valid until the stream has run the call; everything else (`out`'s two
+  // words, the `purged` counter, the streams, what holds beside appends) is
+  // remove_keyed_prefix's. Uses scratch words of its own.
+  void remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now, uint64_t* out,
+                         hipStream_t s);
+  // Soft tag purge: remove_keyed_tags' matcher, soften_keyed_prefix's action, result word and
+  // checks (the cap lies after now; refused while a phase-1 batch waits for its phase 2).
+  void soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
+                         uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
   // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
   // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
   // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte

@@ -43,6 +43,10 @@
 //                  action: a matching live entry is kept, its record's flags become the
 //                  given freshness time and its expiry is capped (never extended), by a CAS
 //                  that keeps the CLOCK bit and stores into the record header.
+//   k_purge_tags   k_purge_prefix's scan and action with a tag matcher: a record whose tag
+//                  block (keyed.h, at value byte 2 + klen) holds one of up to 64 hashes, or
+//                  the overflow block, is removed; unaligned hashes come from aligned dwords.
+//   k_soften_tags  the same matcher with k_soften_prefix's action.
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -3429,6 +3433,216 @@ __global__ __launch_bounds__(kBlock) void k_soften_prefix(
   }
 }
 
+// ---- purge by tag --------------------------------------------------------------------------
+// The matcher of k_purge_tags / k_soften_tags. `rec` is a record whose header was checked
+// (digest, vlen, magic), `v0` its value granule 0, 4 <= vlen <= max_item. The tag block of
+// keyed.h sits at value byte o = 2 + klen: [0x02 | ntags | ntags x u64 LE]. Reads are aligned
+// 16-B granules (the block's two header bytes) and aligned dwords (the hashes, put together
+// with alignbyte), all inside [record, record + item_bytes(vlen)): a byte below vlen lies in
+// a granule, and a dword, that starts below align_up(vlen, 16). The granule holding o and, if
+// the ntags byte falls into the next one, that one too are loaded before either is looked at:
+// one round trip more than the prefix matcher, not two (with klen <= 12 both are granule 0).
+__device__ __forceinline__ uint32_t granule_byte(const uint4 g, const uint32_t i) {
+  const uint32_t w = i < 8 ? (i < 4 ? g.x : g.y) : (i < 12 ? g.z : g.w);
+  return (w >> ((i & 3u) * 8u)) & 0xffu;
+}
+
+__device__ __forceinline__ bool tag_block_match(const uint4* __restrict__ rec, const uint32_t vlen,
+                                                const uint4 v0, const uint2* __restrict__ s_tags,
+                                                const uint32_t nlist) {
+  const uint32_t o = (uint32_t)kKeyedPrefix + (v0.x & 0xffffu);
+  if (o + 2 > vlen) return false;
+  const uint32_t ga = o >> 4, gb = (o + 1) >> 4;
+  uint4 a = v0, b = v0;
+  if (ga) a = rec[2 + ga];
+  if (gb != ga) b = rec[2 + gb];
+  else b = a;
+  if (granule_byte(a, o & 15u) != (uint32_t)kTagMarker) return false;
+  const uint32_t nt = granule_byte(b, (o + 1) & 15u);
+  if (nt == kTagOverflow) return true;
+  if (nt > kMaxObjectTags || o + 2 + 8 * nt > vlen) return false;
+  const uint32_t* const vw = reinterpret_cast<const uint32_t*>(rec + 2);  // the value's dwords
+  const uint32_t sh = (o + 2) & 3u;
+  uint32_t d = (o + 2) >> 2;
+  for (uint32_t t = 0; t < nt; ++t, d += 2) {
+    // hash t holds bytes [4d + sh, 4d + sh + 8): dwords d, d+1 and, unless aligned, d+2
+    const uint32_t w0 = vw[d], w1 = vw[d + 1];
+    const uint32_t w2 = sh ? vw[d + 2] : 0u;
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh);
+    const uint32_t hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
+    for (uint32_t j = 0; j < nlist; ++j) {
+      const uint2 q = s_tags[j];
+      if (q.x == lo && q.y == hi) return true;
+    }
+  }
+  return false;
+}
+
+// The purge list: read once per workgroup into LDS (it may be mapped host memory).
+__device__ __forceinline__ void stage_tag_list(uint2* s_tags, const uint2* __restrict__ tags,
+                                               const uint32_t nlist) {
+  for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s_tags[j] = tags[j];
+  __syncthreads();
+}
+
+// Tag purge: remove every live entry whose stored keyed value carries a tag block (keyed.h)
+// holding one of the `nlist` <= kMaxPurgeTags hashes in `tags`, or the overflow block.
+// k_purge_prefix's traversal (one lane per index slot, grid-stride), liveness, record
+// re-check and action (the CAS of loc to 0, `purged`, the two result words with one add per
+// word per workgroup); only the matcher differs (tag_block_match).
+//
+// What it relies on: what k_purge_prefix relies on. Exactness comes from stream order between
+// whole SET chains: the backend queues it between them. Beside an append on another stream
+// it only reads the log, inside [record, record + item_bytes(vlen)) with vlen <= max_item and
+// a 16-B-aligned loc (inside the log's slack), of a record that carried the entry's digest,
+// vlen and magic; the removal is a CAS of the very loc that was read, so a record torn while
+// it was compared belongs to an entry the append is about to kill, and an entry a SET
+// re-pointed keeps its new loc. The ring and the log are untouched.
+__global__ __launch_bounds__(kBlock) void k_purge_tags(
+    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    const uint2* __restrict__ tags, uint32_t nlist, unsigned long long* __restrict__ out,
+    CacheCounters* __restrict__ ctr) {
+  __shared__ uint2 s_tags[kMaxPurgeTags];
+  stage_tag_list(s_tags, tags, nlist);
+  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
+  const uint64_t head = *head_ptr;
+  unsigned long long removed = 0, bytes = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < kKeyedPrefix + 2 || vlen > max_item || ((loc - 1) & 15)) continue;
+    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    if (!tag_block_match(rec, vlen, rec[2], s_tags, nlist)) continue;
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
+                  0ull) == loc) {
+      ++removed;
+      bytes += item_bytes(vlen);
+    }
+  }
+  block_count(ctr, removed, &CacheCounters::purged);
+  __shared__ unsigned long long s_res[2][kBlock / 64];
+  removed = wave_sum(removed);
+  bytes = wave_sum(bytes);
+  if ((threadIdx.x & 63) == 0) {
+    s_res[0][threadIdx.x >> 6] = removed;
+    s_res[1][threadIdx.x >> 6] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0, t1 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+      t0 += s_res[0][k];
+      t1 += s_res[1][k];
+    }
+    if (t0) atomicAdd(&out[0], t0);
+    if (t1) atomicAdd(&out[1], t1);
+  }
+}
+
+// Soft tag purge: k_purge_tags' scan and matcher, k_soften_prefix's action, word for word:
+// the record's flags become `stale_at` and an expiry of never or after `expire_cap` becomes
+// expire_cap, in the entry by a CAS of the {vlen | expire} word that keeps kRefBit (bounded
+// retries, the slot read again afterwards and the old expiry put back if it passed to another
+// entry), then in the record's ItemHeader. out[0] counts the live matches, whether or not
+// their words changed; no CacheCounters field.
+//
+// What it relies on: what k_soften_prefix relies on. Exactness comes from stream order
+// between whole SET chains. Beside a SET chain on another stream it stays memory-safe and
+// leaves non-matching objects alone: it writes into the log, so liveness is judged at
+// max(head, claim) (a record the queued appends will overwrite is neither written nor
+// counted), the record must carry the entry's digest, vlen and magic, every access stays
+// inside [record, record + item_bytes(vlen)), and the expiry goes in by a CAS of the word
+// read with the digest and the loc. HbmCache::soften_keyed_tags refuses while a detached
+// CLOCK hand is pending (it rewrites that word from a staged value).
+__global__ __launch_bounds__(kBlock) void k_soften_tags(
+    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
+    uint32_t max_item, uint32_t now, const uint2* __restrict__ tags, uint32_t nlist,
+    uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
+  __shared__ uint2 s_tags[kMaxPurgeTags];
+  stage_tag_list(s_tags, tags, nlist);
+  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
+  // the head the queued appends reach (equal to the head slot once they have run)
+  const uint64_t hs = *head_ptr, hc = *claim_ptr;
+  const uint64_t head = hc > hs ? hc : hs;
+  unsigned long long softened = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < kKeyedPrefix + 2 || vlen > max_item || ((loc - 1) & 15)) continue;
+    uint8_t* const recb = log + (loc - 1) % cap;
+    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    if (!tag_block_match(rec, vlen, rec[2], s_tags, nlist)) continue;
+    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
+    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
+      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
+      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
+      bool done = false;
+      for (int t = 0; t < kTouchCasTries; ++t) {
+        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
+        const unsigned long long prev = atomicCAS(w, expect, want);
+        if (prev == expect) {
+          done = true;
+          break;
+        }
+        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
+        expect = prev;
+      }
+      if (!done) continue;
+      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
+      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
+        // the slot passed to another entry with an equal word: put its expiry back
+        unsigned long long cur = want;
+        for (int t = 0; t < 2; ++t) {
+          const unsigned long long prev =
+              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
+          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
+          cur = prev;
+        }
+        continue;
+      }
+      h->expire = expire_cap;
+    }
+    h->flags = stale_at;
+    ++softened;
+  }
+  __shared__ unsigned long long s_res[kBlock / 64];
+  softened = wave_sum(softened);
+  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
+    if (t0) atomicAdd(&out[0], t0);
+  }
+}
+
 // Export the digests of all live entries (rebalancing / warm restore). One atomic
 // per workgroup per pass reserves the output range; lanes write in block order.
 __global__ __launch_bounds__(kBlock) void k_export(const Entry* __restrict__ index, uint64_t nslots,
@@ -3765,7 +3979,7 @@ HbmCache::HbmCache(const ShardConfig& cfg) : cfg_(cfg) {
   HIP_OK(hipMalloc(&index_, cfg_.nbuckets * kBucketBytes));
   HIP_OK(hipMalloc(&head_, 64));
   HIP_OK(hipMalloc(&ctr_, kCtrShards * sizeof(CacheCounters)));
-  HIP_OK(hipMalloc(&scratch_, 64));
+  HIP_OK(hipMalloc(&scratch_, 128));
   HIP_OK(hipMalloc(&done_ctr_, 64));
   HIP_OK(hipMemset(done_ctr_, 0, 64));
   const size_t lb_words = (size_t)(kSmallGetMax / kEdgeKeys + 1);
@@ -4653,6 +4867,45 @@ void HbmCache::soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exa
                      cfg_.max_item, now, reinterpret_cast<const uint4*>(image), plen,
                      (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u, stale_at, expire_cap,
                      acc);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now,
+                                 uint64_t* out, hipStream_t s) {
+  TraceRange tr("hbm.purge_tags");
+  SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
+  SH_CHECK(tags && out, "tag purge needs a tag list and a result buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 8;  // (0..7: sweep, export, the prefix purges)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_purge_tags, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock), 0,
+                     s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
+                     reinterpret_cast<const uint2*>(tags), ntags, acc, ctr_);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
+                                 uint32_t expire_cap, uint32_t now, uint64_t* out,
+                                 hipStream_t s) {
+  TraceRange tr("hbm.soften_tags");
+  SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
+  SH_CHECK(tags && out, "tag purge needs a tag list and a result buffer");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
+  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 10;  // (8..9: the hard tag purge)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_soften_tags, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
+                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
+                     cfg_.max_item, now, reinterpret_cast<const uint2*>(tags), ntags, stale_at,
+                     expire_cap, acc);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
 }

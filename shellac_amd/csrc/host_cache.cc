@@ -441,6 +441,68 @@ uint64_t HostCache::soften_keyed_prefix(const uint8_t* prefix, uint32_t plen, bo
   return softened;
 }
 
+// The record of slot k if the entry is live, its own (digest, vlen, magic) and a candidate for
+// the tag scan; else null.
+uint8_t* HostCache::tag_scan_record(uint64_t k, uint32_t now, uint32_t* vlen_out) {
+  Entry& e = index_[k];
+  if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) return nullptr;
+  const uint32_t vlen = entry_vlen(e.vlen);
+  if (vlen < kKeyedPrefix + 2 || vlen > max_item_ || ((e.loc - 1) & 15)) return nullptr;
+  uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+  ItemHeader h;
+  std::memcpy(&h, rec, sizeof(h));
+  if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) return nullptr;
+  *vlen_out = vlen;
+  return rec;
+}
+
+void HostCache::remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now,
+                                  uint64_t out[2]) {
+  SH_CHECK(tags && ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t removed = 0, bytes = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    uint32_t vlen;
+    const uint8_t* const rec = tag_scan_record(k, now, &vlen);
+    if (!rec || !keyed_tags_match(rec + kItemHeaderBytes, vlen, tags, ntags)) continue;
+    index_[k].loc = 0;
+    ++removed;
+    bytes += item_bytes(vlen);
+  }
+  ctr_.purged += removed;
+  if (out) {
+    out[0] = removed;
+    out[1] = bytes;
+  }
+}
+
+uint64_t HostCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
+                                      uint32_t expire_cap, uint32_t now) {
+  SH_CHECK(tags && ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t softened = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    uint32_t vlen;
+    uint8_t* const rec = tag_scan_record(k, now, &vlen);
+    if (!rec || !keyed_tags_match(rec + kItemHeaderBytes, vlen, tags, ntags)) continue;
+    Entry& e = index_[k];
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
+    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
+      e.expire = expire_cap;
+      h.expire = expire_cap;
+    }
+    h.flags = stale_at;
+    std::memcpy(rec, &h, sizeof(h));
+    ++softened;
+  }
+  return softened;
+}
+
 void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
                       const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
                       uint32_t now) {

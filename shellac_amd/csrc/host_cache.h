@@ -43,6 +43,13 @@ class HostCache {
   // header; nothing else changes. expire_cap is 0 or > now. Returns the live matches.
   uint64_t soften_keyed_prefix(const uint8_t* prefix, uint32_t plen, bool exact, uint32_t stale_at,
                                uint32_t expire_cap, uint32_t now);
+  // Tag purge (HbmCache::remove_keyed_tags, whose semantic reference this is): removes every
+  // live entry whose record is its own and whose keyed value carries a tag block (keyed.h)
+  // matching tags[0..ntags), 1 <= ntags <= 64; out as remove_keyed_prefix.
+  void remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now, uint64_t out[2]);
+  // Soft tag purge: the same matcher with soften_keyed_prefix's action; returns the live matches.
+  uint64_t soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
+                             uint32_t expire_cap, uint32_t now);
   // In-place change of expiry (and flags, nullable) of each row's live entry, in the index
   // and in the record header (HbmCache::touch, whose semantic reference this is). With key
   // bytes (nullable with their offsets) a row only matches a keyed record of exactly that key.
@@ -79,6 +86,7 @@ class HostCache {
   uint64_t reinsert_max() const { return evict_ ? rmax_ : 0; }
 
  private:
+  uint8_t* tag_scan_record(uint64_t k, uint32_t now, uint32_t* vlen_out);
   struct Row {  // one SET row of a (possibly combined) batch
     Digest key;
     const uint8_t* val;

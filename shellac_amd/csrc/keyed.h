@@ -12,6 +12,8 @@
 #include <cstring>
 #include <string>
 
+#include "digest.h"
+
 namespace shellac {
 
 constexpr size_t kKeyedPrefix = 2;
@@ -64,6 +66,99 @@ inline void write_keyed_prefix_image(uint8_t* dst, const uint8_t* prefix, size_t
     if (at >= kKeyedPrefix && at < end) ml[b] = 0xff;
   }
   std::memcpy(pat + kKeyedPrefix, prefix, plen);
+}
+
+// ---- tag block (purge by surrogate key) ------------------------------------------------------
+// A tagged payload starts with a tag block, so that a scan finds an object's tags without
+// parsing HTTP:
+//   [0x02 | u8 ntags | ntags x u64 little-endian tag hash] [the payload as without tags]
+// The proxy's untagged payloads start with "HTTP/" or the Vary marker's 0x01, never 0x02.
+// Tag hash = digest_bytes(tag).lo; a colliding hash purges one object too many (a miss, never
+// a wrong answer). ntags == kTagOverflow: no hashes follow and the object matches every tag
+// purge (the response named more than kMaxObjectTags distinct tags; dropping some silently
+// would leave stale objects). ntags in 33..254 is malformed, a block whose hashes do not fit
+// is truncated: both match nothing and are not stripped. No padding: inside a keyed value
+// the block sits at byte 2 + klen, so the hashes have any byte alignment.
+constexpr uint8_t kTagMarker = 0x02;
+constexpr unsigned kMaxObjectTags = 32;
+constexpr unsigned kTagOverflow = 0xff;
+constexpr unsigned kMaxPurgeTags = 64;  // hashes in one purge's list
+
+inline uint64_t tag_hash(const char* tag, size_t n) {
+  return digest_bytes(reinterpret_cast<const uint8_t*>(tag), n).lo;
+}
+inline uint64_t tag_hash(const std::string& tag) { return tag_hash(tag.data(), tag.size()); }
+
+// Bytes of the block for `ntags` distinct tags (more than kMaxObjectTags: the overflow block).
+inline size_t tag_block_size(size_t ntags) { return 2 + (ntags > kMaxObjectTags ? 0 : 8 * ntags); }
+
+// Writes the block for hashes[0..ntags) (distinct) at dst; returns tag_block_size(ntags).
+inline size_t write_tag_block(uint8_t* dst, const uint64_t* hashes, size_t ntags) {
+  dst[0] = kTagMarker;
+  if (ntags > kMaxObjectTags) {
+    dst[1] = (uint8_t)kTagOverflow;
+    return 2;
+  }
+  dst[1] = (uint8_t)ntags;
+  for (size_t i = 0; i < ntags; ++i) {
+    uint64_t h = hashes[i];
+    for (int b = 0; b < 8; ++b, h >>= 8) dst[2 + 8 * i + b] = (uint8_t)h;
+  }
+  return 2 + 8 * ntags;
+}
+
+// Hash i of a parsed block: `hashes` has no alignment, so it is never dereferenced.
+inline uint64_t tag_block_hash(const uint64_t* hashes, unsigned i) {
+  const uint8_t* const p = reinterpret_cast<const uint8_t*>(hashes) + 8 * (size_t)i;
+  uint64_t h = 0;
+  for (int b = 7; b >= 0; --b) h = (h << 8) | p[b];
+  return h;
+}
+
+// Parses the tag block at the start of payload[0..n). Returns the bytes to strip to reach
+// the plain payload; 0: untagged (no marker, or a malformed or truncated block, which matches
+// nothing). *hashes points at the *ntags stored hashes (unaligned: read them with
+// tag_block_hash); *overflow: the object matches every tag purge (*ntags is 0 then).
+inline size_t parse_tag_block(const char* payload, size_t n, const uint64_t** hashes,
+                              unsigned* ntags, bool* overflow) {
+  *hashes = nullptr;
+  *ntags = 0;
+  *overflow = false;
+  if (n < 2 || (uint8_t)payload[0] != kTagMarker) return 0;
+  const unsigned nt = (uint8_t)payload[1];
+  if (nt == kTagOverflow) {
+    *overflow = true;
+    return 2;
+  }
+  if (nt > kMaxObjectTags || 2 + 8 * (size_t)nt > n) return 0;
+  *hashes = reinterpret_cast<const uint64_t*>(payload + 2);
+  *ntags = nt;
+  return 2 + 8 * (size_t)nt;
+}
+
+// Whether the payload's tag block matches a purge of list[0..nlist).
+inline bool tag_block_matches(const char* payload, size_t n, const uint64_t* list, size_t nlist) {
+  const uint64_t* hs;
+  unsigned nt;
+  bool over;
+  if (!parse_tag_block(payload, n, &hs, &nt, &over)) return false;
+  if (over) return true;
+  for (unsigned i = 0; i < nt; ++i) {
+    const uint64_t h = tag_block_hash(hs, i);
+    for (size_t j = 0; j < nlist; ++j)
+      if (list[j] == h) return true;
+  }
+  return false;
+}
+
+// The same for a whole keyed value [u16 klen | key | payload].
+inline bool keyed_tags_match(const uint8_t* v, size_t vlen, const uint64_t* list, size_t nlist) {
+  if (vlen < kKeyedPrefix + 2) return false;
+  uint16_t kl;
+  std::memcpy(&kl, v, kKeyedPrefix);
+  const size_t o = kKeyedPrefix + kl;
+  if (o + 2 > vlen) return false;
+  return tag_block_matches(reinterpret_cast<const char*>(v) + o, vlen - o, list, nlist);
 }
 
 }  // namespace shellac

@@ -56,6 +56,11 @@ class ObjectCache {
   // Returns the live matching objects, whether or not their words changed.
   uint64_t soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
                          uint32_t expire_cap, uint32_t now);
+  // Purge / soft purge by surrogate key: the same walks with the tag matcher of keyed.h
+  // (keyed_tags_match) on the stored value; `hashes` holds 1..kMaxPurgeTags tag hashes.
+  uint64_t purge_tags(const std::vector<uint64_t>& hashes, uint32_t now);
+  uint64_t soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t expire_cap,
+                       uint32_t now);
   void clear();
   ObjectCacheStats stats() const;
 

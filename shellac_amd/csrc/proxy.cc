@@ -21,6 +21,7 @@
 #include <unordered_map>
 
 #include "http.h"
+#include "keyed.h"
 
 namespace shellac {
 
@@ -267,6 +268,9 @@ struct Pend {
   // that was served stale, `marker` its URL's Vary marker (null: the key is the URL's).
   bool reval = false;
   Bytes stale, marker;
+  // `stale` as the tier holds it, with its tag block (null: it has none): what a
+  // revalidation stores again
+  Bytes stale_raw;
 };
 
 struct Upstream : Conn {
@@ -302,7 +306,8 @@ class Reactor : public Executor {
       streamed{0}, stream_pauses{0}, gzip_gpu_bodies{0}, gzip_gpu_inflated{0}, identity_decoded{0},
       vary_stored{0},
       vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0},
-      soft_purge_requests{0}, softened_objects{0};
+      soft_purge_requests{0}, softened_objects{0}, tag_purge_requests{0},
+      tag_purged_objects{0}, tag_softened_objects{0}, tagged_fills{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -327,6 +332,8 @@ class Reactor : public Executor {
   void on_purge(Client* c, Slot* s, const std::string& key, bool prefix, bool soft);
   void hard_purge(uint64_t cid, uint64_t seq, const std::string& key, bool prefix,
                   bool soft_asked);
+  void on_purge_tags(Client* c, Slot* s, const std::string* list, bool soft);
+  void hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes, bool soft_asked);
   void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                     const std::string& body);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
@@ -348,7 +355,7 @@ class Reactor : public Executor {
   int choose_server();
   // --grace (ProxyConfig::grace)
   uint32_t grace_for(const HttpParser& r) const;
-  void revalidate(Slot* s, const Bytes& stale);
+  void revalidate(Slot* s, const Bytes& stale, const Bytes& raw);
   void revalidation_answered(HttpParser& r, const Pend& p);
   void revalidation_failed(const Pend& p);
   // keys whose revalidation failed: no new attempt before this time (upstream_retry_s)
@@ -687,6 +694,11 @@ void Reactor::on_request(Client* c) {
     const bool prefix = mode && to_lower(*mode) == "prefix";
     const std::string* soft = q.header("x-purge-soft");
     c->slots.push_back(std::move(s));
+    if (mode && to_lower(*mode) == "tag") {
+      const std::string* list = cfg_.tag_header.empty() ? nullptr : q.header(cfg_.tag_header);
+      on_purge_tags(c, sp, list, soft && *soft == "1");
+      return;
+    }
     on_purge(c, sp, key, prefix, soft && *soft == "1");
     return;
   }
@@ -805,6 +817,89 @@ void Reactor::hard_purge(uint64_t cid, uint64_t seq, const std::string& key, boo
   });
 }
 
+// The distinct tags of a tag header's value: split on space, tab and comma, empty tokens
+// dropped, duplicates collapsed; as hashes (keyed.h tag_hash), in order of first appearance.
+static std::vector<uint64_t> tag_hashes_of(const std::string& value) {
+  std::vector<uint64_t> out;
+  size_t pos = 0;
+  while (pos < value.size()) {
+    const size_t e = std::min(value.find_first_of(" \t,", pos), value.size());
+    if (e > pos) {
+      const uint64_t h = tag_hash(value.data() + pos, e - pos);
+      if (std::find(out.begin(), out.end(), h) == out.end()) out.push_back(h);
+    }
+    pos = e + 1;
+  }
+  return out;
+}
+
+// PURGE with X-Purge-Mode: tag. The tags come from the request's header named by
+// ProxyConfig::tag_header (`list`; null: no such header, or the option is off); the URL is
+// ignored. Every object stored behind a tag block that names one of them goes (or, with
+// X-Purge-Soft: 1 and --grace, is made stale: CacheBackend::soften_tags), on the same terms
+// as a prefix purge: the loopback rule, note_purge before the tier is touched, the hard
+// fallback answered with "soft":false, 501 from a tier that cannot scan.
+void Reactor::on_purge_tags(Client* c, Slot* s, const std::string* list, bool soft) {
+  const uint64_t cid = c->id, seq = s->seq;
+  if (!purge_allowed(cfg_.purge, c->loopback)) {
+    purge_denied++;
+    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
+    return;
+  }
+  purge_requests++;
+  if (cfg_.tag_header.empty()) {
+    answer_purge(cid, seq, 400, "Bad Request",
+                 "{\"mode\":\"tag\",\"error\":\"no tag header is configured\"}");
+    return;
+  }
+  std::vector<uint64_t> hashes = list ? tag_hashes_of(*list) : std::vector<uint64_t>();
+  if (hashes.empty() || hashes.size() > kMaxPurgeTags) {
+    answer_purge(cid, seq, 400, "Bad Request",
+                 std::string("{\"mode\":\"tag\",\"error\":\"") +
+                     (hashes.empty() ? "the request names no tags" : "more than 64 tags") + "\"}");
+    return;
+  }
+  CacheBackend* be = px_->backend_.get();
+  if (!be || !px_->cfg_.cache_enabled) {
+    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
+    return;
+  }
+  tag_purge_requests++;
+  px_->note_purge_tags(hashes);  // before the tier is touched: fills in flight are refused
+  if (!soft || !cfg_.grace) {
+    hard_purge_tags(cid, seq, std::move(hashes), soft);
+    return;
+  }
+  be->soften_tags(hashes, unix_now(), cfg_.grace, this, [this, cid, seq, hashes](int64_t n) {
+    if (n < 0) {
+      hard_purge_tags(cid, seq, hashes, true);
+      return;
+    }
+    tag_softened_objects += (uint64_t)n;
+    answer_purge(cid, seq, 200, "OK",
+                 "{\"mode\":\"tag\",\"soft\":true,\"tags\":" + std::to_string(hashes.size()) +
+                     ",\"softened\":" + std::to_string(n) + "}");
+  });
+}
+
+void Reactor::hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes,
+                              bool soft_asked) {
+  const std::string mode =
+      std::string("{\"mode\":\"tag\",") + (soft_asked ? "\"soft\":false," : "");
+  const size_t nt = hashes.size();
+  px_->backend_->purge_tags(hashes, this, [this, cid, seq, mode, nt](int64_t n) {
+    if (n < 0) {
+      answer_purge(cid, seq, 501, "Not Implemented",
+                   mode + "\"error\":\"the cache tier cannot scan its keys\"}");
+      return;
+    }
+    tag_purged_objects += (uint64_t)n;
+    answer_purge(cid, seq, 200, "OK",
+                 mode + "\"tags\":" + std::to_string(nt) + ",\"purged\":" + std::to_string(n) +
+                     "}");
+  });
+}
+
 void Reactor::answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                            const std::string& body) {
   Client* c = find_client(cid);
@@ -820,6 +915,18 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
   if (!c) return;
   Slot* s = find_slot(c, seq);
   if (!s || s->ready) return;
+  // A value stored behind a tag block (whether or not --tag-header is set now): everything
+  // below sees the plain object, a zero-copy slice; `raw` is what a revalidation stores again
+  Bytes raw;
+  if (hit && v.data && v.data->size() && (uint8_t)v.data->data()[0] == kTagMarker) {
+    const uint64_t* hs;
+    unsigned nt;
+    bool over;
+    if (const size_t strip = parse_tag_block(v.data->data(), v.data->size(), &hs, &nt, &over)) {
+      raw = v.data;
+      v.data = raw.sub(strip, raw->size() - strip);
+    }
+  }
   if (hit && v.data && is_vary_marker(v.data->view())) {
     // the URL's responses Vary: look the variant of this request up under its own key
     // (a marker found by a variant lookup, or without the request, counts as a miss)
@@ -842,7 +949,7 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
     // revalidated in the background (before deliver(): that gives the parsed request back)
     if (cfg_.grace && v.flags && unix_now() >= v.flags) {
       stale_served++;
-      revalidate(s, v.data);
+      revalidate(s, v.data, raw);
     }
     deliver(c, s, v.data);
     return;
@@ -1167,7 +1274,7 @@ uint32_t Reactor::grace_for(const HttpParser& r) const {
 // hits are simply served stale — or the last one failed less than upstream_retry_s ago.
 // The request is the client's own (so a Vary'd variant is asked for with its headers), made
 // conditional on the stored object's validators; it holds no client slot.
-void Reactor::revalidate(Slot* s, const Bytes& stale) {
+void Reactor::revalidate(Slot* s, const Bytes& stale, const Bytes& raw) {
   if (!s->req || s->req->method() != "GET" || inflight_.count(s->key)) return;
   const double t = now_s();
   const auto back = reval_retry_at_.find(s->key);
@@ -1181,6 +1288,7 @@ void Reactor::revalidate(Slot* s, const Bytes& stale) {
     p.req_headers = std::make_shared<const std::vector<Header>>(q.headers());
   p.reval = true;
   p.stale = stale;
+  p.stale_raw = raw;
   p.marker = s->vary_marker;
   // the stored validators replace whatever conditions the client sent
   for (const char* h : {"if-none-match", "if-modified-since", "if-match", "if-unmodified-since",
@@ -1234,7 +1342,16 @@ void Reactor::revalidation_answered(HttpParser& r, const Pend& p) {
     return;
   }
   revalidated_304++;
-  if (px_->purged_since(p.purge_gen, p.key, p.base_key)) {
+  // (the stored object's tags: a 304's own tag header is ignored, as its other headers are)
+  std::vector<uint64_t> tags;
+  bool tagged = false, over = false;
+  if (p.stale_raw) {
+    const uint64_t* hs;
+    unsigned nt;
+    tagged = parse_tag_block(p.stale_raw->data(), p.stale_raw->size(), &hs, &nt, &over) != 0;
+    for (unsigned i = 0; i < nt; ++i) tags.push_back(tag_block_hash(hs, i));
+  }
+  if (px_->purged_since(p.purge_gen, p.key, p.base_key, tagged ? &tags : nullptr, over)) {
     fills_purged++;
     release_waiters(p.key, nullptr);
     return;
@@ -1260,7 +1377,7 @@ void Reactor::revalidation_answered(HttpParser& r, const Pend& p) {
   if (p.marker && p.key != p.base_key)
     extend(p.base_key, digest_bytes(reinterpret_cast<const uint8_t*>(p.base_key.data()),
                                     p.base_key.size()), p.marker, false);
-  extend(p.key, p.d, p.stale, true);
+  extend(p.key, p.d, p.stale_raw ? p.stale_raw : p.stale, true);  // (stored with its tag block)
   reval_retry_at_.erase(p.key);
   release_waiters(p.key, p.stale);
 }
@@ -1531,9 +1648,21 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
     // fresh (0 with grace off: stored exactly as without the option)
     const uint32_t grace = grace_for(r), hard_ttl = ttl + grace;
     const uint32_t fresh_until = grace ? unix_now() + ttl : 0;
-    if (px_->purged_since(p.purge_gen, p.key, p.base_key)) {
-      // fetched before a purge of this key: delivered (the collapsed waiters share it as
-      // they would have), not stored
+    // --tag-header: the response's tags; the stored value is the tag block, then the object
+    std::vector<uint64_t> tags;
+    const std::string* th = cfg_.tag_header.empty() ? nullptr : r.header(cfg_.tag_header);
+    if (th) tags = tag_hashes_of(*th);
+    const bool tagged = !tags.empty(), over = tags.size() > kMaxObjectTags;
+    Bytes stored = obj;
+    if (tagged) {
+      auto v = std::make_shared<std::string>(tag_block_size(tags.size()), '\0');
+      write_tag_block(reinterpret_cast<uint8_t*>(&(*v)[0]), tags.data(), tags.size());
+      v->append(obj->data(), obj->size());
+      stored = std::shared_ptr<const std::string>(std::move(v));
+    }
+    if (px_->purged_since(p.purge_gen, p.key, p.base_key, tagged ? &tags : nullptr, over)) {
+      // fetched before a purge of this key (or of one of its tags): delivered (the collapsed
+      // waiters share it as they would have), not stored
       fills_purged++;
       cached = true;
       if (!vnames.empty())
@@ -1542,8 +1671,9 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
     } else if (vnames.empty()) {
       cached = true;
       // Server.py:432 mc.set(key, obj, time=ttl)
-      px_->backend_->set(p.key, p.d, obj, fresh_until, hard_ttl);
+      px_->backend_->set(p.key, p.d, stored, fresh_until, hard_ttl);
       cache_sets++;
+      if (tagged) tagged_fills++;
     } else if (vnames[0] != "*" && p.req_headers) {
       // Vary: marker under the URL key, the object under this request's variant key
       const std::string vk = vary_key(p.base_key, vnames, *p.req_headers);
@@ -1554,8 +1684,9 @@ void Reactor::finish_response(HttpParser& r, const Pend& p) {
       const Digest vd = digest_bytes(reinterpret_cast<const uint8_t*>(vk.data()), vk.size());
       px_->backend_->set(p.base_key, bd, std::make_shared<const std::string>(std::move(marker)),
                          fresh_until, hard_ttl);
-      px_->backend_->set(vk, vd, obj, fresh_until, hard_ttl);
+      px_->backend_->set(vk, vd, stored, fresh_until, hard_ttl);  // (the marker gets no block)
       cache_sets++;
+      if (tagged) tagged_fills++;
       vary_stored++;
       cached = true;
       // requests collapsed onto the URL key may carry other header values: they fetch
@@ -1706,6 +1837,7 @@ void Reactor::gc() {
 Proxy::Proxy(const ProxyConfig& cfg, std::shared_ptr<CacheBackend> backend)
     : cfg_(cfg), backend_(std::move(backend)) {
   SH_CHECK(!cfg_.upstreams.empty(), "no upstream web servers specified");
+  cfg_.tag_header = to_lower(cfg_.tag_header);  // (parsed header names are lower case)
   SH_CHECK(cfg_.threads >= 1, "threads >= 1");
   if (cfg_.cache_enabled) SH_CHECK(backend_ != nullptr, "cache enabled without a backend");
   up_down_until_.reset(new std::atomic<double>[cfg_.upstreams.size()]);
@@ -1927,16 +2059,39 @@ void Proxy::note_purge(const std::string& pattern, bool prefix) {
   r.gen = gen;
   r.pattern = pattern;
   r.prefix = prefix;
+  r.by_tag = false;
+  r.tags.clear();
   purge_gen_.store(gen, std::memory_order_release);
 }
 
-bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string& base_key) {
+void Proxy::note_purge_tags(const std::vector<uint64_t>& hashes) {
+  std::lock_guard<std::mutex> lk(purge_mu_);
+  if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
+  const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
+  PurgeRec& r = purge_ring_[gen % kPurgeRing];
+  r.gen = gen;
+  r.pattern.clear();
+  r.prefix = false;
+  r.by_tag = true;
+  r.tags = hashes;
+  purge_gen_.store(gen, std::memory_order_release);
+}
+
+bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string& base_key,
+                         const std::vector<uint64_t>* tags, bool overflow) {
   if (purge_gen_.load(std::memory_order_acquire) == gen) return false;  // the common case
   std::lock_guard<std::mutex> lk(purge_mu_);
   const uint64_t cur = purge_gen_.load(std::memory_order_relaxed);
   if (cur - gen > kPurgeRing) return true;  // the ring wrapped past this fetch: assume purged
   for (uint64_t g = gen + 1; g <= cur; ++g) {
     const PurgeRec& r = purge_ring_[g % kPurgeRing];
+    if (r.by_tag) {
+      if (!tags) continue;
+      if (overflow) return true;
+      for (uint64_t h : *tags)
+        if (std::find(r.tags.begin(), r.tags.end(), h) != r.tags.end()) return true;
+      continue;
+    }
     if (r.prefix ? key.compare(0, r.pattern.size(), r.pattern) == 0 : base_key == r.pattern)
       return true;
   }
@@ -1947,7 +2102,7 @@ std::string Proxy::stats_json() {
   uint64_t req = 0, hit = 0, miss = 0, ur = 0, resp = 0, bo = 0, err = 0, cl = 0, up = 0, acc = 0,
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
-           sob = 0;
+           sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0;
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -1966,6 +2121,8 @@ std::string Proxy::stats_json() {
     prq += r->purge_requests; pob += r->purged_objects; pdn += r->purge_denied;
     fpg += r->fills_purged;
     spr += r->soft_purge_requests; sob += r->softened_objects;
+    tpr += r->tag_purge_requests; tpo += r->tag_purged_objects;
+    tso += r->tag_softened_objects; tgf += r->tagged_fills;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -1997,6 +2154,8 @@ std::string Proxy::stats_json() {
     << ",\"purge_requests\":" << prq << ",\"purged_objects\":" << pob
     << ",\"purge_denied\":" << pdn << ",\"fills_not_cached_purged\":" << fpg
     << ",\"soft_purge_requests\":" << spr << ",\"softened_objects\":" << sob
+    << ",\"tag_purge_requests\":" << tpr << ",\"tag_purged_objects\":" << tpo
+    << ",\"tag_softened_objects\":" << tso << ",\"tagged_fills\":" << tgf
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
     << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]

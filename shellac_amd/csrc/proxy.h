@@ -68,6 +68,15 @@ struct ProxyConfig {
   // (CacheBackend::soften_prefix; their lives capped at now + grace, never extended);
   // without grace, or where the tier cannot, it is a hard purge answered with "soft":false.
   std::string purge = "off";
+  // Purge by surrogate key (Varnish xkey, Fastly Surrogate-Key, Cloudflare Cache-Tag): the
+  // name of the response header that lists an object's tags, separated by spaces, tabs or
+  // commas; empty (the default) turns the feature off. A response that carries it is stored
+  // behind a tag block (keyed.h; more than 32 distinct tags: the overflow block) and the
+  // header is passed on as it is. `PURGE` with `X-Purge-Mode: tag` takes 1..64 tags from the
+  // request's header of this name (the URL is ignored) and removes every object that
+  // carries one of them; with `X-Purge-Soft: 1` and grace they are made stale instead. A
+  // stored tag block is stripped from a hit whether or not the option is set.
+  std::string tag_header;
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
   bool key_host = false;
@@ -130,9 +139,14 @@ class Proxy {
   static constexpr size_t kPurgeRing = 64;
   uint64_t purge_generation() const { return purge_gen_.load(std::memory_order_acquire); }
   void note_purge(const std::string& pattern, bool prefix);
+  void note_purge_tags(const std::vector<uint64_t>& hashes);
   // `key`: the key the object would be stored under; `base_key`: its URL key (an exact
   // purge of the URL covers every variant)
-  bool purged_since(uint64_t gen, const std::string& key, const std::string& base_key);
+  // `tags`: the object's tag hashes (null: it has none), `overflow`: it named too many — a
+  // tag purge since `gen` that names one of them, or any tag purge for an overflowing
+  // object, refuses the fill as a key purge does
+  bool purged_since(uint64_t gen, const std::string& key, const std::string& base_key,
+                    const std::vector<uint64_t>* tags = nullptr, bool overflow = false);
 
  private:
   friend class Reactor;
@@ -155,6 +169,8 @@ class Proxy {
     uint64_t gen = 0;
     std::string pattern;
     bool prefix = false;
+    bool by_tag = false;  // a tag purge: `tags` holds its hashes, the pattern is unused
+    std::vector<uint64_t> tags;
   };
   std::atomic<uint64_t> purge_gen_{0};
   std::mutex purge_mu_;

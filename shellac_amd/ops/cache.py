@@ -99,6 +99,36 @@ def keyed(key: bytes, payload: bytes) -> bytes:
     return core().keyed(bytes(key), bytes(payload))
 
 
+MAX_OBJECT_TAGS = 32  # keyed.h kMaxObjectTags
+MAX_PURGE_TAGS = 64  # keyed.h kMaxPurgeTags
+
+
+def tag_hash(tag: bytes) -> int:
+    """Hash of one surrogate key (``csrc/keyed.h`` ``tag_hash``): the low word of the tag's
+    digest. Tags are case-sensitive byte strings."""
+    return int(core().tag_hash(bytes(tag)))
+
+
+def tagged(tags: Iterable[bytes], payload: bytes) -> bytes:
+    """``payload`` behind the tag block ``[0x02 | u8 ntags | ntags x u64 LE hash]`` of its
+    distinct ``tags`` (``write_tag_block``); more than 32 distinct tags give the overflow
+    block ``[0x02 | 0xff]``, which every tag purge matches. Goes into ``keyed`` as the
+    payload."""
+    hashes = list(dict.fromkeys(tag_hash(t) for t in tags))
+    return core().tag_block(hashes) + bytes(payload)
+
+
+def split_tagged(value: bytes):
+    """``(hashes | "overflow" | None, payload)`` of a payload as stored (``parse_tag_block``):
+    ``None`` for an untagged payload and for a malformed or truncated block, which are left
+    as they are."""
+    value = bytes(value)
+    strip, hashes, overflow = core().parse_tag_block(value)
+    if not strip:
+        return None, value
+    return ("overflow" if overflow else [int(h) for h in hashes]), value[strip:]
+
+
 def unpack_records(out: torch.Tensor, off: torch.Tensor, size: torch.Tensor) -> list:
     """Decode GET output ([ItemHeader | value | pad] per hit) -> list of (value, flags) or None."""
     o = out.cpu().numpy()
@@ -711,6 +741,49 @@ class CacheShard:
         out = torch.empty(1, dtype=torch.int64, device=self.device)
         self._impl.soften_keyed_prefix(image.data_ptr(), len(prefix), bool(exact), stale_at,
                                        expire_cap, now, out.data_ptr(), self._s())
+        return int(out.item())  # (waits for the stream)
+
+    @staticmethod
+    def _tag_list(tags: Sequence[bytes]) -> list[int]:
+        tags = [bytes(t) for t in tags]
+        if not 1 <= len(tags) <= MAX_PURGE_TAGS:
+            raise ValueError("tag purge takes 1..64 tags")
+        return [tag_hash(t) for t in tags]
+
+    def remove_keyed_tags(self, tags: Sequence[bytes],
+                          now: Optional[int] = None) -> tuple[int, int]:
+        """Purge by surrogate key: removes every live object whose stored keyed value carries
+        a tag block (``tagged``) naming one of ``tags`` (1..64 byte strings), or the overflow
+        block. Returns ``(objects removed, their item bytes)``; synchronises, like
+        ``remove_keyed_prefix``. On a GPU shard ``k_purge_tags`` does the scan."""
+        hashes = self._tag_list(tags)
+        now = self.now() if now is None else now
+        if not self.is_gpu:
+            removed, nbytes = self._impl.remove_keyed_tags(hashes, now)
+            return int(removed), int(nbytes)
+        lst = torch.from_numpy(np.array(hashes, dtype=np.uint64).view(np.int64)).to(self.device)
+        out = torch.empty(2, dtype=torch.int64, device=self.device)
+        self._impl.remove_keyed_tags(lst.data_ptr(), len(hashes), now, out.data_ptr(), self._s())
+        removed, nbytes = out.tolist()  # (waits for the stream)
+        return int(removed), int(nbytes)
+
+    def soften_keyed_tags(self, tags: Sequence[bytes], stale_at: int, expire_cap: int = 0,
+                          now: Optional[int] = None) -> int:
+        """Soft purge by surrogate key: ``remove_keyed_tags``' matcher with
+        ``soften_keyed_prefix``'s action and contract (``flags = stale_at``, the expiry capped
+        at ``expire_cap`` and never extended, the count of live matches). Synchronises; on a
+        GPU shard ``k_soften_tags`` does the scan."""
+        hashes = self._tag_list(tags)
+        now = self.now() if now is None else now
+        stale_at, expire_cap = int(stale_at) & 0xFFFFFFFF, int(expire_cap)
+        if expire_cap and expire_cap <= now:
+            raise ValueError("soft purge: the expiry cap must lie after now")
+        if not self.is_gpu:
+            return int(self._impl.soften_keyed_tags(hashes, stale_at, expire_cap, now))
+        lst = torch.from_numpy(np.array(hashes, dtype=np.uint64).view(np.int64)).to(self.device)
+        out = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._impl.soften_keyed_tags(lst.data_ptr(), len(hashes), stale_at, expire_cap, now,
+                                     out.data_ptr(), self._s())
         return int(out.item())  # (waits for the stream)
 
     def sweep(self, now: Optional[int] = None) -> tuple[int, int]:

@@ -156,7 +156,7 @@ class Server:
                  cpus: Sequence[int] = (), spin_us: int = 0, gzip_gpu: int = -1,
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
                  max_inflate_bytes: int = 64 << 20, purge: str = "off", grace: int = 0,
-                 **backend_opts):
+                 tag_header: str = "", **backend_opts):
         """``grace`` (seconds, 0 = off): keep cached objects that long past their TTL; a hit
         in that window is served stale at once while one background request per key
         revalidates it upstream (``If-None-Match`` / ``If-Modified-Since``) — a 304 extends
@@ -171,7 +171,14 @@ class Server:
         the next request is served from the stale copy and revalidated in the background,
         and their lives are capped at ``grace`` seconds from now (never extended). Without
         ``grace``, or on a tier that cannot (memcached), it is a hard purge and the answer
-        says ``"soft":false``."""
+        says ``"soft":false``.
+
+        ``tag_header`` (empty = off): the response header that lists an object's surrogate
+        keys, e.g. ``Surrogate-Key``, ``xkey`` or ``Cache-Tag`` (separated by spaces, tabs or
+        commas). ``PURGE`` with ``X-Purge-Mode: tag`` and that header naming 1..64 tags
+        removes every object carrying one of them, whatever its URL (on the HBM tier:
+        ``k_purge_tags``); with ``X-Purge-Soft: 1`` and ``grace`` they are made stale
+        instead. A response naming more than 32 distinct tags matches every tag purge."""
         if purge not in ("off", "loopback", "any"):
             raise ValueError("purge must be 'off', 'loopback' or 'any'")
         if not servers:
@@ -193,7 +200,7 @@ class Server:
             health_fails=health_fails, cpus=[int(c) for c in cpus], spin_us=int(spin_us),
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
             max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
-            purge=purge, grace=int(grace))
+            purge=purge, grace=int(grace), tag_header=str(tag_header or ""))
         self._started = False
 
     @property
@@ -301,6 +308,12 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "'X-Purge-Soft: 1' and --grace the objects are kept and made stale "
                         "instead (served at once, revalidated in the background, gone at most "
                         "--grace seconds later)")
+    p.add_argument("--tag-header", default="", metavar="NAME",
+                   help="purge by surrogate key: the response header that lists an object's "
+                        "tags (e.g. Surrogate-Key, xkey, Cache-Tag; separated by spaces, tabs or "
+                        "commas). 'PURGE' with 'X-Purge-Mode: tag' and 'NAME: t1 t2' drops every "
+                        "object carrying one of up to 64 tags (with 'X-Purge-Soft: 1' and "
+                        "--grace: makes them stale). Default: off")
     p.add_argument("--grace", type=int, default=0, metavar="S",
                    help="serve cached objects up to S seconds past their TTL while one "
                         "background request per key revalidates them upstream (If-None-Match / "
@@ -358,7 +371,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  cpus=parse_cpus(args.cpus), spin_us=args.spin_us,
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
                  max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
-                 grace=args.grace,
+                 grace=args.grace, tag_header=args.tag_header,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,

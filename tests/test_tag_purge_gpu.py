@@ -1,0 +1,273 @@
+"""Purge by surrogate key on the GPU: k_purge_tags / k_soften_tags against the host twin and
+the Python model, the HBM backend's tag purge request, hot replicas, a shard out of service,
+and the proxy's --tag-header over the HBM tier."""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+import purge_cases as pc
+import soften_cases as sc
+import tag_cases as tg
+from shellac_amd import core
+from shellac_amd.ops.cache import keyed, split_tagged, tag_hash, tagged
+from shellac_amd.server.proxy import Server, hot_refresh, make_backend
+
+pytestmark = pytest.mark.gpu
+
+T0 = tg.T0
+
+
+# ------------------------------------------------------------------- twins and the model
+def test_twin_alignment_sweep(cuda_dev):
+    tg.run_alignment_sweep([cuda_dev, "cpu"])
+
+
+def test_twin_block_forms(cuda_dev):
+    tg.run_block_forms([cuda_dev, "cpu"])
+
+
+def test_twin_garbage_values(cuda_dev):
+    tg.run_garbage([cuda_dev, "cpu"])
+
+
+def test_twin_near_misses_list_sizes_and_refused_lists(cuda_dev):
+    tg.run_near_misses([cuda_dev, "cpu"])
+
+
+def test_twin_tagged_families(cuda_dev):
+    tg.run_families([cuda_dev, "cpu"])
+
+
+def test_twin_after_the_log_lapped(cuda_dev):
+    tg.run_after_the_log_lapped([cuda_dev, "cpu"])
+
+
+def test_expired_entries_are_not_counted(cuda_dev):
+    tg.run_expired_are_not_counted([cuda_dev])
+
+
+def test_dead_same_digest_entry_and_locked_slot_are_left_alone(cuda_dev):
+    tg.run_dead_entries([cuda_dev])
+
+
+def test_twin_soft_form_over_expiries_and_caps(cuda_dev):
+    tg.run_soft_form([cuda_dev, "cpu"])
+
+
+def test_reference_bit_survives_a_tag_softening(cuda_dev):
+    tg.run_reference_bit([cuda_dev])
+
+
+def test_soften_is_refused_while_a_phase1_batch_is_pending(cuda_dev):
+    tg.run_refused_while_phase1_pending([cuda_dev])
+
+
+def test_twin_clock_hand_keeps_the_tags(cuda_dev):
+    g = tg.clock_keeps_the_tags(pc.make_shard(cuda_dev))
+    h = tg.clock_keeps_the_tags(pc.make_shard("cpu"))
+    assert g == h
+    alive, n, left, reinserted = g
+    assert alive == n == 20 and left == 0 and reinserted >= 20
+
+
+def test_clock_hand_does_not_resurrect_tag_purged_objects(cuda_dev):
+    assert tg.clock_never_resurrects(pc.make_shard(cuda_dev))["purged"] == 150
+
+
+def test_twin_clock_hand_keeps_the_tag_softening(cuda_dev):
+    g = tg.clock_keeps_the_softening(pc.make_shard(cuda_dev))
+    h = tg.clock_keeps_the_softening(pc.make_shard("cpu"))
+    assert g == h
+    meta, live_at_cap, reinserted = g
+    assert len(meta) == 20 and reinserted >= 20 and live_at_cap == set()
+    assert set(meta.values()) == {(sc.STALE_AT, T0 + sc.TTL0)}
+
+
+def test_tag_purge_beside_sets_on_a_second_stream(cuda_dev):
+    """test_purge_beside_sets_on_a_second_stream with the tag matcher: a tag purge on one
+    stream while SET batches on another append to the log, lapping it (FIFO, so the twin
+    tells exactly which records get overwritten): memory-safe through the header re-check,
+    and no object without the tag is lost."""
+    base = tg.tagged_families(2000, seed=5)
+    fills = [{b"/fill/%d/%d" % (b, i): keyed(b"/fill/%d/%d" % (b, i), b"f" * 600)
+              for i in range(400)} for b in range(3)]
+    g, h = tg.make_shards([cuda_dev, "cpu"], base, evict="fifo", nbuckets=1 << 11)
+    s1, s2 = torch.cuda.Stream(cuda_dev), torch.cuda.Stream(cuda_dev)
+    tag = b"fam:/static/"
+    lst = torch.from_numpy(np.array([tag_hash(tag)], dtype=np.uint64).view(np.int64)).to(cuda_dev)
+    out = torch.zeros(2, dtype=torch.int64, device=cuda_dev)
+    torch.cuda.synchronize(cuda_dev)
+    with torch.cuda.stream(s2):
+        pc.store(g, fills[0], batch=400)
+    with torch.cuda.stream(s1):
+        g._impl.remove_keyed_tags(lst.data_ptr(), 1, g.now(), out.data_ptr(), s1.cuda_stream)
+    with torch.cuda.stream(s2):
+        for f in fills[1:]:
+            pc.store(g, f, batch=400)
+    torch.cuda.synchronize(cuda_dev)
+    for f in fills:
+        pc.store(h, f, batch=400)
+    assert g.head() == h.head() > g.log_bytes
+    hs = {tag_hash(tag)}
+    must_survive = {k for k in tg.live_values(h, base) if not tg.value_matches(base[k], hs)}
+    assert must_survive
+    live = tg.live_values(g, {**base, **fills[-1]})
+    assert must_survive <= set(live) and set(fills[-1]) <= set(live)
+    assert all(live[k] == base[k] for k in must_survive)
+    removed = int(out[0].item())
+    assert 0 <= removed <= sum(tg.value_matches(v, hs) for v in base.values())
+    assert g.counters()["purged"] == removed
+
+
+# ------------------------------------------------------------------------------ HbmBackend
+def _wait_get(be, key, timeout=5.0):
+    deadline = time.time() + timeout
+    while time.time() < deadline:
+        r = be.get(key)
+        if r is not None:
+            return r
+        time.sleep(0.005)
+    return None
+
+
+def _ttl_near(got, want):
+    return got is not None and want - 3 <= got[2] <= want
+
+
+def _val(k, tags):
+    return tagged(tags, b"HTTP/ value of " + k * 5)
+
+
+@pytest.mark.parametrize("edge_server", [True, False])
+def test_hbm_backend_purge_tags(edge_server):
+    be = make_backend("hbm", gpus=[0], hbm_gb=0.25, edge_server=edge_server)
+    fam = {f: [b"/%s/%d" % (f, i) for i in range(64)] for f in (b"a", b"b")}
+    tags = {b"a": [b"x", b"y"], b"b": [b"z"]}
+    for f in fam:
+        for k in fam[f]:
+            be.set(k, _val(k, tags[f]), 0, 0)
+    plain = [b"/plain/%d" % i for i in range(8)]
+    for k in plain:
+        be.set(k, b"HTTP/ untagged " + k, 0, 0)
+    assert _wait_get(be, plain[-1]) is not None
+    assert all(v is not None for v in be.get_many(fam[b"a"] + fam[b"b"]))
+    st0 = be.stats()
+    assert be.purge_tags([b"nobody", b"y"]) == 64
+    # after `done` every GET path misses: the launched and the served / reactor-direct ones
+    for _ in range(3):
+        assert be.get_many(fam[b"a"]) == [None] * 64
+        assert all(be.get(k) is None for k in fam[b"a"][:8])
+    assert be.get_many(fam[b"b"]) == [(_val(k, tags[b"b"]), 0) for k in fam[b"b"]]
+    assert be.get_many(plain) == [(b"HTTP/ untagged " + k, 0) for k in plain]
+    assert be.purge_tags([b"y"]) == 0
+    # a SET queued behind the purge is not caught by it
+    be.set(b"/a/new", _val(b"/a/new", [b"y"]), 0, 0)
+    assert _wait_get(be, b"/a/new") == (_val(b"/a/new", [b"y"]), 0)
+    assert be.purge_tags([]) == -1 and be.purge_tags([b"t%d" % i for i in range(65)]) == -1
+    assert be.soften_tags([], 5) == -1
+    st = be.stats()
+    assert st["hbm_tag_purges"] == 2 and st["hbm_tag_purged_objects"] == 64
+    assert st["hbm_tag_softened_objects"] == 0
+    for name in ("hbm_purges", "hbm_soft_purges", "hbm_purged_objects", "hbm_purged_bytes",
+                 "hbm_softened_objects"):
+        assert st[name] == st0[name] == 0, name
+
+
+def test_hbm_backend_soften_tags_then_touch_makes_it_fresh_and_the_tags_remain():
+    be = make_backend("hbm", gpus=[0], hbm_gb=0.25)
+    a = [b"/q/a/%d" % i for i in range(64)]
+    b = [b"/q/b/%d" % i for i in range(64)]
+    for k in a:
+        be.set(k, _val(k, [b"x", b"y"]), 3, 5000)
+    for k in b:
+        be.set(k, _val(k, [b"z"]), 3, 5000)
+    # queued right behind the SETs: it runs after them on the shard's stream
+    assert be.soften_tags([b"y"], 1234, keep_s=100) == 64
+    assert be.soften_tags([b"y"], 1234, keep_s=100) == 64            # the same count again
+    for k in a:
+        got = be.get_ttl(k)
+        assert got[:2] == (_val(k, [b"x", b"y"]), 1234) and _ttl_near(got, 100), (k, got)
+    for k in b:
+        got = be.get_ttl(k)
+        assert got[:2] == (_val(k, [b"z"]), 3) and _ttl_near(got, 5000), (k, got)
+    assert be.touch(a[0], 400, flags=4321) == 1
+    got = be.get_ttl(a[0])
+    assert got[:2] == (_val(a[0], [b"x", b"y"]), 4321) and _ttl_near(got, 400)   # fresh again
+    st = be.stats()
+    assert st["hbm_tag_purges"] == 2 and st["hbm_tag_softened_objects"] == 128
+    assert st["hbm_soft_purges"] == 0 and st["hbm_softened_objects"] == 0 and st["hbm_purges"] == 0
+    assert be.purge_tags([b"x"]) == 64                                # the tags remain
+    assert be.get(a[0]) is None
+
+
+def test_tag_purge_removes_hot_replicas_on_every_shard():
+    be = core().hbm_backend([0, 0], 64 << 20, 1 << 14, 1 << 16, 0, hot_objects=64,
+                            hot_refresh_ms=0, hot_sample=1)
+    a = [b"/hp/a/%d" % i for i in range(200)]
+    b = [b"/hp/b/%d" % i for i in range(200)]
+    for k in a:
+        be.set(k, tagged([b"a"], b"v-" + k * 4), 0, 0)
+    for k in b:
+        be.set(k, tagged([b"b"], b"v-" + k * 4), 0, 0)
+    assert _wait_get(be, b[-1]) is not None and _wait_get(be, a[-1]) is not None
+    hot = a[:16] + b[:16]
+    for _ in range(40):
+        be.get_many(hot)
+    info = hot_refresh(be)
+    assert info["hot"] >= 32 and info["spread_mask"] == 3, info
+    assert all(v is not None for v in be.get_many(hot * 8))
+    n = be.purge_tags([b"a"])
+    assert n > 200                # the owners' copies and replicas of the hot ones
+    assert be.get_many(a[:16] * 16) == [None] * 256   # every replica the spread can pick
+    assert be.get_many(a) == [None] * 200
+    assert be.get_many(b) == [(tagged([b"b"], b"v-" + k * 4), 0) for k in b]
+    st = be.stats()
+    assert st["hbm_tag_purged_objects"] == n and st["hbm_purged_objects"] == 0
+    assert st["hbm_hot_spread_gets"] > 0
+
+
+@pytest.mark.parametrize("purge_while_out", [False, True])
+def test_shard_out_of_service_during_a_tag_purge_is_flushed_on_restore(purge_while_out):
+    be = core().hbm_backend([0], 64 << 20, 1 << 14, 1 << 16, 0, flush_on_restore=False,
+                            warm_restore=False)
+    fam = {f: [b"/%s/%d" % (f, i) for i in range(32)] for f in (b"a", b"b")}
+    for f in fam:
+        for k in fam[f]:
+            be.set(k, tagged([f], b"v-" + k), 0, 0)
+    assert _wait_get(be, fam[b"b"][-1]) is not None
+    assert core().inject_shard_down(be, 0, True)
+    assert be.get(fam[b"a"][0]) is None              # out of the ring: everything misses
+    if purge_while_out:
+        assert be.purge_tags([b"a"]) == 0            # no shard in service scanned anything
+    core().inject_shard_down(be, 0, False)
+    deadline = time.time() + 5
+    while be.stats()["hbm_gpus_up"] == 0 and time.time() < deadline:
+        time.sleep(0.02)
+    assert be.stats()["hbm_gpus_up"] == 1
+    got = be.get_many(fam[b"a"] + fam[b"b"])
+    if purge_while_out:
+        assert got == [None] * 64
+    else:
+        assert got == [(tagged([k.split(b"/")[1]], b"v-" + k), 0) for k in fam[b"a"] + fam[b"b"]]
+
+
+def test_proxy_purge_by_tag_over_the_hbm_backend():
+    be = make_backend("hbm", gpus=[0], hbm_gb=0.25)
+    o = tg.TagOrigin().start()
+    try:
+        with Server([("127.0.0.1", o.port)], port=0, backend=be, threads=2, purge="loopback",
+                    tag_header=tg.TAG_HEADER) as px:
+            def settle(paths):  # the tier stores a fill a moment after the response went out
+                for p in paths:
+                    assert _wait_get(be, b"localhost" + p.encode()) is not None
+            tg.purge_by_tag_round_trip(px, o, settle)
+            st = be.stats()
+            assert st["hbm_tag_purges"] == 2 and st["hbm_tag_purged_objects"] == 4
+            assert st["hbm_purges"] == 0
+            stored = be.get(b"localhost/t/xy")[0]
+            assert split_tagged(stored)[0] == [tag_hash(b"x"), tag_hash(b"y")]
+            assert split_tagged(stored)[1].startswith(b"HTTP/1.1 200")
+    finally:
+        o.stop()
