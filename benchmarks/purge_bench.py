@@ -29,6 +29,13 @@ list of one hash no object carries matches nothing. All no-match runs, of every 
 on the full shard before anything is removed; the hard tag purge then removes the first six
 families and the hard prefix purge the next six ("match_live_first": the live objects when
 its first matching run began). The yardstick of a tag op is the prefix op's line of the same N.
+
+--list: the listing (k_list_scan / k_list_tiles / k_list_emit, HbmCache::list_keyed) is measured
+on the same full shard, before anything is removed ("op": "list"): the count-only form with the
+prefix no key starts with, timed in turn with the hard prefix purge of the same pattern (its
+yardstick: both read the same lines; "count_over_purge" is the ratio of the medians), then a
+list of one family (1/16 of the objects) with limit 100 and with the maximum (4096 rows, 128-byte
+key areas).
 """
 from __future__ import annotations
 
@@ -123,7 +130,8 @@ def summary(ts, nbytes):
             "gb_per_s": round(nbytes / med / 1e3, 1)}
 
 
-def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False) -> list:
+def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False,
+        listing: bool = False) -> list:
     nb = 1
     while nb * 2 < n:       # <= 50 % slot load
         nb *= 2
@@ -210,6 +218,49 @@ def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False) -> list
         res["match_over_sweep"] = round(res["purge_match"]["median_us"] / res["sweep"]["median_us"], 2)
         return res
 
+    def list_runs() -> dict:
+        key_cap, max_rows = 128, c.MAX_LIST_ROWS
+        rows = torch.zeros((max_rows, c.LIST_ROW_BYTES), dtype=torch.uint8, device=dev)
+        keys = torch.zeros((max_rows, key_cap), dtype=torch.uint8, device=dev)
+        res4 = torch.zeros(4, dtype=torch.int64, device=dev)
+        nomatch, fam0 = image(b"/zzz/"), image(b"/f00/")
+
+        def lst(img, limit):
+            shard._impl.list_keyed(c.LIST_PREFIX, img.data_ptr(), 5, False, 0, 0, 0, limit, key_cap,
+                                   now, rows.data_ptr(), keys.data_ptr(), res4.data_ptr(), stream)
+
+        live0 = shard.sweep(now)[0]
+        for _ in range(3):
+            lst(nomatch, 0)
+            hard(nomatch, 5)
+            lst(fam0, 100)
+            lst(fam0, max_rows)
+        torch.cuda.synchronize(dev)
+        t_count, t_purge = [], []
+        for _ in range(iters):      # in turn: the same shard state, the same neighbours
+            t_count.append(timed(lambda: lst(nomatch, 0), dev)[0])
+            assert res4.tolist() == [0, 0, 0, nslots]
+            t_purge.append(timed(lambda: hard(nomatch, 5), dev)[0])
+            assert int(out[0]) == 0
+        t_100 = [timed(lambda: lst(fam0, 100), dev)[0] for _ in range(iters)]
+        got_100 = res4.tolist()
+        t_max = [timed(lambda: lst(fam0, max_rows), dev)[0] for _ in range(iters)]
+        got_max = res4.tolist()
+        assert got_100[0] == got_max[0] and got_100[2] == 100
+        assert got_max[2] == min(max_rows, got_max[0])
+        scan_bytes = nslots * 32 + live0 * 64
+        r = {
+            "op": "list", "objects": n, "live": int(live0), "index_slots": nslots,
+            "purge_nomatch": summary(t_purge, scan_bytes),
+            "list_count_nomatch": summary(t_count, scan_bytes + nslots // 8 + nslots // 64),
+            "list_match_100": summary(t_100, scan_bytes + nslots // 4),
+            "list_match_max": summary(t_max, scan_bytes + nslots // 4 + max_rows * (64 + key_cap)),
+            "list_matched": got_max[0], "list_rows_max": got_max[2],
+        }
+        r["count_over_purge"] = round(r["list_count_nomatch"]["median_us"] /
+                                      r["purge_nomatch"]["median_us"], 3)
+        return r
+
     fams = list(range(min(FAMILIES - 4, max(iters, 10))))
     results = []
     # the soft ops remove nothing: each sees the full shard throughout
@@ -217,6 +268,8 @@ def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False) -> list
                                 ("soft-tags", soften_tags, by_tag, tags)):
         if on:
             results.append(match(no_match(op, purge, args), purge, args, fams))
+    if listing:
+        results.append(list_runs())
     hard_ops = ([("hard-tags", hard_tags, by_tag)] if tags else []) + [("hard", hard, by_prefix)]
     # every hard op's no-match runs first, on the full shard; then the families are shared out
     pending = [(no_match(op, purge, args), purge, args) for op, purge, args in hard_ops]
@@ -235,12 +288,15 @@ def main():
     ap.add_argument("--tags", action="store_true",
                     help="store every object with 4 tags and measure the purge by tag (soft and "
                          "hard) beside the prefix purge, on the same shard")
+    ap.add_argument("--list", action="store_true",
+                    help="also measure the listing (count-only and with rows) on the same full "
+                         "shard, in the same run as the prefix purge that matches nothing")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("purge_bench.py needs a GPU")
     dev = torch.device("cuda", 0)
     for n in (int(x) for x in a.objects.split(",")):
-        for res in run(n, a.iters, dev, a.soft, a.tags):
+        for res in run(n, a.iters, dev, a.soft, a.tags, a.list):
             print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 

@@ -122,6 +122,10 @@ void DramBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stal
   if (done) done(c);
 }
 
+void DramBackend::list_objects(const ListQuery& q, Executor*, ListCallback done) {
+  if (done) done(cache_.list(q, now()));
+}
+
 void DramBackend::touch(const std::string& key, const Digest& d, uint32_t ttl_s,
                         const uint32_t* flags, Executor*, TouchCallback done) {
   const uint32_t n = now();
@@ -253,6 +257,11 @@ void TieredBackend::soften_prefix(const std::string& pattern, bool exact, uint32
       if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });
+}
+
+// Fills write both levels, so L2 holds the superset: the listing is L2's.
+void TieredBackend::list_objects(const ListQuery& q, Executor* ex, ListCallback done) {
+  l2_->list_objects(q, ex, std::move(done));
 }
 
 void TieredBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor* ex,

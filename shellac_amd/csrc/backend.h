@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "digest.h"
+#include "inspect.h"
 #include "host_cache.h"
 #include "host_router.h"
 #include "ketama.h"
@@ -67,6 +68,8 @@ using DelCallback = std::function<void(bool found)>;
 using PurgeCallback = std::function<void(int64_t removed)>;
 // In-place touch: 1 touched, 0 not found, -1 the tier cannot do it.
 using TouchCallback = std::function<void(int status)>;
+// Listing (inspect.h): the answer, ok == false where the tier cannot scan its keys.
+using ListCallback = std::function<void(ListResult)>;
 using StatList = std::vector<std::pair<std::string, uint64_t>>;
 
 // Asynchronous body compressor for the proxy's -z path: `done` runs on the compressor's
@@ -144,6 +147,18 @@ class CacheBackend {
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
   }
+  // Inspection, read-only: the live objects whose stored key starts with (exact: equals)
+  // q.pattern, or that carry one of q.tags, or all of them; how many they are and their bytes
+  // (per stored copy, as a purge's count), and up to q.limit of them after the cursor q.after,
+  // in an order of the tier's own that a cursor pages through exactly (`next`; empty: the
+  // end). `done` runs once, on `ex`'s thread (inline for synchronous backends). ok == false:
+  // the tier cannot scan its keys (the default), or the query is out of range.
+  virtual void list_objects(const ListQuery& q, Executor* ex, ListCallback done) {
+    (void)q;
+    if (!done) return;
+    if (ex) ex->post([done] { done(ListResult{}); });
+    else done(ListResult{});
+  }
   // Touch: give the live object of exactly `key` the TTL `ttl_s` from now (0 = never expires)
   // and, when `flags` is not null (read before the call returns), new flags, without moving
   // its bytes. A write: ordered with
@@ -212,6 +227,7 @@ class DramBackend : public CacheBackend {
   void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
                      Executor* ex, PurgeCallback done) override;
   void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
@@ -293,14 +309,18 @@ struct HbmBackendConfig {
 // What an HbmBackend request asks of its shard's batcher. A flight runs its requests by kind,
 // in this order: GETs, SETs, DELETEs, touches, hot-replica fills, prefix purges (a barrier
 // only reports that its flight has finished).
-enum class ReqKind : uint8_t { Get, Set, Del, Barrier, Fill, Purge, Touch };
+// A list is a control request of its own kind: it writes nothing, so it marks no fill, no
+// shard purge_dirty and no purge generation; it is queued behind the writes queued before it
+// and launched at the end of its flight, as a purge.
+enum class ReqKind : uint8_t { Get, Set, Del, Barrier, Fill, Purge, Touch, List };
 // changes a key's object: ordered against the key's other requests, counted as pending
 constexpr bool is_write(ReqKind k) {
   return k == ReqKind::Set || k == ReqKind::Del || k == ReqKind::Touch;
 }
 // names no key and answers through Req::ccb on the batcher thread
 constexpr bool is_ctl(ReqKind k) {
-  return k == ReqKind::Barrier || k == ReqKind::Fill || k == ReqKind::Purge;
+  return k == ReqKind::Barrier || k == ReqKind::Fill || k == ReqKind::Purge ||
+         k == ReqKind::List;
 }
 
 struct DigestHash {
@@ -334,6 +354,7 @@ class HbmBackend : public CacheBackend {
   // The same ReqKind::Purge request carrying a tag list instead of a pattern: ordering,
   // fan-out, hot replicas, refresh fills and purge_dirty are purge_prefix's.
   void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
   // Routed like del(): to the owner, and for a hot object written through to every shard in
@@ -361,6 +382,20 @@ class HbmBackend : public CacheBackend {
     Executor* ex = nullptr;
     PurgeCallback cb;
   };
+  // One list_objects call walking the shards in order (backend_hbm.cc list_step): every shard
+  // in service scans (the totals cover them all), the shards from the cursor's on are asked
+  // for the rows still wanted, one at a time.
+  struct ListWalk {
+    ListQuery q;
+    ListResult res;
+    int cur_shard = 0;       // the cursor
+    uint64_t cur_slot = 0;
+    int shard = -1;          // the shard being asked
+    uint32_t asked = 0;      // rows asked of it
+    bool have_next = false;  // res.next is set: the shards after it only count
+    Executor* ex = nullptr;
+    ListCallback cb;
+  };
   struct Req {
     ReqKind kind = ReqKind::Get;
     Digest d;
@@ -382,6 +417,8 @@ class HbmBackend : public CacheBackend {
     std::function<void(bool ok)> ccb;
     std::shared_ptr<HotFill> fill;
     std::shared_ptr<Purge> purge;  // Purge (`key` holds the pattern)
+    std::shared_ptr<ListWalk> list;  // List: the walk it belongs to; `flags` holds the rows
+    uint64_t list_start = 0;         // asked of this shard, list_start the start slot
   };
   struct Dev;
   struct Direct;
@@ -452,6 +489,9 @@ class HbmBackend : public CacheBackend {
   // purge_prefix and soften_prefix: `proto` (kind Purge, the pattern and the soft fields) goes
   // to every shard in service
   void purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done);
+  // list_objects' walk: asks the next shard in service, or answers
+  void list_step(std::shared_ptr<ListWalk> w);
+  std::atomic<uint64_t> lists_{0};
   // ---- hot-object spreading (hot_refresh_locked documents the protocol)
   std::unique_ptr<HostRouter> router_;  // ketama owners + the published hot table
   bool hot_on_ = false;
@@ -509,6 +549,7 @@ class TieredBackend : public CacheBackend {
                      Executor* ex, PurgeCallback done) override;
   // L2 then L1 with the purge epoch moved in between, as the prefix forms.
   void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
   // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
@@ -580,6 +621,9 @@ class FaultBackend : public CacheBackend {
   }
   void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override {
     inner_->purge_tags(hashes, ex, std::move(done));
+  }
+  void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override {
+    inner_->list_objects(q, ex, std::move(done));
   }
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override {

@@ -454,6 +454,62 @@ void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback don
   purge_finish(p);
 }
 
+// Inspection: the shards are visited in order, one request at a time (list_next_ask), each
+// queued to its shard's batcher behind the writes queued before it. A shard out of service
+// is skipped and counted; so is one whose flight fails.
+void HbmBackend::list_objects(const ListQuery& q, Executor* ex, ListCallback done) {
+  if (!done) return;
+  auto w = std::make_shared<ListWalk>();
+  w->q = q;
+  w->ex = ex;
+  w->cb = std::move(done);
+  const bool cursor_ok = q.after.empty() || hbm_cursor_parse(q.after, (int)devs_.size(),
+                                                              &w->cur_shard, &w->cur_slot);
+  if (!list_query_valid(q) || !cursor_ok) {
+    ListResult bad;
+    bad.ok = list_query_valid(q);
+    bad.bad_cursor = !cursor_ok;
+    PostGroups::answer_now(ex, [cb = std::move(w->cb), bad]() { cb(bad); });
+    return;
+  }
+  lists_.fetch_add(1, std::memory_order_relaxed);
+  w->res.ok = true;
+  list_step(std::move(w));
+}
+
+void HbmBackend::list_step(std::shared_ptr<ListWalk> w) {
+  for (;;) {
+    const uint32_t got = (uint32_t)w->res.objects.size();
+    const ListAsk a = list_next_ask(w->shard, w->cur_shard, w->cur_slot, w->have_next,
+                                    w->q.limit > got ? w->q.limit - got : 0,
+                                    up_mask_.load(std::memory_order_acquire), (int)devs_.size());
+    w->res.shards_skipped += a.skipped;
+    if (a.shard < 0) {
+      PostGroups::answer_now(w->ex, [w]() { w->cb(std::move(w->res)); });
+      return;
+    }
+    w->shard = a.shard;
+    w->asked = a.limit;
+    Dev* const dv = devs_[(size_t)a.shard].get();
+    const uint64_t nslots = dv->cache->config().nbuckets * kEntriesPerBucket;
+    if (a.start > nslots) {  // (a cursor from another geometry: nothing follows on this shard)
+      w->asked = 0;
+    }
+    Req r;
+    r.kind = ReqKind::List;
+    r.d = Digest{0, 0};
+    r.list = w;
+    r.flags = w->asked;
+    r.list_start = a.start > nslots ? 0 : a.start;
+    r.ccb = [this, w](bool ok) {
+      if (!ok) ++w->res.shards_skipped;
+      list_step(w);
+    };
+    enqueue(a.shard, std::move(r));
+    return;
+  }
+}
+
 void HbmBackend::flush() {
   for (auto& d : devs_) {
     {
@@ -569,6 +625,7 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_soft_purges", soft_purges_.load());
   out->emplace_back("hbm_softened_objects", sum(&Dev::softened_objects));
   out->emplace_back("hbm_tag_purges", by_tag);
+  out->emplace_back("hbm_lists", lists_.load());
   out->emplace_back("hbm_tag_purged_objects", sum(&Dev::tag_purged_objects));
   out->emplace_back("hbm_tag_softened_objects", sum(&Dev::tag_softened_objects));
   // touch requests taken, and the entries the shards' kernels updated (replicas included)

@@ -58,6 +58,11 @@ PYBIND11_MODULE(_shellac_core, m) {
   m.attr("SERVE_KEYS") = (int64_t)HbmCache::kServeKeys;
   m.attr("ITEM_MAGIC") = kItemMagic;
   m.attr("MISS_LOC") = py::int_(kMissLoc);
+  m.attr("LIST_PREFIX") = (int)kListPrefix;
+  m.attr("LIST_TAGS") = (int)kListTags;
+  m.attr("LIST_ALL") = (int)kListAll;
+  m.attr("LIST_ROW_BYTES") = (int)sizeof(ListRow);
+  m.attr("MAX_LIST_ROWS") = (int)kMaxListRows;
 
   m.def("digest", [](py::bytes b) {
     std::string s = b;
@@ -274,6 +279,20 @@ PYBIND11_MODULE(_shellac_core, m) {
                             P<uint64_t>(out), S(s));
       }, py::arg("tags"), py::arg("ntags"), py::arg("stale_at"), py::arg("expire_cap"),
          py::arg("now"), py::arg("out"), py::arg("stream"))
+      // mode: LIST_PREFIX (image, plen, exact), LIST_TAGS (tags, ntags) or LIST_ALL; rows:
+      // limit x LIST_ROW_BYTES, keys: limit x key_cap, out: 4 words {matched, bytes, listed,
+      // next} (device or mapped pinned memory); asynchronous on the stream
+      .def("list_keyed", [](HbmCache& c, uint32_t mode, uintptr_t image, uint32_t plen, bool exact,
+                            uintptr_t tags, uint32_t ntags, uint64_t start, uint32_t limit,
+                            uint32_t key_cap, uint32_t now, uintptr_t rows, uintptr_t keys,
+                            uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.list_keyed(mode, P<const uint8_t>(image), plen, exact, P<const uint64_t>(tags), ntags,
+                     start, limit, key_cap, now, P<ListRow>(rows), P<uint8_t>(keys),
+                     P<uint64_t>(out), S(s));
+      }, py::arg("mode"), py::arg("image"), py::arg("plen"), py::arg("exact"), py::arg("tags"),
+         py::arg("ntags"), py::arg("start"), py::arg("limit"), py::arg("key_cap"), py::arg("now"),
+         py::arg("rows"), py::arg("keys"), py::arg("out"), py::arg("stream"))
       // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
       .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
@@ -507,6 +526,18 @@ PYBIND11_MODULE(_shellac_core, m) {
                                    uint32_t expire_cap, uint32_t now) {
         return c.soften_keyed_tags(tags.data(), (uint32_t)tags.size(), stale_at, expire_cap, now);
       }, py::arg("tags"), py::arg("stale_at"), py::arg("expire_cap"), py::arg("now"))
+      // rows, keys, out: host buffers as HbmCache.list_keyed's; prefix: the plain prefix
+      .def("list_keyed", [](HostCache& c, uint32_t mode, py::bytes prefix, bool exact,
+                            std::vector<uint64_t> tags, uint64_t start, uint32_t limit,
+                            uint32_t key_cap, uint32_t now, uintptr_t rows, uintptr_t keys,
+                            uintptr_t out) {
+        const std::string p = prefix;
+        c.list_keyed(mode, reinterpret_cast<const uint8_t*>(p.data()), (uint32_t)p.size(), exact,
+                     tags.data(), (uint32_t)tags.size(), start, limit, key_cap, now,
+                     P<ListRow>(rows), P<uint8_t>(keys), P<uint64_t>(out));
+      }, py::arg("mode"), py::arg("prefix"), py::arg("exact"), py::arg("tags"), py::arg("start"),
+         py::arg("limit"), py::arg("key_cap"), py::arg("now"), py::arg("rows"), py::arg("keys"),
+         py::arg("out"))
       .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
                        uint32_t now) {

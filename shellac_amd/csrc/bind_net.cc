@@ -291,6 +291,61 @@ void bind_net(py::module_& m) {
           be->soften_tags(hs, stale_at, keep_s, &g_inline, std::move(cb));
         });
       }, py::arg("tags"), py::arg("stale_at"), py::arg("keep_s") = 0)
+      // inspection (blocking): prefix, key (exact) or tags, none of them: everything. None: the
+      // tier cannot scan or refused the query; else a dict (next: None at the end)
+      .def("list_objects", [](BackendHandle& h, py::object prefix, py::object key, py::object tags,
+                              uint32_t limit, const std::string& after) -> py::object {
+        ListQuery q;
+        q.limit = limit;
+        q.after = after;
+        if (!prefix.is_none() || !key.is_none()) {
+          q.mode = kListPrefix;
+          q.exact = prefix.is_none();
+          q.pattern = (q.exact ? key : prefix).cast<std::string>();
+        } else if (!tags.is_none()) {
+          q.mode = kListTags;
+          for (const std::string& t : tags.cast<std::vector<std::string>>())
+            q.tags.push_back(tag_hash(t));
+        }
+        CacheBackend* be = h.be.get();
+        ListResult res;
+        {
+          std::mutex mu;
+          std::condition_variable cv;
+          bool done = false;
+          py::gil_scoped_release nogil;
+          be->list_objects(q, &g_inline, [&](ListResult r) {
+            std::lock_guard<std::mutex> lk(mu);
+            res = std::move(r);
+            done = true;
+            cv.notify_all();
+          });
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return done; });
+        }
+        if (!res.ok || res.bad_cursor) return py::none();
+        py::list objs;
+        for (const ListedObject& o : res.objects) {
+          py::dict d;
+          d["key"] = py::bytes(o.key);
+          d["key_truncated"] = o.key_truncated;
+          d["size"] = o.size;
+          d["ttl"] = o.ttl < 0 ? py::object(py::none()) : py::object(py::int_(o.ttl));
+          d["flags"] = o.flags;
+          d["tags"] = o.ntags;
+          d["referenced"] = o.referenced;
+          d["shard"] = o.shard;
+          objs.append(d);
+        }
+        py::dict out;
+        out["matched"] = res.matched;
+        out["bytes"] = res.bytes;
+        out["next"] = res.next.empty() ? py::object(py::none()) : py::object(py::bytes(res.next));
+        out["shards_skipped"] = res.shards_skipped;
+        out["objects"] = objs;
+        return out;
+      }, py::arg("prefix") = py::none(), py::arg("key") = py::none(), py::arg("tags") = py::none(),
+         py::arg("limit") = 100, py::arg("after") = "")
       // in-place touch (blocking): 1 touched, 0 not found, -1 the tier cannot. `flags` None
       // keeps the object's flags; `digest_of`: look the key up under another key's digest (a
       // forged collision)
@@ -508,10 +563,12 @@ void bind_net(py::module_& m) {
                        int health_interval_ms, int health_timeout_ms, int health_fails,
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
                        uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge,
-                       uint32_t grace, const std::string& tag_header) {
+                       uint32_t grace, const std::string& tag_header,
+                       const std::string& inspect) {
              ProxyConfig c;
              c.grace = grace;
              c.tag_header = tag_header;
+             c.inspect = inspect;
              SH_CHECK(purge == "off" || purge == "loopback" || purge == "any",
                       "purge must be off, loopback or any");
              c.purge = purge;
@@ -565,7 +622,8 @@ void bind_net(py::module_& m) {
            py::arg("cpus") = std::vector<int>{}, py::arg("spin_us") = 0,
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
            py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
-           py::arg("purge") = "off", py::arg("grace") = 0, py::arg("tag_header") = "")
+           py::arg("purge") = "off", py::arg("grace") = 0, py::arg("tag_header") = "",
+           py::arg("inspect") = "off")
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)

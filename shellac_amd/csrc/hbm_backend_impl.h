@@ -228,9 +228,13 @@ struct Flight {
   // launch_purges: pattern images (keyed.h) and {removed, bytes} word pairs, one per purge (a
   // soft purge fills the first word: the objects softened); a tag purge's image is its hash list
   Mapped purge_img, purge_out;
+  // launch_lists (at most one list a flight: plan_take cuts after it): [pattern image or tag
+  // list | 4 result words | rows | key areas], at the offsets below
+  Mapped list_buf;
+  size_t list_out_off = 0, list_rows_off = 0, list_keys_off = 0;
   void release_mapped() {
     for (Mapped* m : {&keys, &offs, &set_keys, &set_vals, &set_voff, &set_meta, &del_keys,
-                      &del_found, &touch_rows, &touch_kbytes, &purge_img, &purge_out})
+                      &del_found, &touch_rows, &touch_kbytes, &purge_img, &purge_out, &list_buf})
       m->release();
   }
   std::vector<uint32_t> trow;
@@ -381,6 +385,8 @@ struct HbmBackend::Dev {
   void launch_touches(Flight& f);
   void launch_fills(Flight& f);
   void launch_purges(Flight& f);
+  void launch_lists(Flight& f);
+  void deliver_list(Flight& f, Req& r);
   bool try_reap(Flight& f, bool block);
   void regather(Flight& f, uint64_t total);
   void deliver_gets(Flight& f);

@@ -209,7 +209,8 @@ void HbmBackend::Dev::launch(Flight& f) {
       case ReqKind::Touch: f.touches.push_back(i); break;
       case ReqKind::Barrier:
       case ReqKind::Fill:
-      case ReqKind::Purge: f.ctls.push_back(i); break;
+      case ReqKind::Purge:
+      case ReqKind::List: f.ctls.push_back(i); break;
     }
   }
   f.tnow = be->now();
@@ -223,6 +224,7 @@ void HbmBackend::Dev::launch(Flight& f) {
   launch_touches(f);
   launch_fills(f);
   launch_purges(f);
+  launch_lists(f);
   HB_OK(hipEventRecord(f.ev, stream));
   batches++;
   batched_reqs += f.reqs.size();
@@ -430,6 +432,77 @@ void HbmBackend::Dev::launch_purges(Flight& f) {
   }
 }
 
+// A list (HbmBackend::list_step): after the flight's writes, as a purge; the query's image or
+// tag list, the result words, the rows and the key areas in one mapped buffer. It writes
+// nothing in the cache, so neither the filter nor `touched` nor purge_dirty hears of it.
+constexpr uint32_t kListBackendKeyCap = 256;  // keys up to 254 bytes come back whole
+
+void HbmBackend::Dev::launch_lists(Flight& f) {
+  for (uint32_t i : f.ctls) {
+    const Req& r = f.reqs[i];
+    if (r.kind != ReqKind::List) continue;
+    const ListQuery& q = r.list->q;
+    const uint32_t limit = r.flags;
+    const size_t img = q.mode == kListPrefix ? keyed_prefix_image_bytes(q.pattern.size())
+                                             : (q.tags.size() * sizeof(uint64_t) + 15) & ~(size_t)15;
+    f.list_out_off = img;
+    f.list_rows_off = img + 32;
+    f.list_keys_off = f.list_rows_off + (size_t)limit * sizeof(ListRow);
+    f.list_buf.ensure(f.list_keys_off + (size_t)limit * kListBackendKeyCap + 16);
+    uint8_t* const h = f.list_buf.host<uint8_t>();
+    uint8_t* const d = f.list_buf.dev<uint8_t>();
+    if (q.mode == kListPrefix)
+      write_keyed_prefix_image(h, reinterpret_cast<const uint8_t*>(q.pattern.data()),
+                               q.pattern.size());
+    else if (q.mode == kListTags)
+      std::memcpy(h, q.tags.data(), q.tags.size() * sizeof(uint64_t));
+    std::memset(h + f.list_out_off, 0, 32);
+    cache->list_keyed(q.mode, d, (uint32_t)q.pattern.size(), q.exact,
+                      reinterpret_cast<const uint64_t*>(d), (uint32_t)q.tags.size(), r.list_start,
+                      limit, kListBackendKeyCap, f.tnow,
+                      reinterpret_cast<ListRow*>(d + f.list_rows_off), d + f.list_keys_off,
+                      reinterpret_cast<uint64_t*>(d + f.list_out_off), stream);
+    return;
+  }
+}
+
+// The flight has finished: this shard's part of the walk. Rows flagged as changed and hot
+// replicas (the digest's owner is another shard) are left out; the counts are per stored copy.
+void HbmBackend::Dev::deliver_list(Flight& f, Req& r) {
+  ListWalk& w = *r.list;
+  const uint8_t* const h = f.list_buf.host<uint8_t>();
+  const uint64_t* const out = reinterpret_cast<const uint64_t*>(h + f.list_out_off);
+  const ListRow* const rows = reinterpret_cast<const ListRow*>(h + f.list_rows_off);
+  w.res.matched += out[kListMatched];
+  w.res.bytes += out[kListBytes];
+  const uint64_t up = be->up_mask_.load(std::memory_order_acquire);
+  for (uint64_t j = 0; j < out[kListListed]; ++j) {
+    const ListRow& row = rows[j];
+    if (row.bits & kListChanged) continue;
+    if (list_row_is_replica(be->owner_of(Digest{row.d0, row.d1}, up), index)) continue;
+    const uint8_t* const area = h + f.list_keys_off + j * kListBackendKeyCap;
+    ListedObject o;
+    const uint32_t have = std::min(row.klen, kListBackendKeyCap - (uint32_t)kKeyedPrefix);
+    o.key.assign(reinterpret_cast<const char*>(area) + kKeyedPrefix, have);
+    o.key_truncated = row.klen > have;
+    o.size = row.vlen;
+    o.ttl = row.expire ? (int64_t)row.expire - (int64_t)f.tnow : -1;
+    o.flags = row.flags;
+    o.ntags = row.ntags == kTagOverflow ? -1 : (int)row.ntags;
+    o.referenced = (row.bits & kListRefBit) != 0;
+    o.shard = index;
+    w.res.objects.push_back(std::move(o));
+  }
+  const uint64_t nslots = cache->config().nbuckets * kEntriesPerBucket;
+  if (!w.have_next) {
+    const uint32_t got = (uint32_t)w.res.objects.size();
+    const uint32_t still = w.q.limit > got ? w.q.limit - got : 0;
+    w.res.next = list_cursor_after(index, w.asked, still, out[kListNext], nslots,
+                                   (int)be->devs_.size());
+    w.have_next = !w.res.next.empty();
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // reaping
 // ---------------------------------------------------------------------------------
@@ -509,6 +582,7 @@ void HbmBackend::Dev::finish_ctls(Flight& f) {
       }
       if (r.purge) r.purge->removed.fetch_add((int64_t)res[0], std::memory_order_relaxed);
     }
+    if (r.kind == ReqKind::List) deliver_list(f, r);
     if (r.ccb) r.ccb(true);
   }
 }
@@ -612,6 +686,7 @@ void HbmBackend::Dev::fail_requests(std::vector<Req>& reqs, bool unlaunched) {
       case ReqKind::Barrier:
       case ReqKind::Fill:
       case ReqKind::Purge:
+      case ReqKind::List:
         if (r.ccb) r.ccb(false);
         r.ccb = nullptr;
         break;

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "keyed.h"
 #include "layout.h"
 
 namespace shellac {
@@ -284,6 +285,27 @@ class HbmCache {
   // checks (the cap lies after now; refused while a phase-1 batch waits for its phase 2).
   void soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
                          uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
+  // List keyed values, read-only: finds every live entry whose stored keyed value matches,
+  // counts them and their item bytes over the whole index, and writes the first `limit` of them
+  // at slots >= start_slot, in index-slot order, as one ListRow (keyed.h) and one key area each
+  // (row r's: keys + r * key_cap, the head of the stored image [u16 klen | key ...], at most
+  // key_cap bytes; bytes of the area past the key's granules are left as they are). `mode`:
+  // kListPrefix (`image`, `plen`, `exact` as soften_keyed_prefix's), kListTags (`tags`, `ntags`
+  // as remove_keyed_tags') or kListAll (every plausible keyed value: 1 <= klen, 2 + klen <=
+  // vlen; an empty key names no object). limit <= kMaxListRows (0: count only, no row is
+  // written and next = nslots); key_cap a multiple of 16 in 16..1024; start_slot <= nslots. `out` (kListWords words) receives
+  // {matched, their item bytes, rows listed, next}: next is the slot after the last listed row
+  // when further matches follow it (the next page's start_slot), else nslots. `rows`, `keys`
+  // and `out` are device or mapped pinned memory. Asynchronous and ordered on `s` like
+  // remove_keyed_prefix; the match bitmap and tile counts are a workspace allocated on the
+  // first call (that call allocates), and with the scratch words they make it one listing at
+  // a time per shard. It writes nothing in the index or the log, counts in no CacheCounters
+  // field, and is not refused while a phase-1 batch is pending. See k_list_scan for what holds
+  // beside a SET chain on another stream (rows may come back flagged kListChanged).
+  void list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bool exact,
+                  const uint64_t* tags, uint32_t ntags, uint64_t start_slot, uint32_t limit,
+                  uint32_t key_cap, uint32_t now, ListRow* rows, uint8_t* keys, uint64_t* out,
+                  hipStream_t s);
   // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
   // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
   // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte
@@ -462,6 +484,7 @@ class HbmCache {
   uint64_t* next_head() const { return head_ + (hsel_ ^ 1); }
   CacheCounters* ctr_ = nullptr;     // device counters (64 shards)
   unsigned long long* scratch_ = nullptr;  // device scratch for reductions
+  uint8_t* list_ws_ = nullptr;       // list_keyed: match bitmap, tile counts and bases
   uint64_t* part_ = nullptr;         // per-workgroup sums: GET sizes, SET sizes, SET counts
   uint64_t* host_buf_ = nullptr;     // pinned scratch for small D2H reads
   uint64_t* host_slots_ = nullptr;   // pinned coherent slots the GPU writes totals into

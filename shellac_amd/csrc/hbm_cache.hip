@@ -47,6 +47,10 @@
 //                  block (keyed.h, at value byte 2 + klen) holds one of up to 64 hashes, or
 //                  the overflow block, is removed; unaligned hashes come from aligned dwords.
 //   k_soften_tags  the same matcher with k_soften_prefix's action.
+//   k_list_scan    the purges' scans and matchers, read-only, by tiles of kBlock slots: each
+//                  wave's match ballot goes into a bitmap, each tile's count into an array.
+//   k_list_tiles   one workgroup scans the tile counts; k_list_emit gives every match its
+//                  rank from them and writes the first `limit` rows and keys in slot order.
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -3643,6 +3647,297 @@ __global__ __launch_bounds__(kBlock) void k_soften_tags(
   }
 }
 
+// ---- listing -------------------------------------------------------------------------------
+// List: find the live entries whose stored keyed value matches, count them and their item
+// bytes over the whole index, and return the first `limit` of them at slots >= start_slot in
+// index-slot order, one ListRow (keyed.h) and one key area each. Slot order makes a cursor
+// exact (the next page starts at the slot after the last row), which an atomic reservation
+// as k_export's cannot give, so the operation is two passes over a match bitmap:
+//   k_list_scan   k_purge_prefix's traversal by *tiles* of kBlock consecutive slots (grid-
+//                 stride over tiles, as k_export), its liveness test, record re-check and
+//                 matchers: the pattern image (exact: klen == plen too, k_soften_prefix), the
+//                 tag list (tag_block_match), or all (any plausible keyed value: 2 + klen <=
+//                 vlen, with a key of at least one byte). Each wave stores its match ballot as
+//                 one 64-bit word of the bitmap (one vector store by lane 0), each tile the
+//                 number of its matches at slots >= start_slot; matched and bytes (the whole
+//                 index, whatever start_slot is) go to the result words with one add per word
+//                 per workgroup.
+//   k_list_tiles  one workgroup: the exclusive scan of the tile counts (a tile's base rank),
+//                 and listed = min(matches from start_slot, limit).
+//   k_list_emit   a tile with no match or a base rank >= limit does nothing; a matching lane
+//                 with rank < limit reads its entry and record header again and writes its
+//                 row and the granules that hold [u16 klen | key] (at most key_cap bytes,
+//                 never past the record) at its rank. The lane of rank limit - 1 writes
+//                 next_slot when more matches follow; otherwise next_slot stays nslots.
+// Nothing in the index or the log is written, and no CacheCounters field counts it.
+//
+// What it relies on. The result is exact when the operation is ordered on a stream between
+// whole SET chains: every matching object stored before the call is counted, and listed in
+// slot order, nothing else is, and no row is flagged. Beside an append on another stream it
+// only reads: the index, and the log inside [record, record + item_bytes(vlen)) with vlen <=
+// max_item and a 16-B-aligned loc (inside the log's slack), of a record that carried the
+// entry's digest, vlen and magic. It never lists an object under a key it was not stored with:
+// the emit pass checks the entry and the header again, copies the key, and then (after a
+// fence: every copy load has returned) reads the newest head any SET chain has published or
+// claimed (k_edge_server's seqlock: a batch raises the claim word before its append). A row
+// whose entry no longer passes, or whose record the claim now reaches, is written with
+// kListChanged and klen = 0, never dropped, so the ranks of the other rows stay as counted.
+template <uint32_t mode>
+__device__ __forceinline__ bool list_slot_matches(
+    const Entry* __restrict__ e, const uint8_t* __restrict__ log, const uint64_t head,
+    const uint64_t cap, const uint32_t max_item, const uint32_t now, const uint32_t plen,
+    const uint32_t ngran, const uint32_t exact, const uint4* s_img,
+    const uint4* __restrict__ pat, const uint2* s_tags, const uint32_t nlist,
+    uint32_t* vlen_out) {
+  const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+  const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+  const uint64_t loc = pack2(eb.x, eb.y);
+  const uint32_t vlen = entry_vlen(eb.z);
+  if (!entry_live(loc, eb.w, head, cap, now)) return false;
+  const uint32_t vmin = (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen
+                                                  : mode == kListTags ? 2u : 0u);
+  if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) return false;
+  const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
+  const uint4 ha = rec[0], hb = rec[1];
+  // the entry's own record: digest, vlen and magic (ItemHeader's words)
+  if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+      hb.w != kItemMagic)
+    return false;
+  const uint4 v0 = rec[2];
+  const uint32_t klen = v0.x & 0xffffu;
+  if (kKeyedPrefix + klen > vlen) return false;
+  *vlen_out = vlen;
+  if (mode == kListAll) return klen != 0;  // (an empty key names no object)
+  if (mode == kListTags) return tag_block_match(rec, vlen, v0, s_tags, nlist);
+  if (klen < plen || (exact && klen != plen)) return false;
+  if (!purge_granule_eq(v0, s_img[0], s_img[2])) return false;
+  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+  for (uint32_t g = 1; g < ngran; ++g) {
+    const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_img[2 + g] : pat[g];
+    if (!purge_granule_eq(rec[2 + g], g + 1 == ngran ? s_img[1] : ones, p)) return false;
+  }
+  return true;
+}
+
+// The bits of a wave's match word at slots >= start_slot; k0 is the slot of its bit 0.
+__device__ __forceinline__ unsigned long long list_word_from(const unsigned long long m,
+                                                             const uint64_t k0,
+                                                             const uint64_t start_slot) {
+  if (k0 >= start_slot) return m;
+  return start_slot - k0 >= 64 ? 0ull : m & (~0ull << (start_slot - k0));
+}
+
+template <uint32_t mode>
+__global__ __launch_bounds__(kBlock) void k_list_scan(
+    const Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    const uint4* __restrict__ img, uint32_t plen, uint32_t ngran, uint32_t exact,
+    const uint2* __restrict__ tags, uint32_t nlist, uint64_t start_slot,
+    unsigned long long* __restrict__ bitmap, uint32_t* __restrict__ tile_cnt,
+    unsigned long long* __restrict__ acc) {
+  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
+  __shared__ uint2 s_tags[kMaxPurgeTags];
+  // per-wave counts of a tile, two sets taken in turn: one barrier per tile
+  __shared__ unsigned int s_cnt[2][kBlock / 64];
+  if (mode == kListPrefix)
+    for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
+      s_img[g] = img[g];
+  if (mode == kListTags)
+    for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s_tags[j] = tags[j];
+  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
+  __syncthreads();
+  const uint64_t head = *head_ptr;
+  const uint64_t ntiles = (nslots + kBlock - 1) / kBlock;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  unsigned long long matched = 0, bytes = 0;
+  int set = 0;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, set ^= 1) {
+    const uint64_t k = tile * kBlock + threadIdx.x;
+    uint32_t vlen = 0;
+    const bool hit = k < nslots &&
+                     list_slot_matches<mode>(index + k, log, head, cap, max_item, now, plen,
+                                             ngran, exact, s_img, img + 2, s_tags, nlist, &vlen);
+    if (hit) {
+      ++matched;
+      bytes += item_bytes(vlen);
+    }
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) {
+      bitmap[tile * (kBlock / 64) + w] = m;
+      s_cnt[set][w] = (unsigned int)__popcll(list_word_from(m, k, start_slot));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned int t = 0;
+#pragma unroll
+      for (int i = 0; i < kBlock / 64; ++i) t += s_cnt[set][i];
+      tile_cnt[tile] = t;
+    }
+  }
+  // the result words: one add per word per workgroup, after its whole loop (k_purge_prefix)
+  __shared__ unsigned long long s_res[2][kBlock / 64];
+  matched = wave_sum(matched);
+  bytes = wave_sum(bytes);
+  if (lane == 0) {
+    s_res[0][w] = matched;
+    s_res[1][w] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0, t1 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+      t0 += s_res[0][k];
+      t1 += s_res[1][k];
+    }
+    if (t0) atomicAdd(&acc[kListMatched], t0);
+    if (t1) atomicAdd(&acc[kListBytes], t1);
+    if (blockIdx.x == 0) acc[kListNext] = nslots;  // (k_list_emit: the cursor, if rows remain)
+  }
+  // the counts' padding up to a multiple of 4 (k_list_tiles reads 16-B groups): zero, on this
+  // stream, every call
+  if (blockIdx.x == 0 && threadIdx.x < ((ntiles + 3) & ~3ull) - ntiles)
+    tile_cnt[ntiles + threadIdx.x] = 0;
+}
+
+// Exclusive scan of the tile counts: tile_base[t] = matches from start_slot in tiles < t,
+// tile_base[ntiles4] (and every entry from ntiles on) = their total; listed = min(total,
+// limit). One workgroup, a contiguous run of tiles per thread (a multiple of 4: 16-B loads
+// and stores); tile_cnt[ntiles .. ntiles4) is zero (k_list_scan clears the padding),
+// ntiles4 = ntiles rounded up to a multiple of 4. The largest index benched has 65 536
+// tiles: 256 per thread.
+__global__ __launch_bounds__(kBlock) void k_list_tiles(const uint32_t* __restrict__ tile_cnt,
+                                                       uint32_t ntiles4,
+                                                       uint32_t* __restrict__ tile_base,
+                                                       uint32_t limit,
+                                                       unsigned long long* __restrict__ acc) {
+  __shared__ unsigned int s_w[kBlock / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t per = ((ntiles4 + kBlock - 1) / kBlock + 3u) & ~3u;
+  const uint64_t b0 = (uint64_t)threadIdx.x * per;
+  const uint32_t i0 = b0 < ntiles4 ? (uint32_t)b0 : ntiles4;
+  const uint32_t i1 = b0 + per < ntiles4 ? (uint32_t)(b0 + per) : ntiles4;
+  unsigned int ts = 0;
+  for (uint32_t i = i0; i < i1; i += 4) {
+    const uint4 c = *reinterpret_cast<const uint4*>(tile_cnt + i);
+    ts += c.x + c.y + c.z + c.w;
+  }
+  unsigned int inc = ts;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned int o = __shfl_up(inc, d);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) s_w[w] = inc;
+  __syncthreads();
+  unsigned int ex = inc - ts;
+  for (int k = 0; k < w; ++k) ex += s_w[k];
+  for (uint32_t i = i0; i < i1; i += 4) {
+    const uint4 c = *reinterpret_cast<const uint4*>(tile_cnt + i);
+    uint4 b;
+    b.x = ex;
+    b.y = b.x + c.x;
+    b.z = b.y + c.y;
+    b.w = b.z + c.z;
+    ex = b.w + c.w;
+    *reinterpret_cast<uint4*>(tile_base + i) = b;
+  }
+  if (threadIdx.x == kBlock - 1) {
+    tile_base[ntiles4] = ex;
+    acc[kListListed] = ex < limit ? ex : limit;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_list_emit(
+    const Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ heads, uint64_t cap,
+    uint32_t max_item, uint32_t now, const unsigned long long* __restrict__ bitmap,
+    const uint32_t* __restrict__ tile_base, uint32_t ntiles4, uint64_t start_slot, uint32_t limit,
+    uint32_t key_cap, ListRow* __restrict__ rows, uint8_t* __restrict__ keys,
+    unsigned long long* __restrict__ acc) {
+  const uint64_t head = *head_ptr;
+  const uint64_t ntiles = (nslots + kBlock - 1) / kBlock;
+  const uint32_t total = tile_base[ntiles4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint64_t tile = start_slot / kBlock + blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint32_t base = tile_base[tile];
+    if (base >= limit) break;  // (the bases ascend: so are all this workgroup's further tiles)
+    if (tile_base[tile + 1] == base) continue;
+    // the lane's rank: the tile's base, the waves before it in the tile, the lanes before it
+    uint32_t rank = base;
+    bool mine = false;
+    for (int i = 0; i <= w; ++i) {
+      const unsigned long long m = list_word_from(bitmap[tile * (kBlock / 64) + i],
+                                                  tile * kBlock + (uint64_t)i * 64, start_slot);
+      if (i < w) {
+        rank += (uint32_t)__popcll(m);
+      } else {
+        mine = (m >> lane) & 1ull;
+        rank += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      }
+    }
+    if (!mine || rank >= limit) continue;
+    const uint64_t k = tile * kBlock + threadIdx.x;
+    const Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    uint32_t klen = 0, ntags = 0, flags = 0;
+    uint32_t bits = (eb.z & kRefBit) ? kListRefBit : 0u;
+    bool ok = entry_live(loc, eb.w, head, cap, now) && vlen >= kKeyedPrefix && vlen <= max_item &&
+              ((loc - 1) & 15) == 0;
+    if (ok) {
+      const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
+      const uint4 ha = rec[0], hb = rec[1];
+      const uint4 v0 = rec[2];  // (vlen >= 2: inside the record)
+      klen = v0.x & 0xffffu;
+      ok = ha.x == ea.x && ha.y == ea.y && ha.z == ea.z && ha.w == ea.w && hb.x == vlen &&
+           hb.w == kItemMagic && kKeyedPrefix + klen <= vlen;
+      if (ok) {
+        flags = hb.y;
+        // the granules that hold [u16 klen | key]: 2 + klen <= vlen, so inside the record
+        const uint32_t o = (uint32_t)kKeyedPrefix + klen;
+        const uint32_t need = (o + 15u) >> 4, room = key_cap >> 4;
+        const uint32_t ng = need < room ? need : room;
+        uint4* const dst = reinterpret_cast<uint4*>(keys + (uint64_t)rank * key_cap);
+        dst[0] = v0;
+        for (uint32_t g = 1; g < ng; ++g) dst[g] = rec[2 + g];
+        // the tag block's two header bytes (tag_block_match's reads and checks)
+        if (o + 2 <= vlen) {
+          const uint32_t ga = o >> 4, gb = (o + 1) >> 4;
+          const uint4 a = ga ? rec[2 + ga] : v0;
+          const uint4 b = gb != ga ? rec[2 + gb] : a;
+          if (granule_byte(a, o & 15u) == (uint32_t)kTagMarker) {
+            const uint32_t nt = granule_byte(b, (o + 1) & 15u);
+            if (nt == kTagOverflow || (nt <= kMaxObjectTags && o + 2 + 8 * nt <= vlen)) ntags = nt;
+          }
+        }
+        // every load of the record has returned: is it still out of the appends' reach?
+        __threadfence();
+        uint64_t newest = 0;  // head slots 0 / 1 and the claim word 4
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const uint64_t h = __hip_atomic_load(heads + (i < 2 ? i : 4), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+          newest = h > newest ? h : newest;
+        }
+        ok = newest <= (loc - 1) + cap;
+      }
+    }
+    if (!ok) {
+      bits |= kListChanged;
+      klen = ntags = flags = 0;
+    }
+    uint4* const row = reinterpret_cast<uint4*>(rows + rank);
+    row[0] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), eb.x, eb.y);
+    row[1] = ea;
+    row[2] = make_uint4(vlen, eb.w, flags, klen);
+    row[3] = make_uint4(ntags, bits, 0u, 0u);
+    if (rank + 1 == limit && total > limit) acc[kListNext] = k + 1;
+  }
+}
+
 // Export the digests of all live entries (rebalancing / warm restore). One atomic
 // per workgroup per pass reserves the output range; lanes write in block order.
 __global__ __launch_bounds__(kBlock) void k_export(const Entry* __restrict__ index, uint64_t nslots,
@@ -4045,6 +4340,7 @@ HbmCache::~HbmCache() {
   (void)hipFree(head_);
   (void)hipFree(ctr_);
   (void)hipFree(scratch_);
+  (void)hipFree(list_ws_);
   (void)hipFree(done_ctr_);
   (void)hipFree(lb_state_);
   (void)hipFree(part_);
@@ -4908,6 +5204,75 @@ void HbmCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t 
                      expire_cap, acc);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bool exact,
+                          const uint64_t* tags, uint32_t ntags, uint64_t start_slot,
+                          uint32_t limit, uint32_t key_cap, uint32_t now, ListRow* rows,
+                          uint8_t* keys, uint64_t* out, hipStream_t s) {
+  TraceRange tr("hbm.list");
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll, "list: unknown mode");
+  if (mode == kListPrefix) {
+    SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "list prefix must hold 1..65535 bytes");
+    SH_CHECK(image, "list by prefix needs a pattern image");
+  } else {
+    plen = 0;
+    exact = false;
+  }
+  if (mode == kListTags) {
+    SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "list by tag takes 1..64 tags");
+    SH_CHECK(tags, "list by tag needs a tag list");
+  } else {
+    ntags = 0;
+  }
+  SH_CHECK(limit <= kMaxListRows, "list: at most 4096 rows a call");
+  SH_CHECK(key_cap >= kListKeyCapMin && key_cap <= kListKeyCapMax && key_cap % 16 == 0,
+           "list: key_cap must be a multiple of 16 in 16..1024");
+  SH_CHECK(start_slot <= nslots, "list: the start slot lies past the index");
+  SH_CHECK(out && (limit == 0 || (rows && keys)), "list needs result words, rows and a key buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  DeviceGuard g(cfg_.device);
+  // (not refused while a phase-1 batch is pending: nothing is written)
+  const uint64_t ntiles = (nslots + kBlock - 1) / kBlock;
+  // (tile counts, bases and ranks are 32-bit words)
+  SH_CHECK(nslots < (1ull << 32) && ntiles + 4 < (1ull << 32), "list: the index is too large");
+  const uint32_t ntiles4 = (uint32_t)((ntiles + 3) & ~3ull);
+  const size_t bitmap_bytes = ntiles * (kBlock / 64) * sizeof(unsigned long long);
+  const size_t cnt_bytes = (size_t)ntiles4 * sizeof(uint32_t);  // (a multiple of 16)
+  if (!list_ws_) {
+    // [match bitmap | tile counts | tile bases + the total], allocated on first use
+    HIP_OK(hipMalloc(&list_ws_, bitmap_bytes + 2 * cnt_bytes + 16));
+  }
+  unsigned long long* const bitmap = reinterpret_cast<unsigned long long*>(list_ws_);
+  uint32_t* const tile_cnt = reinterpret_cast<uint32_t*>(list_ws_ + bitmap_bytes);
+  uint32_t* const tile_base = tile_cnt + ntiles4;
+  unsigned long long* const acc = scratch_ + 12;  // (0..11: sweep, export, the purges)
+  HIP_OK(hipMemsetAsync(acc, 0, kListWords * sizeof(unsigned long long), s));
+  // (one instance per matcher: the three in one kernel cost a wave per SIMD in registers)
+  const auto scan = mode == kListPrefix ? k_list_scan<kListPrefix>
+                    : mode == kListTags ? k_list_scan<kListTags> : k_list_scan<kListAll>;
+  hipLaunchKernelGGL(scan, dim3(grid_for((int64_t)ntiles, 1, 4096)), dim3(kBlock), 0, s,
+                     index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
+                     reinterpret_cast<const uint4*>(image), plen,
+                     (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u,
+                     reinterpret_cast<const uint2*>(tags), ntags, start_slot, bitmap, tile_cnt,
+                     acc);
+  HIP_OK(hipGetLastError());
+  if (limit) {  // (0: the count-only form)
+    hipLaunchKernelGGL(k_list_tiles, dim3(1), dim3(kBlock), 0, s, tile_cnt, ntiles4, tile_base,
+                       limit, acc);
+    HIP_OK(hipGetLastError());
+    const uint64_t t0 = start_slot / kBlock;
+    if (t0 < ntiles) {
+      hipLaunchKernelGGL(k_list_emit, dim3(grid_for((int64_t)(ntiles - t0), 1, 4096)),
+                         dim3(kBlock), 0, s, index_, nslots, log_, cur_head(), head_,
+                         cfg_.log_bytes, cfg_.max_item, now, bitmap, tile_base, ntiles4,
+                         start_slot, limit, key_cap, rows, keys, acc);
+      HIP_OK(hipGetLastError());
+    }
+  }
+  HIP_OK(hipMemcpyAsync(out, acc, kListWords * sizeof(uint64_t), hipMemcpyDefault, s));
 }
 
 uint64_t HbmCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now, hipStream_t s) {

@@ -54,6 +54,7 @@ inline size_t plan_take(const std::vector<HbmReq>& q, int max_batch, TakeScratch
         break;
       case ReqKind::Fill:
       case ReqKind::Purge:
+      case ReqKind::List:  // (sees the flight's writes, and one listing runs at a time)
         return i + 1;
       case ReqKind::Barrier:
         break;
@@ -192,6 +193,49 @@ struct FanIn {
 inline bool fan_any(bool found, bool) { return found; }
 // touch: the owner's answer (the replicas follow the owner's copy)
 inline bool fan_owner(int, bool from_owner) { return from_owner; }
+
+// ---- listing ------------------------------------------------------------------------------
+// A list_objects call visits the shards in ascending order, one at a time. The cursor is
+// (shard, slot): shards before the cursor's only count (the totals cover every shard in
+// service on every page), the cursor's shard lists from its slot, later shards from slot 0,
+// each asked for the rows still wanted; once a shard has more matches than were wanted the
+// cursor for the next page is known and the rest only count.
+struct ListAsk {
+  int shard = -1;       // -1: no shard is left, the walk answers
+  uint64_t start = 0;
+  uint32_t limit = 0;   // 0: count only
+  uint32_t skipped = 0; // shards out of service passed over on the way
+};
+inline ListAsk list_next_ask(int after_shard, int cur_shard, uint64_t cur_slot, bool have_next,
+                             uint32_t wanted, uint64_t up_mask, int nshards) {
+  ListAsk a;
+  for (int k = after_shard + 1; k < nshards && k < 64; ++k) {
+    if (!((up_mask >> k) & 1)) {
+      ++a.skipped;
+      continue;
+    }
+    a.shard = k;
+    if (k >= cur_shard && !have_next) {
+      a.limit = wanted;
+      a.start = k == cur_shard ? cur_slot : 0;
+    }
+    break;
+  }
+  return a;
+}
+// A row is a hot replica, dropped from the listing on the host, if its digest's ketama owner
+// among the shards in service is another shard than the one that listed it.
+inline bool list_row_is_replica(int owner, int shard) { return owner >= 0 && owner != shard; }
+// After a shard answered `listed` of the `asked` rows with `next_slot` (nslots: it has no
+// further match): the cursor of the next page, if it is known now. Empty: go on.
+inline std::string list_cursor_after(int shard, uint32_t asked, uint32_t still_wanted,
+                                     uint64_t next_slot, uint64_t nslots, int nshards) {
+  if (!asked) return std::string();
+  if (next_slot < nslots) return hbm_cursor(shard, next_slot);
+  // exhausted exactly as the page filled: the next page starts on the next shard
+  if (!still_wanted && shard + 1 < nshards) return hbm_cursor(shard + 1, 0);
+  return std::string();
+}
 
 // ---- hot-set refresh ----------------------------------------------------------------------
 using DigestSet = std::unordered_set<Digest, DigestHash, DigestEq>;

@@ -503,6 +503,76 @@ uint64_t HostCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint
   return softened;
 }
 
+void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, bool exact,
+                           const uint64_t* tags, uint32_t ntags, uint64_t start_slot,
+                           uint32_t limit, uint32_t key_cap, uint32_t now, ListRow* rows,
+                           uint8_t* keys, uint64_t out[kListWords]) {
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll, "list: unknown mode");
+  if (mode == kListPrefix)
+    SH_CHECK(prefix && plen >= 1 && plen <= kMaxKeyedKey, "list prefix must hold 1..65535 bytes");
+  if (mode == kListTags)
+    SH_CHECK(tags && ntags >= 1 && ntags <= kMaxPurgeTags, "list by tag takes 1..64 tags");
+  SH_CHECK(limit <= kMaxListRows, "list: at most 4096 rows a call");
+  SH_CHECK(key_cap >= kListKeyCapMin && key_cap <= kListKeyCapMax && key_cap % 16 == 0,
+           "list: key_cap must be a multiple of 16 in 16..1024");
+  SH_CHECK(start_slot <= nslots, "list: the start slot lies past the index");
+  SH_CHECK(out && (limit == 0 || (rows && keys)), "list needs result words, rows and a key buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t matched = 0, bytes = 0, listed = 0, next = nslots;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    const Entry& e = index_[k];
+    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
+    const uint32_t vlen = entry_vlen(e.vlen);
+    const uint32_t vmin =
+        (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen : mode == kListTags ? 2u : 0u);
+    if (vlen < vmin || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
+    const uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
+    const uint8_t* const v = rec + kItemHeaderBytes;
+    uint16_t klen;
+    std::memcpy(&klen, v, kKeyedPrefix);
+    if (kKeyedPrefix + klen > vlen) continue;
+    if (mode == kListPrefix) {
+      if (exact ? klen != plen : klen < plen) continue;
+      if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
+    } else if (mode == kListTags) {
+      if (!keyed_tags_match(v, vlen, tags, ntags)) continue;
+    } else if (klen == 0) {
+      continue;  // (an empty key names no object)
+    }
+    ++matched;
+    bytes += item_bytes(vlen);
+    if (k < start_slot || limit == 0) continue;
+    if (listed == limit) {  // further matches remain: the cursor is the slot after the last row
+      if (next == nslots) next = rows[limit - 1].slot + 1;
+      continue;
+    }
+    ListRow& r = rows[listed];
+    std::memset(&r, 0, sizeof(r));
+    r.slot = k;
+    r.loc = e.loc;
+    r.d0 = e.d0;
+    r.d1 = e.d1;
+    r.vlen = vlen;
+    r.expire = e.expire;
+    r.flags = h.flags;
+    r.klen = klen;
+    r.ntags = keyed_ntags(v, vlen);
+    r.bits = (e.vlen & kRefBit) ? kListRefBit : 0u;
+    // the granules that hold [u16 klen | key], at most key_cap bytes (inside the record)
+    const size_t need = (kKeyedPrefix + (size_t)klen + 15) / 16 * 16;
+    std::memcpy(keys + listed * (uint64_t)key_cap, v, need < key_cap ? need : key_cap);
+    ++listed;
+  }
+  out[kListMatched] = matched;
+  out[kListBytes] = bytes;
+  out[kListListed] = listed;
+  out[kListNext] = next;
+}
+
 void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
                       const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
                       uint32_t now) {

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "keyed.h"
 #include "layout.h"
 
 namespace shellac {
@@ -50,6 +51,13 @@ class HostCache {
   // Soft tag purge: the same matcher with soften_keyed_prefix's action; returns the live matches.
   uint64_t soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
                              uint32_t expire_cap, uint32_t now);
+  // Listing (HbmCache::list_keyed, whose semantic reference this is): the same modes, checks,
+  // rows, key areas and result words, in this index's own slot order; `prefix` is the plain
+  // prefix, not a pattern image. No row is ever flagged kListChanged here.
+  void list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, bool exact,
+                  const uint64_t* tags, uint32_t ntags, uint64_t start_slot, uint32_t limit,
+                  uint32_t key_cap, uint32_t now, ListRow* rows, uint8_t* keys,
+                  uint64_t out[kListWords]);
   // In-place change of expiry (and flags, nullable) of each row's live entry, in the index
   // and in the record header (HbmCache::touch, whose semantic reference this is). With key
   // bytes (nullable with their offsets) a row only matches a keyed record of exactly that key.

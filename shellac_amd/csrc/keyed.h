@@ -161,4 +161,44 @@ inline bool keyed_tags_match(const uint8_t* v, size_t vlen, const uint64_t* list
   return tag_block_matches(reinterpret_cast<const char*>(v) + o, vlen - o, list, nlist);
 }
 
+// ---- listing (HbmCache / HostCache::list_keyed) ----------------------------------------------
+// One row per listed object, in index-slot order; row r's key area is keys + r * key_cap and
+// holds the head of the stored keyed image [u16 klen | key ...]: the granules that hold the
+// key, at most key_cap bytes (a key longer than key_cap - 2 bytes comes back truncated).
+constexpr uint32_t kMaxListRows = 4096;
+constexpr uint32_t kListKeyCapMin = 16, kListKeyCapMax = 1024;
+enum : uint32_t { kListPrefix = 0, kListTags = 1, kListAll = 2 };
+constexpr uint32_t kListRefBit = 1;   // ListRow::bits: the CLOCK reference bit
+constexpr uint32_t kListChanged = 2;  // the entry changed after it was matched (klen = 0)
+
+struct alignas(16) ListRow {
+  uint64_t slot;    // index slot
+  uint64_t loc;     // the entry's loc word (logical log offset of the record + 1)
+  uint64_t d0, d1;  // digest
+  uint32_t vlen;    // stored value bytes (the keyed image: 2 + klen + payload)
+  uint32_t expire;  // absolute expiry, 0 = never
+  uint32_t flags;   // ItemHeader::flags
+  uint32_t klen;
+  uint32_t ntags;   // 0: no or malformed tag block, kTagOverflow, else the block's count
+  uint32_t bits;    // kListRefBit | kListChanged
+  uint32_t pad[2];
+};
+static_assert(sizeof(ListRow) == 64, "ListRow is four 16-byte granules");
+
+// Result words of a listing.
+enum : int { kListMatched = 0, kListBytes = 1, kListListed = 2, kListNext = 3, kListWords = 4 };
+
+// ntags of a keyed value as ListRow reports it.
+inline uint32_t keyed_ntags(const uint8_t* v, size_t vlen) {
+  if (vlen < kKeyedPrefix) return 0;
+  uint16_t kl;
+  std::memcpy(&kl, v, kKeyedPrefix);
+  const size_t o = kKeyedPrefix + kl;
+  if (o + 2 > vlen || v[o] != kTagMarker) return 0;
+  const unsigned nt = v[o + 1];
+  if (nt == kTagOverflow) return kTagOverflow;
+  if (nt > kMaxObjectTags || o + 2 + 8 * (size_t)nt > vlen) return 0;
+  return nt;
+}
+
 }  // namespace shellac

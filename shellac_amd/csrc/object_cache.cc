@@ -1,6 +1,8 @@
 // ObjectCache: see object_cache.h.
 #include "object_cache.h"
 
+#include <algorithm>
+
 #include "keyed.h"
 
 namespace shellac {
@@ -263,6 +265,45 @@ uint64_t ObjectCache::soften_prefix(const std::string& pattern, bool exact, uint
     }
   }
   return softened;
+}
+
+ListResult ObjectCache::list(const ListQuery& q, uint32_t now) {
+  ListResult res;
+  if (!list_query_valid(q)) return res;
+  res.ok = true;
+  std::vector<ListedObject> all;
+  for (auto& sp : stripes_) {
+    Stripe& s = *sp;
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (const Obj& o : s.slots) {
+      if (!o.data || (o.expire && o.expire <= now)) continue;
+      const std::string& v = *o.data;
+      const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data());
+      if (!keyed_value_listed(b, v.size(), q)) continue;
+      ++res.matched;
+      res.bytes += v.size();
+      uint16_t kl;
+      std::memcpy(&kl, b, kKeyedPrefix);
+      ListedObject lo;
+      lo.key.assign(v.data() + kKeyedPrefix, kl);
+      if (!q.limit || (!q.after.empty() && lo.key <= q.after)) continue;
+      lo.size = (uint32_t)v.size();
+      lo.ttl = o.expire ? (int64_t)o.expire - now : -1;
+      lo.flags = o.flags;
+      const uint32_t nt = keyed_ntags(b, v.size());
+      lo.ntags = nt == kTagOverflow ? -1 : (int)nt;
+      lo.referenced = o.ref;
+      all.push_back(std::move(lo));
+    }
+  }
+  std::sort(all.begin(), all.end(),
+            [](const ListedObject& a, const ListedObject& b) { return a.key < b.key; });
+  if (all.size() > q.limit) {
+    all.resize(q.limit);
+    res.next = all.back().key;
+  }
+  res.objects = std::move(all);
+  return res;
 }
 
 uint64_t ObjectCache::purge_tags(const std::vector<uint64_t>& hashes, uint32_t now) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "digest.h"
+#include "inspect.h"
 #include "stream_buf.h"
 
 namespace shellac {
@@ -61,6 +62,11 @@ class ObjectCache {
   uint64_t purge_tags(const std::vector<uint64_t>& hashes, uint32_t now);
   uint64_t soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t expire_cap,
                        uint32_t now);
+  // Inspection (CacheBackend::list_objects): the live objects the query matches are collected
+  // under each stripe's lock and sorted by key bytes; the cursor is "after this key" (q.after:
+  // the last key of the page before; a truncated key is never handed out). ttl is left from
+  // `now`. An administrative path: simple beats fast.
+  ListResult list(const ListQuery& q, uint32_t now);
   void clear();
   ObjectCacheStats stats() const;
 

@@ -307,7 +307,8 @@ class Reactor : public Executor {
       vary_stored{0},
       vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0},
       soft_purge_requests{0}, softened_objects{0}, tag_purge_requests{0},
-      tag_purged_objects{0}, tag_softened_objects{0}, tagged_fills{0};
+      tag_purged_objects{0}, tag_softened_objects{0}, tagged_fills{0}, inspect_requests{0},
+      purge_dry_runs{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -336,6 +337,9 @@ class Reactor : public Executor {
   void hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes, bool soft_asked);
   void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                     const std::string& body);
+  void on_inspect(Client* c, Slot* s, const std::string& qs);
+  void on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
+                        const std::string* list);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
   void forward(Client* c, Slot* s);
   static std::string upstream_request(HttpParser& q);
@@ -687,13 +691,26 @@ void Reactor::on_request(Client* c) {
     return;
   }
   const std::string& method = q.method();
+  if (cfg_.inspect != "off" && method == "GET" && url.compare(0, 17, "/_shellac/objects") == 0 &&
+      (url.size() == 17 || url[17] == '?')) {
+    c->slots.push_back(std::move(s));
+    on_inspect(c, sp, url.size() > 18 ? url.substr(18) : std::string());
+    return;
+  }
   if (method == "PURGE" && cfg_.purge != "off") {
     const std::string* host = q.header("host");
     const std::string key = cfg_.key_host && host ? *host + url : url;  // as a GET's
     const std::string* mode = q.header("x-purge-mode");
     const bool prefix = mode && to_lower(*mode) == "prefix";
     const std::string* soft = q.header("x-purge-soft");
+    const std::string* dry = q.header("x-purge-dry-run");
     c->slots.push_back(std::move(s));
+    if (dry && *dry == "1") {  // (X-Purge-Soft is ignored: nothing is changed either way)
+      const bool tag = mode && to_lower(*mode) == "tag";
+      on_purge_dry_run(c, sp, key, tag ? 2 : prefix ? 1 : 0,
+                       tag && !cfg_.tag_header.empty() ? q.header(cfg_.tag_header) : nullptr);
+      return;
+    }
     if (mode && to_lower(*mode) == "tag") {
       const std::string* list = cfg_.tag_header.empty() ? nullptr : q.header(cfg_.tag_header);
       on_purge_tags(c, sp, list, soft && *soft == "1");
@@ -897,6 +914,162 @@ void Reactor::hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> 
     answer_purge(cid, seq, 200, "OK",
                  mode + "\"tags\":" + std::to_string(nt) + ",\"purged\":" + std::to_string(n) +
                      "}");
+  });
+}
+
+// PURGE with X-Purge-Dry-Run: 1: what the purge would hit, answered from the count-only list
+// (CacheBackend::list_objects with limit 0). The --purge access rule holds; nothing is removed
+// or softened and note_purge is not called, so a fill in flight is still stored. mode: 0 exact
+// (a second scan counts the Vary variants under key + '\x1f'), 1 prefix, 2 tag.
+void Reactor::on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
+                               const std::string* list) {
+  const uint64_t cid = c->id, seq = s->seq;
+  if (!purge_allowed(cfg_.purge, c->loopback)) {
+    purge_denied++;
+    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
+    return;
+  }
+  ListQuery q;
+  q.limit = 0;
+  std::string head;
+  if (mode == 2) {
+    if (cfg_.tag_header.empty()) {
+      answer_purge(cid, seq, 400, "Bad Request",
+                   "{\"mode\":\"tag\",\"error\":\"no tag header is configured\"}");
+      return;
+    }
+    q.mode = kListTags;
+    if (list) q.tags = tag_hashes_of(*list);
+    if (q.tags.empty() || q.tags.size() > kMaxPurgeTags) {
+      answer_purge(cid, seq, 400, "Bad Request",
+                   std::string("{\"mode\":\"tag\",\"error\":\"") +
+                       (q.tags.empty() ? "the request names no tags" : "more than 64 tags") + "\"}");
+      return;
+    }
+    head = "{\"mode\":\"tag\",\"dry_run\":true,\"tags\":" + std::to_string(q.tags.size()) + ",";
+  } else {
+    q.mode = kListPrefix;
+    q.pattern = key;
+    q.exact = mode == 0;
+    head = std::string("{\"mode\":\"") + (mode ? "prefix" : "exact") + "\",\"dry_run\":true,";
+  }
+  CacheBackend* be = px_->backend_.get();
+  if (!be || !px_->cfg_.cache_enabled) {
+    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
+    return;
+  }
+  purge_dry_runs++;
+  be->list_objects(q, this, [this, be, cid, seq, head, key, mode](ListResult r) {
+    if (!r.ok) {
+      answer_purge(cid, seq, 501, "Not Implemented",
+                   head + "\"error\":\"the cache tier cannot scan its keys\"}");
+      return;
+    }
+    const std::string counts = head + "\"matched\":" + std::to_string(r.matched) +
+                               ",\"bytes\":" + std::to_string(r.bytes);
+    if (mode != 0) {
+      answer_purge(cid, seq, 200, "OK", counts + "}");
+      return;
+    }
+    ListQuery v;
+    v.mode = kListPrefix;
+    v.pattern = key + '\x1f';
+    v.limit = 0;
+    be->list_objects(v, this, [this, cid, seq, counts](ListResult m) {
+      answer_purge(cid, seq, 200, "OK",
+                   counts + ",\"variants\":" + std::to_string(m.ok ? (int64_t)m.matched : -1) + "}");
+    });
+  });
+}
+
+// GET /_shellac/objects (ProxyConfig::inspect): what is cached under ?prefix=, at ?key=, with
+// one of ?tag=a,b, or at all; &limit=N objects a page (default 100), &after=<the page
+// before's "next">. Values are percent-decoded once. The cursor in "next" is written
+// percent-encoded, so it goes into &after= as it is. Objects flagged as changed by the engine
+// never reach here (the tier drops them).
+void Reactor::on_inspect(Client* c, Slot* s, const std::string& qs) {
+  const uint64_t cid = c->id, seq = s->seq;
+  if (!purge_allowed(cfg_.inspect, c->loopback)) {
+    answer_purge(cid, seq, 403, "Forbidden",
+                 "{\"error\":\"inspection is allowed from loopback only\"}");
+    return;
+  }
+  inspect_requests++;
+  InspectParams p;
+  if (!parse_inspect_query(qs, &p)) {
+    answer_purge(cid, seq, 400, "Bad Request", "{\"error\":\"bad query\"}");
+    return;
+  }
+  ListQuery q;
+  q.limit = p.limit;
+  q.after = p.after;
+  const char* mode = "all";
+  if (p.which == 1 || p.which == 2) {
+    q.mode = kListPrefix;
+    q.pattern = p.value;
+    q.exact = p.which == 2;
+    mode = q.exact ? "key" : "prefix";
+    if (q.pattern.empty() || q.pattern.size() > kMaxKeyedKey) {
+      answer_purge(cid, seq, 400, "Bad Request", "{\"error\":\"empty or oversized pattern\"}");
+      return;
+    }
+  } else if (p.which == 3) {
+    mode = "tag";
+    q.mode = kListTags;
+    if (!cfg_.tag_header.empty()) q.tags = tag_hashes_of(p.value);
+    if (q.tags.empty() || q.tags.size() > kMaxPurgeTags) {
+      answer_purge(cid, seq, 400, "Bad Request",
+                   std::string("{\"mode\":\"tag\",\"error\":\"") +
+                       (cfg_.tag_header.empty() ? "no tag header is configured"
+                        : q.tags.empty()        ? "the request names no tags"
+                                                : "more than 64 tags") + "\"}");
+      return;
+    }
+  }
+  CacheBackend* be = px_->backend_.get();
+  if (!be || !px_->cfg_.cache_enabled) {
+    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
+    return;
+  }
+  const std::string m = mode;
+  const bool grace = cfg_.grace != 0;
+  be->list_objects(q, this, [this, cid, seq, m, grace](ListResult r) {
+    if (r.bad_cursor) {
+      answer_purge(cid, seq, 400, "Bad Request", "{\"error\":\"bad cursor\"}");
+      return;
+    }
+    if (!r.ok) {
+      answer_purge(cid, seq, 501, "Not Implemented",
+                   "{\"mode\":\"" + m + "\",\"error\":\"the cache tier cannot scan its keys\"}");
+      return;
+    }
+    std::string b = "{\"mode\":\"" + m + "\",\"matched\":" + std::to_string(r.matched) +
+                    ",\"bytes\":" + std::to_string(r.bytes) +
+                    ",\"listed\":" + std::to_string(r.objects.size()) + ",\"next\":";
+    if (r.next.empty()) {
+      b += "null";
+    } else {
+      b += '"';
+      percent_encode(r.next, &b);
+      b += '"';
+    }
+    b += ",\"shards_skipped\":" + std::to_string(r.shards_skipped) + ",\"objects\":[";
+    const int64_t now = (int64_t)unix_now();
+    bool first = true;
+    for (const ListedObject& o : r.objects) {
+      if (!first) b += ',';
+      first = false;
+      b += "{\"key\":\"";
+      json_escape_key(o.key, &b);
+      b += std::string("\",\"key_truncated\":") + (o.key_truncated ? "true" : "false") +
+           ",\"size\":" + std::to_string(o.size) +
+           ",\"ttl\":" + (o.ttl < 0 ? std::string("null") : std::to_string(o.ttl));
+      if (grace) b += ",\"fresh_for\":" + std::to_string((int64_t)o.flags - now);
+      b += ",\"tags\":" + std::to_string(o.ntags) +
+           ",\"referenced\":" + (o.referenced ? "true" : "false") +
+           ",\"shard\":" + std::to_string(o.shard) + "}";
+    }
+    answer_purge(cid, seq, 200, "OK", b + "]}");
   });
 }
 
@@ -2102,7 +2275,7 @@ std::string Proxy::stats_json() {
   uint64_t req = 0, hit = 0, miss = 0, ur = 0, resp = 0, bo = 0, err = 0, cl = 0, up = 0, acc = 0,
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
-           sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0;
+           sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0, insp = 0, pdr = 0;
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -2123,6 +2296,7 @@ std::string Proxy::stats_json() {
     spr += r->soft_purge_requests; sob += r->softened_objects;
     tpr += r->tag_purge_requests; tpo += r->tag_purged_objects;
     tso += r->tag_softened_objects; tgf += r->tagged_fills;
+    insp += r->inspect_requests; pdr += r->purge_dry_runs;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -2156,6 +2330,7 @@ std::string Proxy::stats_json() {
     << ",\"soft_purge_requests\":" << spr << ",\"softened_objects\":" << sob
     << ",\"tag_purge_requests\":" << tpr << ",\"tag_purged_objects\":" << tpo
     << ",\"tag_softened_objects\":" << tso << ",\"tagged_fills\":" << tgf
+    << ",\"inspect_requests\":" << insp << ",\"purge_dry_runs\":" << pdr
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
     << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]

@@ -77,6 +77,10 @@ struct ProxyConfig {
   // carries one of them; with `X-Purge-Soft: 1` and grace they are made stale instead. A
   // stored tag block is stripped from a hit whether or not the option is set.
   std::string tag_header;
+  // "off" (the default: /_shellac/objects is an ordinary URL), "loopback" or "any": who may
+  // GET /_shellac/objects, the listing of what is cached (by ?prefix=, ?key=, ?tag=a,b or
+  // everything, &limit= and &after= to page). Read-only.
+  std::string inspect = "off";
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
   bool key_host = false;

@@ -786,6 +786,87 @@ class CacheShard:
                                      out.data_ptr(), self._s())
         return int(out.item())  # (waits for the stream)
 
+    def list_keyed(self, prefix: Optional[bytes] = None, tags: Optional[Sequence[bytes]] = None,
+                   exact: bool = False, start: int = 0, limit: int = 100, key_cap: int = 256,
+                   now: Optional[int] = None) -> dict:
+        """List the live keyed objects whose stored key starts with ``prefix`` (``exact``:
+        equals it), or that carry one of ``tags`` (``remove_keyed_tags``' matcher), or, with
+        neither, all of them. Read-only: the index, the log and the counters stay as they
+        are. Returns ``{"matched", "bytes", "next", "rows"}``: the live matches in the whole
+        shard and their item bytes (what a hard purge of the same pattern would remove), and
+        up to ``limit`` (0..MAX_LIST_ROWS; 0 only counts) row dicts for the matches at index
+        slots >= ``start``, in slot order. ``next`` is the ``start`` of the following page, or
+        ``None`` when no match lies past the last row. A row holds ``slot``, ``loc``,
+        ``digest`` (lo, hi), ``vlen``, ``expire``, ``flags``, ``klen``, ``ntags`` (0: no or
+        malformed tag block, 0xff: the overflow block), ``referenced`` (the CLOCK bit),
+        ``changed`` and ``key``: the first ``min(klen, key_cap - 2)`` key bytes (``key_cap``: a
+        multiple of 16 in 16..1024; ``truncated`` tells a longer key). Synchronises, like
+        ``remove_keyed_prefix``; on a GPU shard ``k_list_scan`` / ``k_list_emit`` do the work.
+        ``changed`` rows (klen 0, no key) occur only beside SETs on another stream.
+        Precondition: one listing at a time per shard (the match bitmap and the result words are
+        the shard's): listings on different streams of one shard must be ordered by the caller.
+        This method synchronises, so calls from one thread are."""
+        c = core()
+        if prefix is not None and tags is not None:
+            raise ValueError("list by prefix or by tags, not both")
+        if exact and prefix is None:
+            raise ValueError("exact needs a key")
+        limit, key_cap, start = int(limit), int(key_cap), int(start)
+        if not 0 <= limit <= c.MAX_LIST_ROWS:
+            raise ValueError("list: at most %d rows a call" % c.MAX_LIST_ROWS)
+        if key_cap % 16 or not 16 <= key_cap <= 1024:
+            raise ValueError("list: key_cap must be a multiple of 16 in 16..1024")
+        nslots = 4 * self.nbuckets
+        if not 0 <= start <= nslots:
+            raise ValueError("list: the start slot lies past the index")
+        mode, hashes = c.LIST_ALL, []
+        if prefix is not None:
+            prefix = bytes(prefix)
+            if not 1 <= len(prefix) <= 0xFFFF:
+                raise ValueError("list prefix must hold 1..65535 bytes")
+            mode = c.LIST_PREFIX
+        elif tags is not None:
+            hashes = self._tag_list(tags)
+            mode = c.LIST_TAGS
+        now = self.now() if now is None else now
+        rows = torch.zeros((max(limit, 1), c.LIST_ROW_BYTES), dtype=torch.uint8, device=self.device)
+        keys = torch.zeros((max(limit, 1), key_cap), dtype=torch.uint8, device=self.device)
+        out = torch.zeros(4, dtype=torch.int64, device=self.device)
+        if self.is_gpu:
+            image = lst = None
+            if mode == c.LIST_PREFIX:
+                img = np.frombuffer(c.keyed_prefix_image(prefix), dtype=np.uint8)
+                image = torch.from_numpy(img.copy()).to(self.device)
+            elif mode == c.LIST_TAGS:
+                lst = torch.from_numpy(np.array(hashes, dtype=np.uint64).view(np.int64))
+                lst = lst.to(self.device)
+            self._impl.list_keyed(mode, 0 if image is None else image.data_ptr(),
+                                  len(prefix) if image is not None else 0, bool(exact),
+                                  0 if lst is None else lst.data_ptr(), len(hashes), start, limit,
+                                  key_cap, now, rows.data_ptr(), keys.data_ptr(), out.data_ptr(),
+                                  self._s())
+        else:
+            self._impl.list_keyed(mode, prefix or b"", bool(exact), hashes, start, limit, key_cap,
+                                  now, rows.data_ptr(), keys.data_ptr(), out.data_ptr())
+        matched, nbytes, listed, nxt = (int(x) for x in out.tolist())  # (waits for the stream)
+        r64 = rows.cpu().numpy().view(np.uint64)
+        r32 = rows.cpu().numpy().view(np.uint32)
+        kb = keys.cpu().numpy()
+        res = []
+        for i in range(listed):
+            klen, bits = int(r32[i, 11]), int(r32[i, 13])
+            have = min(klen, key_cap - 2)
+            res.append({
+                "slot": int(r64[i, 0]), "loc": int(r64[i, 1]),
+                "digest": (int(r64[i, 2]), int(r64[i, 3])),
+                "vlen": int(r32[i, 8]), "expire": int(r32[i, 9]), "flags": int(r32[i, 10]),
+                "klen": klen, "ntags": int(r32[i, 12]),
+                "referenced": bool(bits & 1), "changed": bool(bits & 2),
+                "key": kb[i, 2:2 + have].tobytes(), "truncated": klen > have,
+            })
+        return {"matched": matched, "bytes": nbytes, "next": None if nxt >= nslots else nxt,
+                "rows": res}
+
     def sweep(self, now: Optional[int] = None) -> tuple[int, int]:
         now = self.now() if now is None else now
         return tuple(self._impl.sweep(now, self._s()) if self.is_gpu else self._impl.sweep(now))

@@ -156,7 +156,7 @@ class Server:
                  cpus: Sequence[int] = (), spin_us: int = 0, gzip_gpu: int = -1,
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
                  max_inflate_bytes: int = 64 << 20, purge: str = "off", grace: int = 0,
-                 tag_header: str = "", **backend_opts):
+                 tag_header: str = "", inspect: str = "off", **backend_opts):
         """``grace`` (seconds, 0 = off): keep cached objects that long past their TTL; a hit
         in that window is served stale at once while one background request per key
         revalidates it upstream (``If-None-Match`` / ``If-Modified-Since``) — a 304 extends
@@ -178,9 +178,16 @@ class Server:
         commas). ``PURGE`` with ``X-Purge-Mode: tag`` and that header naming 1..64 tags
         removes every object carrying one of them, whatever its URL (on the HBM tier:
         ``k_purge_tags``); with ``X-Purge-Soft: 1`` and ``grace`` they are made stale
-        instead. A response naming more than 32 distinct tags matches every tag purge."""
+        instead. A response naming more than 32 distinct tags matches every tag purge.
+        ``inspect``: who may ``GET /_shellac/objects`` (``"off"``, ``"loopback"``, ``"any"``): the
+        read-only listing of what is cached by ``?prefix=``, ``?key=``, ``?tag=a,b`` or
+        everything, ``&limit=`` objects a page, ``&after=`` the page before's ``next``. A
+        ``PURGE`` with ``X-Purge-Dry-Run: 1`` (under the ``purge`` rule) answers what the purge
+        would remove and removes nothing."""
         if purge not in ("off", "loopback", "any"):
             raise ValueError("purge must be 'off', 'loopback' or 'any'")
+        if inspect not in ("off", "loopback", "any"):
+            raise ValueError("inspect must be 'off', 'loopback' or 'any'")
         if not servers:
             raise ValueError("No upstream web servers specified.")
         self._backend = backend
@@ -200,7 +207,8 @@ class Server:
             health_fails=health_fails, cpus=[int(c) for c in cpus], spin_us=int(spin_us),
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
             max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
-            purge=purge, grace=int(grace), tag_header=str(tag_header or ""))
+            purge=purge, grace=int(grace), tag_header=str(tag_header or ""),
+            inspect=inspect)
         self._started = False
 
     @property
@@ -314,6 +322,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "commas). 'PURGE' with 'X-Purge-Mode: tag' and 'NAME: t1 t2' drops every "
                         "object carrying one of up to 64 tags (with 'X-Purge-Soft: 1' and "
                         "--grace: makes them stale). Default: off")
+    p.add_argument("--inspect", choices=["off", "loopback", "any"], default="off",
+                   help="who may GET /_shellac/objects, the read-only listing of cached objects "
+                        "by ?prefix=, ?key=, ?tag=a,b or all (&limit=N&after=CURSOR to page). "
+                        "'PURGE' with 'X-Purge-Dry-Run: 1' answers what a purge would hit. "
+                        "Default: off (the URL is forwarded like any other)")
     p.add_argument("--grace", type=int, default=0, metavar="S",
                    help="serve cached objects up to S seconds past their TTL while one "
                         "background request per key revalidates them upstream (If-None-Match / "
@@ -371,7 +384,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  cpus=parse_cpus(args.cpus), spin_us=args.spin_us,
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
                  max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
-                 grace=args.grace, tag_header=args.tag_header,
+                 grace=args.grace, tag_header=args.tag_header, inspect=args.inspect,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,
