@@ -36,6 +36,16 @@ prefix no key starts with, timed in turn with the hard prefix purge of the same 
 yardstick: both read the same lines; "count_over_purge" is the ratio of the medians), then a
 list of one family (1/16 of the objects) with limit 100 and with the maximum (4096 rows, 128-byte
 key areas).
+
+--glob: the purge by URL glob (k_purge_glob, HbmCache::remove_keyed_glob) is measured on the same
+full shard, before anything is removed ("op": "glob"), timed in turn with the hard prefix purge
+that matches nothing (its yardstick, in the same run): a glob with a literal head that matches
+nothing (`/nothing/*`: the head-granule reject, the prefix scan's reads), and one with a tail
+only (`*.nothing`: every live record's key is read to its end). Each is also given as a ratio of
+the prefix purge's median. Once every op's no-match runs are done, and before any other op
+removes anything, a glob with a head, a middle and a tail (`/fXX/*/xx*x`) removes one family
+(1/16 of the objects stored), in turn with the prefix purge of another family, over the four
+families the other ops leave alone ("glob_match", "prefix_match", "match_live_first").
 """
 from __future__ import annotations
 
@@ -131,7 +141,7 @@ def summary(ts, nbytes):
 
 
 def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False,
-        listing: bool = False) -> list:
+        listing: bool = False, glob: bool = False) -> list:
     nb = 1
     while nb * 2 < n:       # <= 50 % slot load
         nb *= 2
@@ -261,6 +271,61 @@ def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False,
                                       r["purge_nomatch"]["median_us"], 3)
         return r
 
+    def glob_image(pattern: bytes):
+        return torch.from_numpy(np.frombuffer(c.keyed_glob_image(pattern), np.uint8).copy()).to(dev)
+
+    def hard_glob(img):
+        shard._impl.remove_keyed_glob(img.data_ptr(), img.numel(), now, out.data_ptr(), stream)
+
+    def glob_nomatch_runs() -> dict:
+        nomatch = image(b"/zzz/")
+        head, tail = glob_image(b"/nothing/*"), glob_image(b"*.nothing")
+        live0 = shard.sweep(now)[0]
+        for _ in range(3):
+            hard(nomatch, 5)
+            hard_glob(head)
+            hard_glob(tail)
+        torch.cuda.synchronize(dev)
+        t_prefix, t_head, t_tail = [], [], []
+        for _ in range(iters):      # in turn: the same shard state, the same neighbours
+            for ts, fn in ((t_prefix, lambda: hard(nomatch, 5)), (t_head, lambda: hard_glob(head)),
+                           (t_tail, lambda: hard_glob(tail))):
+                ts.append(timed(fn, dev)[0])
+                assert int(out[0]) == 0
+        # a live entry costs its header and value granule 0 (64 B); the tail-only form reads
+        # the key to its end: 42..82 value bytes, the record's first 128 B
+        r = {
+            "op": "glob", "objects": n, "live": int(live0), "index_slots": nslots,
+            "purge_nomatch": summary(t_prefix, nslots * 32 + live0 * 64),
+            "glob_head_nomatch": summary(t_head, nslots * 32 + live0 * 64),
+            "glob_tail_nomatch": summary(t_tail, nslots * 32 + live0 * 128),
+        }
+        for name in ("glob_head_nomatch", "glob_tail_nomatch"):
+            r[name.replace("glob_", "") + "_over_prefix"] = round(
+                r[name]["median_us"] / r["purge_nomatch"]["median_us"], 3)
+        return r
+
+    def glob_match_runs(res: dict) -> dict:
+        live_first = live = shard.sweep(now)[0]
+        t_glob, t_prefix, removed = [], [], []
+        for f in range(FAMILIES - 4, FAMILIES):
+            if f % 2 == 0:
+                img = glob_image(b"/f%02d/*/xx*x" % f)
+                t_glob.append(timed(lambda: hard_glob(img), dev)[0])
+            else:
+                img = image(b"/f%02d/" % f)
+                t_prefix.append(timed(lambda: hard(img, 5), dev)[0])
+            removed.append(int(out[0]))
+            live -= removed[-1]
+        res.update({
+            "match_live_first": int(live_first), "match_removed": removed,
+            "glob_match": summary(t_glob, nslots * 32 + live_first * 64),
+            "prefix_match": summary(t_prefix, nslots * 32 + live_first * 64),
+        })
+        res["match_over_prefix"] = round(res["glob_match"]["median_us"] /
+                                         res["prefix_match"]["median_us"], 3)
+        return res
+
     fams = list(range(min(FAMILIES - 4, max(iters, 10))))
     results = []
     # the soft ops remove nothing: each sees the full shard throughout
@@ -270,9 +335,12 @@ def run(n: int, iters: int, dev, soft: bool = False, tags: bool = False,
             results.append(match(no_match(op, purge, args), purge, args, fams))
     if listing:
         results.append(list_runs())
+    glob_res = glob_nomatch_runs() if glob else None
     hard_ops = ([("hard-tags", hard_tags, by_tag)] if tags else []) + [("hard", hard, by_prefix)]
     # every hard op's no-match runs first, on the full shard; then the families are shared out
     pending = [(no_match(op, purge, args), purge, args) for op, purge, args in hard_ops]
+    if glob:      # the first to remove: the four families the other ops leave alone
+        results.append(glob_match_runs(glob_res))
     share = len(fams) // len(pending)
     for j, (res, purge, args) in enumerate(pending):
         results.append(match(res, purge, args, fams[j * share:(j + 1) * share]))
@@ -291,12 +359,16 @@ def main():
     ap.add_argument("--list", action="store_true",
                     help="also measure the listing (count-only and with rows) on the same full "
                          "shard, in the same run as the prefix purge that matches nothing")
+    ap.add_argument("--glob", action="store_true",
+                    help="also measure the purge by glob: two patterns that match nothing, in the "
+                         "same run as the prefix purge that matches nothing, and one that removes "
+                         "a family")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("purge_bench.py needs a GPU")
     dev = torch.device("cuda", 0)
     for n in (int(x) for x in a.objects.split(",")):
-        for res in run(n, a.iters, dev, a.soft, a.tags, a.list):
+        for res in run(n, a.iters, dev, a.soft, a.tags, a.list, a.glob):
             print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 

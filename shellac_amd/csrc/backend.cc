@@ -122,6 +122,23 @@ void DramBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stal
   if (done) done(c);
 }
 
+void DramBackend::purge_glob(const std::string& pattern, Executor*, PurgeCallback done) {
+  KeyedGlob g;
+  const int64_t n = compile_keyed_glob(pattern, &g, nullptr) ? (int64_t)cache_.purge_glob(g, now())
+                                                             : -1;
+  if (done) done(n);
+}
+
+void DramBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
+                              Executor*, PurgeCallback done) {
+  const uint32_t n = now();
+  KeyedGlob g;
+  const int64_t c = compile_keyed_glob(pattern, &g, nullptr)
+                        ? (int64_t)cache_.soften_glob(g, stale_at, keep_s ? n + keep_s : 0, n)
+                        : -1;
+  if (done) done(c);
+}
+
 void DramBackend::list_objects(const ListQuery& q, Executor*, ListCallback done) {
   if (done) done(cache_.list(q, now()));
 }
@@ -283,6 +300,29 @@ void TieredBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t st
                    [this, hashes, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
     move_purge_epoch();
     l1_->soften_tags(hashes, stale_at, keep_s, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
+    });
+  });
+}
+
+void TieredBackend::purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->purge_glob(pattern, ex, [this, pattern, ex, done = std::move(done)](int64_t n2) {
+    // as purge_prefix: L2 is clean from here on, promotions read before it are dropped
+    move_purge_epoch();
+    l1_->purge_glob(pattern, ex, [done, n2](int64_t n1) {
+      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
+    });
+  });
+}
+
+void TieredBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
+                                Executor* ex, PurgeCallback done) {
+  purges_.fetch_add(1, std::memory_order_relaxed);
+  l2_->soften_glob(pattern, stale_at, keep_s, ex,
+                   [this, pattern, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
+    move_purge_epoch();
+    l1_->soften_glob(pattern, stale_at, keep_s, ex, [done, n2](int64_t n1) {
       if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });

@@ -147,8 +147,30 @@ class CacheBackend {
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
   }
+  // Purge by glob: drop every live object whose stored key, up to its first 0x1f byte (a Vary
+  // variant goes with its base key), matches `pattern` (keyed.h: '*' is any run of bytes, '\\'
+  // makes the next byte literal, anchored at both ends). Ordered and answered as purge_prefix:
+  // the objects removed, or -1 where the tier cannot do it (the default) and for a pattern
+  // compile_keyed_glob refuses (empty, stars only, a dangling '\\', over a limit).
+  virtual void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
+    (void)pattern;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
+  // Soft purge by glob: purge_glob's matcher, soften_prefix's action and answer.
+  virtual void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
+                           Executor* ex, PurgeCallback done) {
+    (void)pattern;
+    (void)stale_at;
+    (void)keep_s;
+    if (!done) return;
+    if (ex) ex->post([done] { done(-1); });
+    else done(-1);
+  }
   // Inspection, read-only: the live objects whose stored key starts with (exact: equals)
-  // q.pattern, or that carry one of q.tags, or all of them; how many they are and their bytes
+  // q.pattern, or that carry one of q.tags, or whose key matches the glob q.pattern
+  // (kListGlob), or all of them; how many they are and their bytes
   // (per stored copy, as a purge's count), and up to q.limit of them after the cursor q.after,
   // in an order of the tier's own that a cursor pages through exactly (`next`; empty: the
   // end). `done` runs once, on `ex`'s thread (inline for synchronous backends). ok == false:
@@ -230,6 +252,9 @@ class DramBackend : public CacheBackend {
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
+  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
+  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
+                   PurgeCallback done) override;
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override;
   void flush() override;
@@ -357,6 +382,12 @@ class HbmBackend : public CacheBackend {
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
+  // The same ReqKind::Purge request carrying the compiled glob (compiled once per call, shared
+  // by the shards' requests): ordering, fan-out, hot replicas, refresh fills and purge_dirty
+  // are purge_prefix's.
+  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
+  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
+                   PurgeCallback done) override;
   // Routed like del(): to the owner, and for a hot object written through to every shard in
   // service (the answer is the owner's). Queued on the shard's stream behind the writes
   // queued before it; a flight's touches are one key-exact HbmCache::touch launch.
@@ -408,6 +439,8 @@ class HbmBackend : public CacheBackend {
     bool soft = false, exact = false;
     // Purge by tag (purge_tags / soften_tags): the hash list; `key` is empty then
     std::shared_ptr<const std::vector<uint64_t>> tags;
+    // Purge by glob (purge_glob / soften_glob): the compiled pattern; `key` is empty then
+    std::shared_ptr<const KeyedGlob> glob;
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
@@ -485,10 +518,13 @@ class HbmBackend : public CacheBackend {
   // purge_tags and soften_tags calls taken (they count in purge_started_ / purge_done_ for
   // the restore's overlap check, and are taken out of the `hbm_purges` figure)
   std::atomic<uint64_t> tag_purges_{0};
+  std::atomic<uint64_t> glob_purges_{0};  // purge_glob and soften_glob calls, counted likewise
   void purge_finish(const std::shared_ptr<Purge>& p);
   // purge_prefix and soften_prefix: `proto` (kind Purge, the pattern and the soft fields) goes
   // to every shard in service
   void purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done);
+  void soften_or_purge_glob(const std::string& pattern, bool soft, uint32_t stale_at,
+                            uint32_t keep_s, Executor* ex, PurgeCallback done);
   // list_objects' walk: asks the next shard in service, or answers
   void list_step(std::shared_ptr<ListWalk> w);
   std::atomic<uint64_t> lists_{0};
@@ -552,6 +588,9 @@ class TieredBackend : public CacheBackend {
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override;
+  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
+  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
+                   PurgeCallback done) override;
   // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
   // writes both levels). A promotion that straddles the touch is dropped, as for del(): it
   // would carry the pre-touch TTL and flags into L1.
@@ -628,6 +667,13 @@ class FaultBackend : public CacheBackend {
   void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
                    Executor* ex, PurgeCallback done) override {
     inner_->soften_tags(hashes, stale_at, keep_s, ex, std::move(done));
+  }
+  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override {
+    inner_->purge_glob(pattern, ex, std::move(done));
+  }
+  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
+                   PurgeCallback done) override {
+    inner_->soften_glob(pattern, stale_at, keep_s, ex, std::move(done));
   }
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override {

@@ -418,13 +418,42 @@ void HbmBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale
   purge_fan_out(proto, ex, std::move(done));
 }
 
+// A glob purge is the same request with the compiled pattern: compiled here, once per call.
+void HbmBackend::purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
+  soften_or_purge_glob(pattern, false, 0, 0, ex, std::move(done));
+}
+
+void HbmBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
+                             Executor* ex, PurgeCallback done) {
+  soften_or_purge_glob(pattern, true, stale_at, keep_s, ex, std::move(done));
+}
+
+void HbmBackend::soften_or_purge_glob(const std::string& pattern, bool soft, uint32_t stale_at,
+                                      uint32_t keep_s, Executor* ex, PurgeCallback done) {
+  auto g = std::make_shared<KeyedGlob>();
+  if (!compile_keyed_glob(pattern, g.get(), nullptr)) {
+    if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
+    return;
+  }
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  proto.glob = std::move(g);
+  proto.soft = soft;
+  proto.flags = stale_at;
+  proto.ttl = keep_s;
+  purge_fan_out(proto, ex, std::move(done));
+}
+
 void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done) {
-  if (proto.tags ? proto.tags->empty() || proto.tags->size() > kMaxPurgeTags
-                 : proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
+  if (proto.glob ? false
+      : proto.tags ? proto.tags->empty() || proto.tags->size() > kMaxPurgeTags
+                   : proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
     if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
     return;
   }
   if (proto.tags) tag_purges_.fetch_add(1, std::memory_order_acq_rel);  // (before started)
+  if (proto.glob) glob_purges_.fetch_add(1, std::memory_order_acq_rel);
   purge_started_.fetch_add(1, std::memory_order_acq_rel);
   auto p = std::make_shared<Purge>();
   p->ex = ex;
@@ -619,7 +648,8 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_dropped_sets", sum(&Dev::dropped));
   // (prefix purges, hard and soft: the tag purges among the calls begun are counted apart)
   const uint64_t begun = purge_started_.load(), by_tag = tag_purges_.load();
-  out->emplace_back("hbm_purges", begun - (by_tag < begun ? by_tag : begun));
+  const uint64_t by_glob = glob_purges_.load(), apart = by_tag + by_glob;
+  out->emplace_back("hbm_purges", begun - (apart < begun ? apart : begun));
   out->emplace_back("hbm_purged_objects", sum(&Dev::purged_objects));
   out->emplace_back("hbm_purged_bytes", sum(&Dev::purged_bytes));
   out->emplace_back("hbm_soft_purges", soft_purges_.load());
@@ -628,6 +658,9 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_lists", lists_.load());
   out->emplace_back("hbm_tag_purged_objects", sum(&Dev::tag_purged_objects));
   out->emplace_back("hbm_tag_softened_objects", sum(&Dev::tag_softened_objects));
+  out->emplace_back("hbm_glob_purges", by_glob);
+  out->emplace_back("hbm_glob_purged_objects", sum(&Dev::glob_purged_objects));
+  out->emplace_back("hbm_glob_softened_objects", sum(&Dev::glob_softened_objects));
   // touch requests taken, and the entries the shards' kernels updated (replicas included)
   out->emplace_back("hbm_touches", sum(&Dev::touch_reqs));
   out->emplace_back("hbm_touched", t.touched);

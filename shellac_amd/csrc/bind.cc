@@ -61,6 +61,9 @@ PYBIND11_MODULE(_shellac_core, m) {
   m.attr("LIST_PREFIX") = (int)kListPrefix;
   m.attr("LIST_TAGS") = (int)kListTags;
   m.attr("LIST_ALL") = (int)kListAll;
+  m.attr("LIST_GLOB") = (int)kListGlob;
+  m.attr("MAX_GLOB_STARS") = (int)kMaxGlobStars;
+  m.attr("MAX_GLOB_LITERAL") = (int)kMaxGlobLiteral;
   m.attr("LIST_ROW_BYTES") = (int)sizeof(ListRow);
   m.attr("MAX_LIST_ROWS") = (int)kMaxListRows;
 
@@ -85,6 +88,21 @@ PYBIND11_MODULE(_shellac_core, m) {
                              reinterpret_cast<const uint8_t*>(p.data()), p.size());
     return py::bytes(img);
   }, "pattern image of a purge prefix for HbmCache.remove_keyed_prefix");
+  m.def("keyed_glob_image", [](py::bytes pattern) {
+    const std::string p = pattern;
+    KeyedGlob g;
+    std::string why;
+    if (!compile_keyed_glob(p, &g, &why)) throw py::value_error(why);
+    return py::bytes(reinterpret_cast<const char*>(&g), keyed_glob_used_bytes(g));
+  }, "compiled glob pattern ('*' wildcards, '\\' escapes) for HbmCache.remove_keyed_glob; "
+     "ValueError on a refused pattern");
+  m.def("glob_match", [](py::bytes pattern, py::bytes key) {
+    const std::string p = pattern, k = key;
+    KeyedGlob g;
+    std::string why;
+    if (!compile_keyed_glob(p, &g, &why)) throw py::value_error(why);
+    return keyed_glob_matches(g, reinterpret_cast<const uint8_t*>(k.data()), k.size());
+  }, "the host glob matcher on a stored key (its subject ends at the first 0x1f)");
   m.def("tag_hash", [](py::bytes tag) {
     const std::string t = tag;
     return tag_hash(t);
@@ -279,7 +297,25 @@ PYBIND11_MODULE(_shellac_core, m) {
                             P<uint64_t>(out), S(s));
       }, py::arg("tags"), py::arg("ntags"), py::arg("stale_at"), py::arg("expire_cap"),
          py::arg("now"), py::arg("out"), py::arg("stream"))
-      // mode: LIST_PREFIX (image, plen, exact), LIST_TAGS (tags, ntags) or LIST_ALL; rows:
+      // image: keyed_glob_image(pattern) in device-readable memory, image_bytes its length;
+      // out: 2 words; asynchronous on the stream
+      .def("remove_keyed_glob", [](HbmCache& c, uintptr_t image, uint32_t image_bytes,
+                                   uint32_t now, uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.remove_keyed_glob(P<const uint8_t>(image), image_bytes, now, P<uint64_t>(out), S(s));
+      }, py::arg("image"), py::arg("image_bytes"), py::arg("now"), py::arg("out"),
+         py::arg("stream"))
+      // out: 1 word; asynchronous on the stream
+      .def("soften_keyed_glob", [](HbmCache& c, uintptr_t image, uint32_t image_bytes,
+                                   uint32_t stale_at, uint32_t expire_cap, uint32_t now,
+                                   uintptr_t out, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        c.soften_keyed_glob(P<const uint8_t>(image), image_bytes, stale_at, expire_cap, now,
+                            P<uint64_t>(out), S(s));
+      }, py::arg("image"), py::arg("image_bytes"), py::arg("stale_at"), py::arg("expire_cap"),
+         py::arg("now"), py::arg("out"), py::arg("stream"))
+      // mode: LIST_PREFIX (image, plen, exact), LIST_TAGS (tags, ntags), LIST_GLOB (image:
+      // keyed_glob_image's, plen: its length) or LIST_ALL; rows:
       // limit x LIST_ROW_BYTES, keys: limit x key_cap, out: 4 words {matched, bytes, listed,
       // next} (device or mapped pinned memory); asynchronous on the stream
       .def("list_keyed", [](HbmCache& c, uint32_t mode, uintptr_t image, uint32_t plen, bool exact,
@@ -526,7 +562,25 @@ PYBIND11_MODULE(_shellac_core, m) {
                                    uint32_t expire_cap, uint32_t now) {
         return c.soften_keyed_tags(tags.data(), (uint32_t)tags.size(), stale_at, expire_cap, now);
       }, py::arg("tags"), py::arg("stale_at"), py::arg("expire_cap"), py::arg("now"))
+      .def("remove_keyed_glob", [](HostCache& c, py::bytes pattern, uint32_t now) {
+        const std::string p = pattern;
+        KeyedGlob g;
+        std::string why;
+        if (!compile_keyed_glob(p, &g, &why)) throw py::value_error(why);
+        uint64_t out[2] = {0, 0};
+        c.remove_keyed_glob(g, now, out);
+        return py::make_tuple(out[0], out[1]);
+      }, py::arg("pattern"), py::arg("now"))
+      .def("soften_keyed_glob", [](HostCache& c, py::bytes pattern, uint32_t stale_at,
+                                   uint32_t expire_cap, uint32_t now) {
+        const std::string p = pattern;
+        KeyedGlob g;
+        std::string why;
+        if (!compile_keyed_glob(p, &g, &why)) throw py::value_error(why);
+        return c.soften_keyed_glob(g, stale_at, expire_cap, now);
+      }, py::arg("pattern"), py::arg("stale_at"), py::arg("expire_cap"), py::arg("now"))
       // rows, keys, out: host buffers as HbmCache.list_keyed's; prefix: the plain prefix
+      // (LIST_GLOB: the plain pattern)
       .def("list_keyed", [](HostCache& c, uint32_t mode, py::bytes prefix, bool exact,
                             std::vector<uint64_t> tags, uint64_t start, uint32_t limit,
                             uint32_t key_cap, uint32_t now, uintptr_t rows, uintptr_t keys,

@@ -291,14 +291,35 @@ void bind_net(py::module_& m) {
           be->soften_tags(hs, stale_at, keep_s, &g_inline, std::move(cb));
         });
       }, py::arg("tags"), py::arg("stale_at"), py::arg("keep_s") = 0)
-      // inspection (blocking): prefix, key (exact) or tags, none of them: everything. None: the
-      // tier cannot scan or refused the query; else a dict (next: None at the end)
+      // purge / soft purge by glob (blocking): `pattern` as keyed.h's glob ('*' wildcards);
+      // -1: the tier cannot, or the pattern is refused
+      .def("purge_glob", [](BackendHandle& h, py::bytes pattern) {
+        const std::string pat = pattern;
+        CacheBackend* be = h.be.get();
+        return blocking_purge(
+            [&](PurgeCallback cb) { be->purge_glob(pat, &g_inline, std::move(cb)); });
+      }, py::arg("pattern"))
+      .def("soften_glob", [](BackendHandle& h, py::bytes pattern, uint32_t stale_at,
+                             uint32_t keep_s) {
+        const std::string pat = pattern;
+        CacheBackend* be = h.be.get();
+        return blocking_purge([&](PurgeCallback cb) {
+          be->soften_glob(pat, stale_at, keep_s, &g_inline, std::move(cb));
+        });
+      }, py::arg("pattern"), py::arg("stale_at"), py::arg("keep_s") = 0)
+      // inspection (blocking): prefix, key (exact), tags or glob, none of them: everything. None:
+      // the tier cannot scan or refused the query; else a dict (next: None at the end)
       .def("list_objects", [](BackendHandle& h, py::object prefix, py::object key, py::object tags,
-                              uint32_t limit, const std::string& after) -> py::object {
+                              uint32_t limit, const std::string& after,
+                              py::object glob) -> py::object {
         ListQuery q;
         q.limit = limit;
         q.after = after;
-        if (!prefix.is_none() || !key.is_none()) {
+        if (!glob.is_none()) {
+          q.mode = kListGlob;
+          q.pattern = glob.cast<std::string>();
+          q.exact = !prefix.is_none() || !key.is_none() || !tags.is_none();  // (refused with them)
+        } else if (!prefix.is_none() || !key.is_none()) {
           q.mode = kListPrefix;
           q.exact = prefix.is_none();
           q.pattern = (q.exact ? key : prefix).cast<std::string>();
@@ -345,7 +366,7 @@ void bind_net(py::module_& m) {
         out["objects"] = objs;
         return out;
       }, py::arg("prefix") = py::none(), py::arg("key") = py::none(), py::arg("tags") = py::none(),
-         py::arg("limit") = 100, py::arg("after") = "")
+         py::arg("limit") = 100, py::arg("after") = "", py::arg("glob") = py::none())
       // in-place touch (blocking): 1 touched, 0 not found, -1 the tier cannot. `flags` None
       // keeps the object's flags; `digest_of`: look the key up under another key's digest (a
       // forged collision)

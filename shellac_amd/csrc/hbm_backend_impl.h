@@ -372,7 +372,7 @@ struct HbmBackend::Dev {
       migrated{0}, migrate_ns{0}, direct_jobs{0}, direct_reqs{0}, direct_fallbacks{0},
       direct_overflows{0}, direct_timeouts{0}, direct_ns{0}, purged_objects{0},
       purged_bytes{0}, touch_reqs{0}, softened_objects{0}, tag_purged_objects{0},
-      tag_softened_objects{0};
+      tag_softened_objects{0}, glob_purged_objects{0}, glob_softened_objects{0};
 
   void loop();
   bool take_batch(std::vector<Req>* out, bool* do_flush, bool* rebuilding);

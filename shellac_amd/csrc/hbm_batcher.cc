@@ -388,10 +388,12 @@ void HbmBackend::Dev::launch_fills(Flight& f) {
 // Prefix purges: after the SETs and DELETEs queued before them (a purge is its flight's last
 // request); pattern image and result words in mapped memory
 void HbmBackend::Dev::launch_purges(Flight& f) {
-  // a request's bytes in purge_img: the pattern image, or the tag list (kept 16-B aligned)
+  // a request's bytes in purge_img: the pattern image, the compiled glob's bytes in use, or
+  // the tag list (kept 16-B aligned)
   const auto img_size = [](const Req& r) {
-    return r.tags ? (r.tags->size() * sizeof(uint64_t) + 15) & ~(size_t)15
-                  : keyed_prefix_image_bytes(r.key.size());
+    return r.glob ? (size_t)keyed_glob_used_bytes(*r.glob)
+           : r.tags ? (r.tags->size() * sizeof(uint64_t) + 15) & ~(size_t)15
+                    : keyed_prefix_image_bytes(r.key.size());
   };
   size_t np = 0, img_bytes = 0;
   for (uint32_t i : f.ctls)
@@ -410,7 +412,13 @@ void HbmBackend::Dev::launch_purges(Flight& f) {
     res[0] = res[1] = 0;
     uint64_t* const out = f.purge_out.dev<uint64_t>() + 2 * j;
     const uint32_t cap = r.ttl ? f.tnow + r.ttl : 0;  // (soft: flags is stale_at, ttl keep_s)
-    if (r.tags) {
+    if (r.glob) {
+      const uint32_t nb = keyed_glob_used_bytes(*r.glob);
+      std::memcpy(f.purge_img.host<uint8_t>() + off, r.glob.get(), nb);
+      const uint8_t* const img = f.purge_img.dev<uint8_t>() + off;
+      if (r.soft) cache->soften_keyed_glob(img, nb, r.flags, cap, f.tnow, out, stream);
+      else cache->remove_keyed_glob(img, nb, f.tnow, out, stream);
+    } else if (r.tags) {
       const uint32_t nt = (uint32_t)r.tags->size();
       std::memcpy(f.purge_img.host<uint8_t>() + off, r.tags->data(), nt * sizeof(uint64_t));
       const uint64_t* const list =
@@ -443,7 +451,10 @@ void HbmBackend::Dev::launch_lists(Flight& f) {
     if (r.kind != ReqKind::List) continue;
     const ListQuery& q = r.list->q;
     const uint32_t limit = r.flags;
+    KeyedGlob glob;
+    if (q.mode == kListGlob) compile_keyed_glob(q.pattern, &glob, nullptr);  // (valid: list_objects)
     const size_t img = q.mode == kListPrefix ? keyed_prefix_image_bytes(q.pattern.size())
+                       : q.mode == kListGlob ? (size_t)keyed_glob_used_bytes(glob)
                                              : (q.tags.size() * sizeof(uint64_t) + 15) & ~(size_t)15;
     f.list_out_off = img;
     f.list_rows_off = img + 32;
@@ -456,8 +467,11 @@ void HbmBackend::Dev::launch_lists(Flight& f) {
                                q.pattern.size());
     else if (q.mode == kListTags)
       std::memcpy(h, q.tags.data(), q.tags.size() * sizeof(uint64_t));
+    else if (q.mode == kListGlob)
+      std::memcpy(h, &glob, img);
     std::memset(h + f.list_out_off, 0, 32);
-    cache->list_keyed(q.mode, d, (uint32_t)q.pattern.size(), q.exact,
+    cache->list_keyed(q.mode, d, q.mode == kListGlob ? (uint32_t)img : (uint32_t)q.pattern.size(),
+                      q.exact,
                       reinterpret_cast<const uint64_t*>(d), (uint32_t)q.tags.size(), r.list_start,
                       limit, kListBackendKeyCap, f.tnow,
                       reinterpret_cast<ListRow*>(d + f.list_rows_off), d + f.list_keys_off,
@@ -572,7 +586,9 @@ void HbmBackend::Dev::finish_ctls(Flight& f) {
     Req& r = f.reqs[i];
     if (r.kind == ReqKind::Purge) {
       const uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * pj++;
-      if (r.tags) {
+      if (r.glob) {
+        (r.soft ? glob_softened_objects : glob_purged_objects) += res[0];
+      } else if (r.tags) {
         (r.soft ? tag_softened_objects : tag_purged_objects) += res[0];
       } else if (r.soft) {
         softened_objects += res[0];

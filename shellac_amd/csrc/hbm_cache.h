@@ -285,14 +285,28 @@ class HbmCache {
   // checks (the cap lies after now; refused while a phase-1 batch waits for its phase 2).
   void soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
                          uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
+  // Glob purge of keyed values: removes every live entry whose stored key, up to its first
+  // kVarySep byte, matches the compiled pattern (keyed.h: '*' wildcards, anchored at both
+  // ends). `image`: the KeyedGlob compile_keyed_glob() wrote, `image_bytes` =
+  // keyed_glob_used_bytes() of it, 16-byte aligned, in device or mapped host memory, valid
+  // until the stream has run the call; everything else (`out`'s two words, the `purged`
+  // counter, the streams, what holds beside appends) is remove_keyed_prefix's. Uses scratch
+  // words of its own.
+  void remove_keyed_glob(const uint8_t* image, uint32_t image_bytes, uint32_t now, uint64_t* out,
+                         hipStream_t s);
+  // Soft glob purge: remove_keyed_glob's matcher, soften_keyed_prefix's action, result word and
+  // checks (the cap lies after now; refused while a phase-1 batch waits for its phase 2).
+  void soften_keyed_glob(const uint8_t* image, uint32_t image_bytes, uint32_t stale_at,
+                         uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
   // List keyed values, read-only: finds every live entry whose stored keyed value matches,
   // counts them and their item bytes over the whole index, and writes the first `limit` of them
   // at slots >= start_slot, in index-slot order, as one ListRow (keyed.h) and one key area each
   // (row r's: keys + r * key_cap, the head of the stored image [u16 klen | key ...], at most
   // key_cap bytes; bytes of the area past the key's granules are left as they are). `mode`:
   // kListPrefix (`image`, `plen`, `exact` as soften_keyed_prefix's), kListTags (`tags`, `ntags`
-  // as remove_keyed_tags') or kListAll (every plausible keyed value: 1 <= klen, 2 + klen <=
-  // vlen; an empty key names no object). limit <= kMaxListRows (0: count only, no row is
+  // as remove_keyed_tags'), kListGlob (`image`: the compiled pattern, `plen`: its bytes in
+  // use, both as remove_keyed_glob's) or kListAll (every plausible keyed value: 1 <= klen, 2 +
+  // klen <= vlen; an empty key names no object). limit <= kMaxListRows (0: count only, no row is
   // written and next = nslots); key_cap a multiple of 16 in 16..1024; start_slot <= nslots. `out` (kListWords words) receives
   // {matched, their item bytes, rows listed, next}: next is the slot after the last listed row
   // when further matches follow it (the next page's start_slot), else nslots. `rows`, `keys`

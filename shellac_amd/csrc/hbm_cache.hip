@@ -47,6 +47,10 @@
 //                  block (keyed.h, at value byte 2 + klen) holds one of up to 64 hashes, or
 //                  the overflow block, is removed; unaligned hashes come from aligned dwords.
 //   k_soften_tags  the same matcher with k_soften_prefix's action.
+//   k_purge_glob   k_purge_prefix's scan and action with a glob matcher: a record whose key,
+//                  up to its first 0x1f, matches a compiled '*' pattern (keyed.h) from end to
+//                  end: head on granule 0, tail at the subject's end, middles leftmost in order.
+//   k_soften_glob  the same matcher with k_soften_prefix's action.
 //   k_list_scan    the purges' scans and matchers, read-only, by tiles of kBlock slots: each
 //                  wave's match ballot goes into a bitmap, each tile's count into an array.
 //   k_list_tiles   one workgroup scans the tile counts; k_list_emit gives every match its
@@ -3647,6 +3651,262 @@ __global__ __launch_bounds__(kBlock) void k_soften_tags(
   }
 }
 
+// ---- purge by glob -------------------------------------------------------------------------
+// The matcher of k_purge_glob / k_soften_glob / k_list_scan<kListGlob>: keyed.h's glob
+// algorithm on a record whose header was checked (digest, vlen, magic); `v0` its value
+// granule 0, `s_img` the compiled pattern (KeyedGlob: eight header granules, then the literal
+// bytes) staged in LDS. Tests in order of cost, since a wave costs what its slowest lane
+// costs: klen against the minimum length (no memory access); the head's first 14 bytes on the
+// granule already loaded (the prefix scan's one-granule reject); the first kVarySep, which
+// ends the subject (one pass over the key's granules, a word trick per dword); the rest of
+// the head; the tail at the subject's end; the middle segments, each leftmost from where the
+// previous one ended. The record is read in aligned 16-B granules and the bytes are taken out
+// of registers (glob_byte keeps the last granule); the literals are bytes of LDS.
+// Memory safety: every byte read is value byte b < 2 + klen <= vlen, in granule b >> 4, which
+// starts below align_up(vlen, 16): inside [record + 32, record + item_bytes(vlen)) with vlen
+// <= max_item, the bounds the prefix kernels rely on. Work per record: at most klen x (longest
+// middle segment) byte compares, after one pass over the key for the separator.
+constexpr uint32_t kGlobLdsGranules = (uint32_t)(sizeof(KeyedGlob) / 16);
+
+__device__ __forceinline__ uint32_t glob_byte(const uint4* __restrict__ rec, const uint32_t b,
+                                              uint32_t& gi, uint4& g) {
+  if ((b >> 4) != gi) {
+    gi = b >> 4;
+    g = rec[2 + gi];
+  }
+  return granule_byte(g, b & 15u);
+}
+
+// 0x80 in every byte of w that equals kVarySep (exact: no carry crosses a byte).
+__device__ __forceinline__ uint32_t glob_sep_bytes(const uint32_t w) {
+  const uint32_t x = w ^ (0x01010101u * kVarySep);
+  return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+}
+
+__device__ __forceinline__ bool glob_match(const uint4* __restrict__ rec, const uint32_t vlen,
+                                           const uint4 v0, const uint4* s_img) {
+  const uint4 h0 = s_img[0], h1 = s_img[1];
+  const uint32_t nmid = h0.x < kMaxGlobStars ? h0.x : kMaxGlobStars;
+  const uint32_t head_len = h0.y, tail_len = h0.z, min_len = h0.w;
+  const uint32_t klen = v0.x & 0xffffu;
+  if (klen == 0 || klen < min_len || (uint32_t)kKeyedPrefix + klen > vlen) return false;
+  if (!purge_granule_eq(v0, s_img[2], s_img[3])) return false;
+  const uint8_t* const lit = reinterpret_cast<const uint8_t*>(s_img + 8);
+  const uint32_t* const mid = reinterpret_cast<const uint32_t*>(s_img + 4);
+  const uint32_t vend = (uint32_t)kKeyedPrefix + klen;  // the key's end, as a value byte
+  // the subject's end: the first separator in value bytes [2, 2 + klen)
+  uint32_t send = vend;
+  for (uint32_t gq = 0; gq * 16u < vend; ++gq) {
+    const uint4 q = gq ? rec[2 + gq] : v0;
+    uint32_t t0 = glob_sep_bytes(q.x);
+    if (gq == 0) t0 &= 0x80800000u;  // (the klen word is no key byte)
+    const uint32_t t1 = glob_sep_bytes(q.y), t2 = glob_sep_bytes(q.z), t3 = glob_sep_bytes(q.w);
+    if (t0 | t1 | t2 | t3) {
+      const uint32_t at = t0 ? (uint32_t)(__ffs(t0) - 1) >> 3
+                          : t1 ? 4u + ((uint32_t)(__ffs(t1) - 1) >> 3)
+                          : t2 ? 8u + ((uint32_t)(__ffs(t2) - 1) >> 3)
+                               : 12u + ((uint32_t)(__ffs(t3) - 1) >> 3);
+      const uint32_t b = gq * 16u + at;
+      if (b < vend) send = b;  // (a separator past the key is payload)
+      break;
+    }
+  }
+  const uint32_t slen = send - (uint32_t)kKeyedPrefix;
+  if (slen < min_len || slen < head_len + tail_len) return false;
+  if (h1.x == 0 && slen != head_len) return false;  // no star: the subject equals the pattern
+  uint32_t gi = 0;
+  uint4 g = v0;
+  for (uint32_t i = (uint32_t)(kPurgeGranule - kKeyedPrefix); i < head_len; ++i)
+    if (glob_byte(rec, (uint32_t)kKeyedPrefix + i, gi, g) != lit[i]) return false;
+  const uint32_t tail_off = h1.z;
+  for (uint32_t i = 0; i < tail_len; ++i)
+    if (glob_byte(rec, send - tail_len + i, gi, g) != lit[tail_off + i]) return false;
+  uint32_t cur = (uint32_t)kKeyedPrefix + head_len;  // value bytes from here on
+  const uint32_t lim = send - tail_len;
+  for (uint32_t m = 0; m < nmid; ++m) {
+    const uint32_t off = mid[2 * m], len = mid[2 * m + 1];
+    bool found = false;
+    for (; cur + len <= lim; ++cur) {
+      uint32_t j = 0;
+      while (j < len && glob_byte(rec, cur + j, gi, g) == lit[off + j]) ++j;
+      if (j == len) {
+        found = true;
+        break;
+      }
+    }
+    if (!found) return false;
+    cur += len;
+  }
+  return true;
+}
+
+// The compiled pattern: read once per workgroup into LDS (it may be mapped host memory).
+__device__ __forceinline__ void stage_glob_image(uint4* s_img, const uint4* __restrict__ img,
+                                                 const uint32_t ngran) {
+  for (uint32_t g = threadIdx.x; g < ngran && g < kGlobLdsGranules; g += kBlock) s_img[g] = img[g];
+  __syncthreads();
+}
+
+// Glob purge: remove every live entry whose stored keyed value has a key whose subject (the
+// key up to its first kVarySep) matches the compiled pattern `img` (`ngran` granules of it are
+// used). k_purge_prefix's traversal (one lane per index slot, grid-stride), liveness, record
+// re-check and action (the CAS of loc to 0, `purged`, the two result words with one add per
+// word per workgroup); only the matcher differs (glob_match, which also states the bound on
+// the work per record).
+//
+// What it relies on: what k_purge_prefix relies on, all of it unchanged. Exactness comes from
+// stream order between whole SET chains: the backend queues it between them. Beside an append
+// on another stream it only reads the log, inside [record, record + item_bytes(vlen)) with
+// vlen <= max_item and a 16-B-aligned loc (inside the log's slack), of a record that carried
+// the entry's digest, vlen and magic, and never removes a live non-matching object: the
+// removal is a CAS of the very loc that was read, so a record torn while it was compared
+// belongs to an entry the append is about to kill, and an entry a SET re-pointed keeps its new
+// loc. The ring and the log are untouched.
+__global__ __launch_bounds__(kBlock) void k_purge_glob(
+    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    const uint4* __restrict__ img, uint32_t ngran, unsigned long long* __restrict__ out,
+    CacheCounters* __restrict__ ctr) {
+  __shared__ uint4 s_img[kGlobLdsGranules];
+  stage_glob_image(s_img, img, ngran);
+  const uint32_t vmin = (uint32_t)kKeyedPrefix + s_img[0].w;
+  const uint64_t head = *head_ptr;
+  unsigned long long removed = 0, bytes = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) continue;
+    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    if (!glob_match(rec, vlen, rec[2], s_img)) continue;
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
+                  0ull) == loc) {
+      ++removed;
+      bytes += item_bytes(vlen);
+    }
+  }
+  block_count(ctr, removed, &CacheCounters::purged);
+  __shared__ unsigned long long s_res[2][kBlock / 64];
+  removed = wave_sum(removed);
+  bytes = wave_sum(bytes);
+  if ((threadIdx.x & 63) == 0) {
+    s_res[0][threadIdx.x >> 6] = removed;
+    s_res[1][threadIdx.x >> 6] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0, t1 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+      t0 += s_res[0][k];
+      t1 += s_res[1][k];
+    }
+    if (t0) atomicAdd(&out[0], t0);
+    if (t1) atomicAdd(&out[1], t1);
+  }
+}
+
+// Soft glob purge: k_purge_glob's scan and matcher, k_soften_prefix's action, word for word:
+// the record's flags become `stale_at` and an expiry of never or after `expire_cap` becomes
+// expire_cap, in the entry by a CAS of the {vlen | expire} word that keeps kRefBit (bounded
+// retries, the slot read again afterwards and the old expiry put back if it passed to another
+// entry), then in the record's ItemHeader. A life is only ever shortened. out[0] counts the
+// live matches, whether or not their words changed; no CacheCounters field.
+//
+// What it relies on: what k_soften_prefix relies on, all of it unchanged. Exactness comes from
+// stream order between whole SET chains. Beside a SET chain on another stream it stays
+// memory-safe and leaves non-matching objects alone: it writes into the log, so liveness is
+// judged at max(head, claim) (a record the queued appends will overwrite is neither written
+// nor counted), the record must carry the entry's digest, vlen and magic, every access stays
+// inside [record, record + item_bytes(vlen)), and the expiry goes in by a CAS of the word read
+// with the digest and the loc. HbmCache::soften_keyed_glob refuses while a phase-1 batch waits
+// for its phase 2 (a detached CLOCK hand rewrites that word from a staged value).
+__global__ __launch_bounds__(kBlock) void k_soften_glob(
+    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
+    uint32_t max_item, uint32_t now, const uint4* __restrict__ img, uint32_t ngran,
+    uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
+  __shared__ uint4 s_img[kGlobLdsGranules];
+  stage_glob_image(s_img, img, ngran);
+  const uint32_t vmin = (uint32_t)kKeyedPrefix + s_img[0].w;
+  // the head the queued appends reach (equal to the head slot once they have run)
+  const uint64_t hs = *head_ptr, hc = *claim_ptr;
+  const uint64_t head = hc > hs ? hc : hs;
+  unsigned long long softened = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
+       k += (uint64_t)gridDim.x * kBlock) {
+    Entry* const e = index + k;
+    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
+    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
+    const uint64_t loc = pack2(eb.x, eb.y);
+    const uint32_t vlen = entry_vlen(eb.z);
+    if (!entry_live(loc, eb.w, head, cap, now)) continue;
+    if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) continue;
+    uint8_t* const recb = log + (loc - 1) % cap;
+    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
+    const uint4 ha = rec[0], hb = rec[1];
+    // the entry's own record: digest, vlen and magic (ItemHeader's words)
+    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
+        hb.w != kItemMagic)
+      continue;
+    if (!glob_match(rec, vlen, rec[2], s_img)) continue;
+    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
+    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
+      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
+      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
+      bool done = false;
+      for (int t = 0; t < kTouchCasTries; ++t) {
+        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
+        const unsigned long long prev = atomicCAS(w, expect, want);
+        if (prev == expect) {
+          done = true;
+          break;
+        }
+        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
+        expect = prev;
+      }
+      if (!done) continue;
+      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
+      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
+        // the slot passed to another entry with an equal word: put its expiry back
+        unsigned long long cur = want;
+        for (int t = 0; t < 2; ++t) {
+          const unsigned long long prev =
+              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
+          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
+          cur = prev;
+        }
+        continue;
+      }
+      h->expire = expire_cap;
+    }
+    h->flags = stale_at;
+    ++softened;
+  }
+  __shared__ unsigned long long s_res[kBlock / 64];
+  softened = wave_sum(softened);
+  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
+    if (t0) atomicAdd(&out[0], t0);
+  }
+}
+
 // ---- listing -------------------------------------------------------------------------------
 // List: find the live entries whose stored keyed value matches, count them and their item
 // bytes over the whole index, and return the first `limit` of them at slots >= start_slot in
@@ -3695,7 +3955,8 @@ __device__ __forceinline__ bool list_slot_matches(
   const uint32_t vlen = entry_vlen(eb.z);
   if (!entry_live(loc, eb.w, head, cap, now)) return false;
   const uint32_t vmin = (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen
-                                                  : mode == kListTags ? 2u : 0u);
+                                                  : mode == kListTags ? 2u
+                                                  : mode == kListGlob ? s_img[0].w : 0u);
   if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) return false;
   const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
   const uint4 ha = rec[0], hb = rec[1];
@@ -3709,6 +3970,7 @@ __device__ __forceinline__ bool list_slot_matches(
   *vlen_out = vlen;
   if (mode == kListAll) return klen != 0;  // (an empty key names no object)
   if (mode == kListTags) return tag_block_match(rec, vlen, v0, s_tags, nlist);
+  if (mode == kListGlob) return glob_match(rec, vlen, v0, s_img);
   if (klen < plen || (exact && klen != plen)) return false;
   if (!purge_granule_eq(v0, s_img[0], s_img[2])) return false;
   const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
@@ -3735,12 +3997,15 @@ __global__ __launch_bounds__(kBlock) void k_list_scan(
     const uint2* __restrict__ tags, uint32_t nlist, uint64_t start_slot,
     unsigned long long* __restrict__ bitmap, uint32_t* __restrict__ tile_cnt,
     unsigned long long* __restrict__ acc) {
-  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
+  __shared__ uint4 s_img[mode == kListGlob ? kGlobLdsGranules : 2 + kPurgeLdsGranules];
   __shared__ uint2 s_tags[kMaxPurgeTags];
   // per-wave counts of a tile, two sets taken in turn: one barrier per tile
   __shared__ unsigned int s_cnt[2][kBlock / 64];
   if (mode == kListPrefix)
     for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
+      s_img[g] = img[g];
+  if (mode == kListGlob)  // (ngran: the granules of the compiled pattern in use)
+    for (uint32_t g = threadIdx.x; g < ngran && g < kGlobLdsGranules; g += kBlock)
       s_img[g] = img[g];
   if (mode == kListTags)
     for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s_tags[j] = tags[j];
@@ -4274,7 +4539,7 @@ HbmCache::HbmCache(const ShardConfig& cfg) : cfg_(cfg) {
   HIP_OK(hipMalloc(&index_, cfg_.nbuckets * kBucketBytes));
   HIP_OK(hipMalloc(&head_, 64));
   HIP_OK(hipMalloc(&ctr_, kCtrShards * sizeof(CacheCounters)));
-  HIP_OK(hipMalloc(&scratch_, 128));
+  HIP_OK(hipMalloc(&scratch_, 160));
   HIP_OK(hipMalloc(&done_ctr_, 64));
   HIP_OK(hipMemset(done_ctr_, 0, 64));
   const size_t lb_words = (size_t)(kSmallGetMax / kEdgeKeys + 1);
@@ -5206,16 +5471,68 @@ void HbmCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t 
   HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
 }
 
+static bool glob_image_bytes_ok(uint32_t n) {
+  return n > kGlobHeaderBytes && n <= sizeof(KeyedGlob) && n % 16 == 0;
+}
+
+void HbmCache::remove_keyed_glob(const uint8_t* image, uint32_t image_bytes, uint32_t now,
+                                 uint64_t* out, hipStream_t s) {
+  TraceRange tr("hbm.purge_glob");
+  SH_CHECK(image && glob_image_bytes_ok(image_bytes), "glob purge needs a compiled pattern");
+  SH_CHECK(out, "glob purge needs a result buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 16;  // (0..15: sweep, export, the purges, list)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_purge_glob, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock), 0,
+                     s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
+                     reinterpret_cast<const uint4*>(image), image_bytes / 16, acc, ctr_);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::soften_keyed_glob(const uint8_t* image, uint32_t image_bytes, uint32_t stale_at,
+                                 uint32_t expire_cap, uint32_t now, uint64_t* out,
+                                 hipStream_t s) {
+  TraceRange tr("hbm.soften_glob");
+  SH_CHECK(image && glob_image_bytes_ok(image_bytes), "glob purge needs a compiled pattern");
+  SH_CHECK(out, "glob purge needs a result buffer");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
+  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + 18;  // (16..17: the hard glob purge)
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL(k_soften_glob, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
+                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
+                     cfg_.max_item, now, reinterpret_cast<const uint4*>(image), image_bytes / 16,
+                     stale_at, expire_cap, acc);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
 void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bool exact,
                           const uint64_t* tags, uint32_t ntags, uint64_t start_slot,
                           uint32_t limit, uint32_t key_cap, uint32_t now, ListRow* rows,
                           uint8_t* keys, uint64_t* out, hipStream_t s) {
   TraceRange tr("hbm.list");
   const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll, "list: unknown mode");
+  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll || mode == kListGlob,
+           "list: unknown mode");
+  uint32_t ngran = (uint32_t)keyed_prefix_granules(0);  // (by tag, all: unused by the scan)
   if (mode == kListPrefix) {
     SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "list prefix must hold 1..65535 bytes");
     SH_CHECK(image, "list by prefix needs a pattern image");
+    ngran = (uint32_t)keyed_prefix_granules(plen);
+  } else if (mode == kListGlob) {
+    // (plen: the bytes of the compiled pattern in use, keyed_glob_used_bytes())
+    SH_CHECK(image && glob_image_bytes_ok(plen), "list by glob needs a compiled pattern");
+    ngran = plen / 16;
+    plen = 0;
+    exact = false;
   } else {
     plen = 0;
     exact = false;
@@ -5251,11 +5568,11 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
   HIP_OK(hipMemsetAsync(acc, 0, kListWords * sizeof(unsigned long long), s));
   // (one instance per matcher: the three in one kernel cost a wave per SIMD in registers)
   const auto scan = mode == kListPrefix ? k_list_scan<kListPrefix>
-                    : mode == kListTags ? k_list_scan<kListTags> : k_list_scan<kListAll>;
+                    : mode == kListTags ? k_list_scan<kListTags>
+                    : mode == kListGlob ? k_list_scan<kListGlob> : k_list_scan<kListAll>;
   hipLaunchKernelGGL(scan, dim3(grid_for((int64_t)ntiles, 1, 4096)), dim3(kBlock), 0, s,
                      index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
-                     reinterpret_cast<const uint4*>(image), plen,
-                     (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u,
+                     reinterpret_cast<const uint4*>(image), plen, ngran, exact ? 1u : 0u,
                      reinterpret_cast<const uint2*>(tags), ntags, start_slot, bitmap, tile_cnt,
                      acc);
   HIP_OK(hipGetLastError());

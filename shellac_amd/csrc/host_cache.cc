@@ -503,12 +503,80 @@ uint64_t HostCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint
   return softened;
 }
 
+// The record of slot k if the entry is live, its own and long enough for the pattern; else null.
+uint8_t* HostCache::glob_scan_record(uint64_t k, uint32_t now, const KeyedGlob& g,
+                                     uint32_t* vlen_out) {
+  Entry& e = index_[k];
+  if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) return nullptr;
+  const uint32_t vlen = entry_vlen(e.vlen);
+  if (vlen < kKeyedPrefix + g.min_len || vlen > max_item_ || ((e.loc - 1) & 15)) return nullptr;
+  uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+  ItemHeader h;
+  std::memcpy(&h, rec, sizeof(h));
+  if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) return nullptr;
+  *vlen_out = vlen;
+  return rec;
+}
+
+void HostCache::remove_keyed_glob(const KeyedGlob& g, uint32_t now, uint64_t out[2]) {
+  SH_CHECK(g.lit_bytes >= 1 && g.lit_bytes <= kMaxGlobLiteral, "glob purge needs a compiled pattern");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t removed = 0, bytes = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    uint32_t vlen;
+    const uint8_t* const rec = glob_scan_record(k, now, g, &vlen);
+    if (!rec || !keyed_value_glob_matches(g, rec + kItemHeaderBytes, vlen)) continue;
+    index_[k].loc = 0;
+    ++removed;
+    bytes += item_bytes(vlen);
+  }
+  ctr_.purged += removed;
+  if (out) {
+    out[0] = removed;
+    out[1] = bytes;
+  }
+}
+
+uint64_t HostCache::soften_keyed_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap,
+                                      uint32_t now) {
+  SH_CHECK(g.lit_bytes >= 1 && g.lit_bytes <= kMaxGlobLiteral, "glob purge needs a compiled pattern");
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t softened = 0;
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  for (uint64_t k = 0; k < nslots; ++k) {
+    uint32_t vlen;
+    uint8_t* const rec = glob_scan_record(k, now, g, &vlen);
+    if (!rec || !keyed_value_glob_matches(g, rec + kItemHeaderBytes, vlen)) continue;
+    Entry& e = index_[k];
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
+    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
+      e.expire = expire_cap;
+      h.expire = expire_cap;
+    }
+    h.flags = stale_at;
+    std::memcpy(rec, &h, sizeof(h));
+    ++softened;
+  }
+  return softened;
+}
+
 void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, bool exact,
                            const uint64_t* tags, uint32_t ntags, uint64_t start_slot,
                            uint32_t limit, uint32_t key_cap, uint32_t now, ListRow* rows,
                            uint8_t* keys, uint64_t out[kListWords]) {
   const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll, "list: unknown mode");
+  SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll || mode == kListGlob,
+           "list: unknown mode");
+  // (kListGlob: `prefix` is the plain pattern, compiled here)
+  KeyedGlob glob;
+  if (mode == kListGlob) {
+    std::string why;
+    SH_CHECK(prefix && compile_keyed_glob(prefix, plen, &glob, &why), "list by glob: bad pattern");
+  }
   if (mode == kListPrefix)
     SH_CHECK(prefix && plen >= 1 && plen <= kMaxKeyedKey, "list prefix must hold 1..65535 bytes");
   if (mode == kListTags)
@@ -525,7 +593,9 @@ void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, 
     if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
     const uint32_t vlen = entry_vlen(e.vlen);
     const uint32_t vmin =
-        (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen : mode == kListTags ? 2u : 0u);
+        (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen
+                                  : mode == kListTags ? 2u
+                                  : mode == kListGlob ? glob.min_len : 0u);
     if (vlen < vmin || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
     const uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
     ItemHeader h;
@@ -540,6 +610,8 @@ void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, 
       if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
     } else if (mode == kListTags) {
       if (!keyed_tags_match(v, vlen, tags, ntags)) continue;
+    } else if (mode == kListGlob) {
+      if (!keyed_value_glob_matches(glob, v, vlen)) continue;
     } else if (klen == 0) {
       continue;  // (an empty key names no object)
     }

@@ -51,9 +51,15 @@ class HostCache {
   // Soft tag purge: the same matcher with soften_keyed_prefix's action; returns the live matches.
   uint64_t soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
                              uint32_t expire_cap, uint32_t now);
+  // Glob purge and its soft form (HbmCache::remove_keyed_glob / soften_keyed_glob, whose
+  // semantic reference these are): the walks above with keyed_value_glob_matches on the
+  // compiled pattern; out and the return value as the prefix forms'.
+  void remove_keyed_glob(const KeyedGlob& g, uint32_t now, uint64_t out[2]);
+  uint64_t soften_keyed_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap,
+                             uint32_t now);
   // Listing (HbmCache::list_keyed, whose semantic reference this is): the same modes, checks,
   // rows, key areas and result words, in this index's own slot order; `prefix` is the plain
-  // prefix, not a pattern image. No row is ever flagged kListChanged here.
+  // prefix (kListGlob: the plain pattern), not a pattern image. No row is ever flagged kListChanged here.
   void list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, bool exact,
                   const uint64_t* tags, uint32_t ntags, uint64_t start_slot, uint32_t limit,
                   uint32_t key_cap, uint32_t now, ListRow* rows, uint8_t* keys,
@@ -95,6 +101,7 @@ class HostCache {
 
  private:
   uint8_t* tag_scan_record(uint64_t k, uint32_t now, uint32_t* vlen_out);
+  uint8_t* glob_scan_record(uint64_t k, uint32_t now, const KeyedGlob& g, uint32_t* vlen_out);
   struct Row {  // one SET row of a (possibly combined) batch
     Digest key;
     const uint8_t* val;

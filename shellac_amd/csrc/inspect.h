@@ -16,7 +16,8 @@
 namespace shellac {
 
 struct ListQuery {
-  uint32_t mode = kListAll;    // kListPrefix (pattern, exact), kListTags (tags) or kListAll
+  uint32_t mode = kListAll;    // kListPrefix (pattern, exact), kListTags (tags), kListGlob
+                               // (pattern: a glob, keyed.h) or kListAll
   std::string pattern;
   bool exact = false;
   std::vector<uint64_t> tags;  // tag hashes, 1..kMaxPurgeTags
@@ -45,12 +46,15 @@ struct ListResult {
 };
 
 // Whether a stored keyed value [u16 klen | key | payload] matches the query (the matcher of
-// HostCache::list_keyed, for tiers that hold whole values).
-inline bool keyed_value_listed(const uint8_t* v, size_t n, const ListQuery& q) {
+// HostCache::list_keyed, for tiers that hold whole values). kListGlob: `glob` is q.pattern
+// compiled (once per walk, by the caller); without it nothing matches.
+inline bool keyed_value_listed(const uint8_t* v, size_t n, const ListQuery& q,
+                               const KeyedGlob* glob = nullptr) {
   if (n < kKeyedPrefix) return false;
   uint16_t kl;
   std::memcpy(&kl, v, kKeyedPrefix);
   if (kKeyedPrefix + kl > n) return false;
+  if (q.mode == kListGlob) return glob && keyed_glob_matches(*glob, v + kKeyedPrefix, kl);
   if (q.mode == kListTags) return keyed_tags_match(v, n, q.tags.data(), q.tags.size());
   if (q.mode == kListAll) return kl != 0;
   if (q.exact ? kl != q.pattern.size() : kl < q.pattern.size()) return false;
@@ -61,6 +65,10 @@ inline bool list_query_valid(const ListQuery& q) {
   if (q.limit > kMaxListRows) return false;
   if (q.mode == kListPrefix) return !q.pattern.empty() && q.pattern.size() <= kMaxKeyedKey;
   if (q.mode == kListTags) return !q.tags.empty() && q.tags.size() <= kMaxPurgeTags;
+  if (q.mode == kListGlob) {  // (the pattern is checked by compiling it)
+    KeyedGlob g;
+    return !q.exact && compile_keyed_glob(q.pattern, &g, nullptr);
+  }
   return q.mode == kListAll;
 }
 
@@ -106,11 +114,12 @@ inline void percent_encode(const std::string& in, std::string* out) {
   }
 }
 
-// The parameters of GET /_shellac/objects?prefix=..|key=..|tag=a,b[&limit=N][&after=CURSOR],
-// values percent-decoded once. `which`: 0 none (all), 1 prefix, 2 key, 3 tag.
+// The parameters of GET /_shellac/objects?prefix=..|key=..|tag=a,b|glob=..[&limit=N]
+// [&after=CURSOR], values percent-decoded once. `which`: 0 none (all), 1 prefix, 2 key, 3 tag,
+// 4 glob.
 struct InspectParams {
   int which = 0;
-  std::string value;   // the prefix, the key, or the tag list as written
+  std::string value;   // the prefix, the key, the tag list or the glob as written
   uint32_t limit = 100;
   std::string after;
 };
@@ -130,7 +139,8 @@ inline bool parse_inspect_query(const std::string& qs, InspectParams* p) {
       const std::string name = item.substr(0, eq);
       std::string val;
       if (!percent_decode(eq == std::string::npos ? "" : item.substr(eq + 1), &val)) return false;
-      const int sel = name == "prefix" ? 1 : name == "key" ? 2 : name == "tag" ? 3 : 0;
+      const int sel = name == "prefix" ? 1 : name == "key" ? 2 : name == "tag" ? 3
+                      : name == "glob" ? 4 : 0;
       if (sel) {
         if (p->which) return false;
         p->which = sel;

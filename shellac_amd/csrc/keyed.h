@@ -161,13 +161,152 @@ inline bool keyed_tags_match(const uint8_t* v, size_t vlen, const uint64_t* list
   return tag_block_matches(reinterpret_cast<const char*>(v) + o, vlen - o, list, nlist);
 }
 
+// ---- glob (purge, soft purge and listing by URL wildcard) ------------------------------------
+// A pattern is a byte string: '*' matches any run of bytes (the empty run and '/' included),
+// '\' makes the next byte literal, every other byte is literal; no '?', no classes. The match
+// is anchored at both ends of the *subject*: the stored key up to, not including, its first
+// kVarySep byte (the separator vary_key puts before a variant suffix), or the whole key. A
+// Vary marker and its variants so match together, by their base key. An empty key never
+// matches. The pattern splits at its unescaped stars into a head segment (anchored at the
+// start), a tail segment (anchored at the end) and middle segments, each found leftmost, in
+// order, between the two; with no star the subject equals the pattern.
+// Refused: an empty pattern, stars only (that is flush()), a dangling '\', more than
+// kMaxGlobStars stars, more than kMaxGlobLiteral literal bytes.
+constexpr unsigned kMaxGlobStars = 8;
+constexpr unsigned kMaxGlobLiteral = 1024;  // the 1 KiB of LDS the prefix image gets
+constexpr uint8_t kVarySep = 0x1f;
+
+// The compiled pattern, as the device reads it: eight 16-byte granules of header, then the
+// literal bytes [head | middle segments in order | tail]. Empty middle segments (adjacent
+// stars) are dropped. m0 / p0 are granule 0 of write_keyed_prefix_image for the head's first
+// min(head_len, 14) bytes (all zero for an empty head: every record passes).
+struct alignas(16) KeyedGlob {
+  uint32_t nmid, head_len, tail_len, min_len;  // min_len: the sum of the segment lengths
+  uint32_t stars, lit_bytes, tail_off, pad0;   // stars == 0: the subject equals the head
+  uint8_t m0[kPurgeGranule], p0[kPurgeGranule];
+  uint32_t mid[kMaxGlobStars][2];              // (offset into lit, length), nmid < kMaxGlobStars
+  uint8_t lit[kMaxGlobLiteral];
+};
+constexpr size_t kGlobHeaderBytes = 8 * kPurgeGranule;
+static_assert(sizeof(KeyedGlob) == kGlobHeaderBytes + kMaxGlobLiteral, "glob image layout");
+
+inline size_t keyed_glob_image_bytes() { return sizeof(KeyedGlob); }
+// The bytes a scan has to read: the header and the literal bytes' granules.
+inline uint32_t keyed_glob_used_bytes(const KeyedGlob& g) {
+  return (uint32_t)(kGlobHeaderBytes + (g.lit_bytes + kPurgeGranule - 1) / kPurgeGranule *
+                                           kPurgeGranule);
+}
+
+inline bool compile_keyed_glob(const uint8_t* pat, size_t n, KeyedGlob* out, std::string* error) {
+  const auto fail = [&](const char* why) {
+    if (error) *error = why;
+    return false;
+  };
+  std::memset(out, 0, sizeof(*out));
+  if (n == 0) return fail("glob: empty pattern");
+  // segment s = lit[seg_off[s], seg_off[s + 1]); a star closes a segment
+  uint32_t seg_off[kMaxGlobStars + 2] = {0};
+  uint32_t nlit = 0, stars = 0;
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t c = pat[i];
+    if (c == '*') {
+      if (++stars > kMaxGlobStars) return fail("glob: more than 8 stars");
+      seg_off[stars] = nlit;
+      continue;
+    }
+    if (c == '\\') {
+      if (++i == n) return fail("glob: dangling backslash");
+      c = pat[i];
+    }
+    if (nlit == kMaxGlobLiteral) return fail("glob: more than 1024 literal bytes");
+    out->lit[nlit++] = c;
+  }
+  if (nlit == 0) return fail("glob: stars only (that is a flush)");
+  seg_off[stars + 1] = nlit;
+  out->stars = stars;
+  out->lit_bytes = nlit;
+  out->min_len = nlit;
+  out->head_len = seg_off[1];
+  if (stars) {
+    out->tail_off = seg_off[stars];
+    out->tail_len = nlit - seg_off[stars];
+    for (uint32_t s = 1; s < stars; ++s) {
+      const uint32_t len = seg_off[s + 1] - seg_off[s];
+      if (!len) continue;
+      out->mid[out->nmid][0] = seg_off[s];
+      out->mid[out->nmid][1] = len;
+      ++out->nmid;
+    }
+  }
+  if (out->head_len) {
+    const size_t h = out->head_len < kPurgeGranule - kKeyedPrefix ? out->head_len
+                                                                  : kPurgeGranule - kKeyedPrefix;
+    uint8_t img[3 * kPurgeGranule];  // (one granule: mask, mask, pattern)
+    write_keyed_prefix_image(img, out->lit, h);
+    std::memcpy(out->m0, img, kPurgeGranule);
+    std::memcpy(out->p0, img + 2 * kPurgeGranule, kPurgeGranule);
+  }
+  return true;
+}
+inline bool compile_keyed_glob(const std::string& pat, KeyedGlob* out, std::string* error) {
+  return compile_keyed_glob(reinterpret_cast<const uint8_t*>(pat.data()), pat.size(), out, error);
+}
+
+// Escapes a literal byte string for compile_keyed_glob: '\' and, unless keep_stars, '*'.
+inline std::string keyed_glob_escape(const std::string& s, bool keep_stars) {
+  std::string o;
+  o.reserve(s.size() + 8);
+  for (const char c : s) {
+    if (c == '\\' || (c == '*' && !keep_stars)) o.push_back('\\');
+    o.push_back(c);
+  }
+  return o;
+}
+
+// The matching algorithm on key[0..klen). Work: at most klen x (longest middle segment)
+// byte compares.
+inline bool keyed_glob_matches(const KeyedGlob& g, const uint8_t* key, size_t klen) {
+  if (klen == 0 || klen < g.min_len) return false;
+  const void* const sep = std::memchr(key, kVarySep, klen);
+  const size_t slen = sep ? (size_t)(static_cast<const uint8_t*>(sep) - key) : klen;
+  if (slen < g.min_len) return false;
+  if (g.stars == 0 && slen != g.head_len) return false;
+  if (g.head_len && std::memcmp(key, g.lit, g.head_len) != 0) return false;
+  if (g.tail_len && std::memcmp(key + slen - g.tail_len, g.lit + g.tail_off, g.tail_len) != 0)
+    return false;
+  size_t cur = g.head_len;
+  const size_t lim = slen - g.tail_len;
+  for (uint32_t m = 0; m < g.nmid && m < kMaxGlobStars; ++m) {
+    const uint8_t* const seg = g.lit + g.mid[m][0];
+    const size_t len = g.mid[m][1];
+    bool found = false;
+    for (; cur + len <= lim; ++cur)
+      if (std::memcmp(key + cur, seg, len) == 0) {
+        found = true;
+        break;
+      }
+    if (!found) return false;
+    cur += len;
+  }
+  return true;
+}
+
+// The same for a whole keyed value [u16 klen | key | payload] (keyed_tags_match's bounds).
+inline bool keyed_value_glob_matches(const KeyedGlob& g, const uint8_t* v, size_t vlen) {
+  if (vlen < kKeyedPrefix) return false;
+  uint16_t kl;
+  std::memcpy(&kl, v, kKeyedPrefix);
+  if (kKeyedPrefix + (size_t)kl > vlen) return false;
+  return keyed_glob_matches(g, v + kKeyedPrefix, kl);
+}
+
 // ---- listing (HbmCache / HostCache::list_keyed) ----------------------------------------------
 // One row per listed object, in index-slot order; row r's key area is keys + r * key_cap and
 // holds the head of the stored keyed image [u16 klen | key ...]: the granules that hold the
 // key, at most key_cap bytes (a key longer than key_cap - 2 bytes comes back truncated).
 constexpr uint32_t kMaxListRows = 4096;
 constexpr uint32_t kListKeyCapMin = 16, kListKeyCapMax = 1024;
-enum : uint32_t { kListPrefix = 0, kListTags = 1, kListAll = 2 };
+enum : uint32_t { kListPrefix = 0, kListTags = 1, kListAll = 2, kListGlob = 3 };
 constexpr uint32_t kListRefBit = 1;   // ListRow::bits: the CLOCK reference bit
 constexpr uint32_t kListChanged = 2;  // the entry changed after it was matched (klen = 0)
 

@@ -270,6 +270,8 @@ uint64_t ObjectCache::soften_prefix(const std::string& pattern, bool exact, uint
 ListResult ObjectCache::list(const ListQuery& q, uint32_t now) {
   ListResult res;
   if (!list_query_valid(q)) return res;
+  KeyedGlob glob;
+  if (q.mode == kListGlob) compile_keyed_glob(q.pattern, &glob, nullptr);
   res.ok = true;
   std::vector<ListedObject> all;
   for (auto& sp : stripes_) {
@@ -279,7 +281,7 @@ ListResult ObjectCache::list(const ListQuery& q, uint32_t now) {
       if (!o.data || (o.expire && o.expire <= now)) continue;
       const std::string& v = *o.data;
       const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data());
-      if (!keyed_value_listed(b, v.size(), q)) continue;
+      if (!keyed_value_listed(b, v.size(), q, &glob)) continue;
       ++res.matched;
       res.bytes += v.size();
       uint16_t kl;
@@ -340,6 +342,47 @@ uint64_t ObjectCache::soften_tags(const std::vector<uint64_t>& hashes, uint32_t 
       const std::string& v = *o.data;
       if (!keyed_tags_match(reinterpret_cast<const uint8_t*>(v.data()), v.size(), hashes.data(),
                             hashes.size()))
+        continue;
+      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
+      o.flags = stale_at;
+      ++softened;
+    }
+  }
+  return softened;
+}
+
+uint64_t ObjectCache::purge_glob(const KeyedGlob& g, uint32_t now) {
+  uint64_t removed = 0;
+  for (auto& sp : stripes_) {
+    Stripe& s = *sp;
+    std::vector<std::shared_ptr<const std::string>> dead;  // freed outside the stripe lock
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (size_t id = 0; id < s.slots.size(); ++id) {
+      const Obj& o = s.slots[id];
+      if (!o.data || (o.expire && o.expire <= now)) continue;
+      const std::string& v = *o.data;
+      if (!keyed_value_glob_matches(g, reinterpret_cast<const uint8_t*>(v.data()), v.size()))
+        continue;
+      if (int32_t* pos = find(s, o.d)) {
+        erase_slot(s, pos, &dead);
+        ++removed;
+      }
+    }
+  }
+  return removed;
+}
+
+uint64_t ObjectCache::soften_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap,
+                                  uint32_t now) {
+  uint64_t softened = 0;
+  for (auto& sp : stripes_) {
+    Stripe& s = *sp;
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (size_t id = 0; id < s.slots.size(); ++id) {
+      Obj& o = s.slots[id];
+      if (!o.data || (o.expire && o.expire <= now)) continue;
+      const std::string& v = *o.data;
+      if (!keyed_value_glob_matches(g, reinterpret_cast<const uint8_t*>(v.data()), v.size()))
         continue;
       if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
       o.flags = stale_at;

@@ -62,6 +62,10 @@ class ObjectCache {
   uint64_t purge_tags(const std::vector<uint64_t>& hashes, uint32_t now);
   uint64_t soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t expire_cap,
                        uint32_t now);
+  // Purge / soft purge by glob: the same walks with keyed_value_glob_matches on the compiled
+  // pattern (keyed.h: the key up to its first 0x1f, '*' wildcards, anchored at both ends).
+  uint64_t purge_glob(const KeyedGlob& g, uint32_t now);
+  uint64_t soften_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap, uint32_t now);
   // Inspection (CacheBackend::list_objects): the live objects the query matches are collected
   // under each stripe's lock and sorted by key bytes; the cursor is "after this key" (q.after:
   // the last key of the page before; a truncated key is never handed out). ttl is left from

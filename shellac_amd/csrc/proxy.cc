@@ -308,7 +308,7 @@ class Reactor : public Executor {
       vary_hits{0}, purge_requests{0}, purged_objects{0}, purge_denied{0}, fills_purged{0},
       soft_purge_requests{0}, softened_objects{0}, tag_purge_requests{0},
       tag_purged_objects{0}, tag_softened_objects{0}, tagged_fills{0}, inspect_requests{0},
-      purge_dry_runs{0};
+      purge_dry_runs{0}, purge_glob_requests{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -335,6 +335,8 @@ class Reactor : public Executor {
                   bool soft_asked);
   void on_purge_tags(Client* c, Slot* s, const std::string* list, bool soft);
   void hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes, bool soft_asked);
+  void on_purge_glob(Client* c, Slot* s, const std::string& key, bool soft);
+  void hard_purge_glob(uint64_t cid, uint64_t seq, const std::string& pattern, bool soft_asked);
   void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                     const std::string& body);
   void on_inspect(Client* c, Slot* s, const std::string& qs);
@@ -705,15 +707,20 @@ void Reactor::on_request(Client* c) {
     const std::string* soft = q.header("x-purge-soft");
     const std::string* dry = q.header("x-purge-dry-run");
     c->slots.push_back(std::move(s));
+    const bool glob = mode && to_lower(*mode) == "glob";
     if (dry && *dry == "1") {  // (X-Purge-Soft is ignored: nothing is changed either way)
       const bool tag = mode && to_lower(*mode) == "tag";
-      on_purge_dry_run(c, sp, key, tag ? 2 : prefix ? 1 : 0,
+      on_purge_dry_run(c, sp, key, glob ? 3 : tag ? 2 : prefix ? 1 : 0,
                        tag && !cfg_.tag_header.empty() ? q.header(cfg_.tag_header) : nullptr);
       return;
     }
     if (mode && to_lower(*mode) == "tag") {
       const std::string* list = cfg_.tag_header.empty() ? nullptr : q.header(cfg_.tag_header);
       on_purge_tags(c, sp, list, soft && *soft == "1");
+      return;
+    }
+    if (glob) {
+      on_purge_glob(c, sp, key, soft && *soft == "1");
       return;
     }
     on_purge(c, sp, key, prefix, soft && *soft == "1");
@@ -917,10 +924,73 @@ void Reactor::hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> 
   });
 }
 
+// PURGE with X-Purge-Mode: glob. The pattern is the request's key as formed for the other
+// modes (Host + URL with key_host, else the URL) with '*' as the wildcard: every '\\' is escaped
+// before compiling, so every other byte of the URL is literal, a '?' before a query string
+// included. An object goes when its key, up to the first '\x1f', matches (keyed.h), so a Vary
+// marker and its variants go together. A pattern the compiler refuses (stars only, more than
+// 8 stars or 1024 literal bytes) is a 400. Everything else is on a prefix purge's terms: the
+// loopback rule, note_purge before the tier is touched, X-Purge-Soft: 1 with --grace
+// (CacheBackend::soften_glob), the hard fallback answered with "soft":false, 501 from a tier
+// that cannot scan.
+void Reactor::on_purge_glob(Client* c, Slot* s, const std::string& key, bool soft) {
+  const uint64_t cid = c->id, seq = s->seq;
+  if (!purge_allowed(cfg_.purge, c->loopback)) {
+    purge_denied++;
+    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
+    return;
+  }
+  purge_requests++;
+  const std::string pattern = keyed_glob_escape(key, true);
+  auto g = std::make_shared<KeyedGlob>();
+  std::string why;
+  if (!compile_keyed_glob(pattern, g.get(), &why)) {
+    answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
+    return;
+  }
+  CacheBackend* be = px_->backend_.get();
+  if (!be || !px_->cfg_.cache_enabled) {
+    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
+    return;
+  }
+  purge_glob_requests++;
+  px_->note_purge_glob(std::move(g));  // before the tier is touched: fills in flight are refused
+  if (!soft || !cfg_.grace) {
+    hard_purge_glob(cid, seq, pattern, soft);
+    return;
+  }
+  be->soften_glob(pattern, unix_now(), cfg_.grace, this, [this, cid, seq, pattern](int64_t n) {
+    if (n < 0) {
+      hard_purge_glob(cid, seq, pattern, true);
+      return;
+    }
+    soft_purge_requests++;
+    softened_objects += (uint64_t)n;
+    answer_purge(cid, seq, 200, "OK",
+                 "{\"mode\":\"glob\",\"soft\":true,\"softened\":" + std::to_string(n) + "}");
+  });
+}
+
+void Reactor::hard_purge_glob(uint64_t cid, uint64_t seq, const std::string& pattern,
+                              bool soft_asked) {
+  const std::string mode =
+      std::string("{\"mode\":\"glob\",") + (soft_asked ? "\"soft\":false," : "");
+  px_->backend_->purge_glob(pattern, this, [this, cid, seq, mode](int64_t n) {
+    if (n < 0) {
+      answer_purge(cid, seq, 501, "Not Implemented",
+                   mode + "\"error\":\"the cache tier cannot scan its keys\"}");
+      return;
+    }
+    purged_objects += (uint64_t)n;
+    answer_purge(cid, seq, 200, "OK", mode + "\"purged\":" + std::to_string(n) + "}");
+  });
+}
+
 // PURGE with X-Purge-Dry-Run: 1: what the purge would hit, answered from the count-only list
 // (CacheBackend::list_objects with limit 0). The --purge access rule holds; nothing is removed
 // or softened and note_purge is not called, so a fill in flight is still stored. mode: 0 exact
-// (a second scan counts the Vary variants under key + '\x1f'), 1 prefix, 2 tag.
+// (a second scan counts the Vary variants under key + '\x1f'), 1 prefix, 2 tag, 3 glob (the
+// pattern formed and refused as on_purge_glob's).
 void Reactor::on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
                                const std::string* list) {
   const uint64_t cid = c->id, seq = s->seq;
@@ -947,6 +1017,16 @@ void Reactor::on_purge_dry_run(Client* c, Slot* s, const std::string& key, int m
       return;
     }
     head = "{\"mode\":\"tag\",\"dry_run\":true,\"tags\":" + std::to_string(q.tags.size()) + ",";
+  } else if (mode == 3) {
+    q.mode = kListGlob;
+    q.pattern = keyed_glob_escape(key, true);
+    KeyedGlob g;
+    std::string why;
+    if (!compile_keyed_glob(q.pattern, &g, &why)) {
+      answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
+      return;
+    }
+    head = "{\"mode\":\"glob\",\"dry_run\":true,";
   } else {
     q.mode = kListPrefix;
     q.pattern = key;
@@ -983,7 +1063,7 @@ void Reactor::on_purge_dry_run(Client* c, Slot* s, const std::string& key, int m
 }
 
 // GET /_shellac/objects (ProxyConfig::inspect): what is cached under ?prefix=, at ?key=, with
-// one of ?tag=a,b, or at all; &limit=N objects a page (default 100), &after=<the page
+// one of ?tag=a,b, matching ?glob=PATTERN, or at all; &limit=N objects a page (default 100), &after=<the page
 // before's "next">. Values are percent-decoded once. The cursor in "next" is written
 // percent-encoded, so it goes into &after= as it is. Objects flagged as changed by the engine
 // never reach here (the tier drops them).
@@ -1023,6 +1103,16 @@ void Reactor::on_inspect(Client* c, Slot* s, const std::string& qs) {
                        (cfg_.tag_header.empty() ? "no tag header is configured"
                         : q.tags.empty()        ? "the request names no tags"
                                                 : "more than 64 tags") + "\"}");
+      return;
+    }
+  } else if (p.which == 4) {  // (the pattern as written: '*' the wildcard, '\\' escapes)
+    mode = "glob";
+    q.mode = kListGlob;
+    q.pattern = p.value;
+    KeyedGlob g;
+    std::string why;
+    if (!compile_keyed_glob(q.pattern, &g, &why)) {
+      answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
       return;
     }
   }
@@ -2234,6 +2324,21 @@ void Proxy::note_purge(const std::string& pattern, bool prefix) {
   r.prefix = prefix;
   r.by_tag = false;
   r.tags.clear();
+  r.glob.reset();
+  purge_gen_.store(gen, std::memory_order_release);
+}
+
+void Proxy::note_purge_glob(std::shared_ptr<const KeyedGlob> glob) {
+  std::lock_guard<std::mutex> lk(purge_mu_);
+  if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
+  const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
+  PurgeRec& r = purge_ring_[gen % kPurgeRing];
+  r.gen = gen;
+  r.pattern.clear();
+  r.prefix = false;
+  r.by_tag = false;
+  r.tags.clear();
+  r.glob = std::move(glob);
   purge_gen_.store(gen, std::memory_order_release);
 }
 
@@ -2247,6 +2352,7 @@ void Proxy::note_purge_tags(const std::vector<uint64_t>& hashes) {
   r.prefix = false;
   r.by_tag = true;
   r.tags = hashes;
+  r.glob.reset();
   purge_gen_.store(gen, std::memory_order_release);
 }
 
@@ -2265,6 +2371,12 @@ bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string
         if (std::find(r.tags.begin(), r.tags.end(), h) != r.tags.end()) return true;
       continue;
     }
+    if (r.glob) {  // (the subject of a variant's key is its base key)
+      if (keyed_glob_matches(*r.glob, reinterpret_cast<const uint8_t*>(base_key.data()),
+                             base_key.size()))
+        return true;
+      continue;
+    }
     if (r.prefix ? key.compare(0, r.pattern.size(), r.pattern) == 0 : base_key == r.pattern)
       return true;
   }
@@ -2275,7 +2387,7 @@ std::string Proxy::stats_json() {
   uint64_t req = 0, hit = 0, miss = 0, ur = 0, resp = 0, bo = 0, err = 0, cl = 0, up = 0, acc = 0,
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
-           sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0, insp = 0, pdr = 0;
+           sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0, insp = 0, pdr = 0, pgr = 0;
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -2297,6 +2409,7 @@ std::string Proxy::stats_json() {
     tpr += r->tag_purge_requests; tpo += r->tag_purged_objects;
     tso += r->tag_softened_objects; tgf += r->tagged_fills;
     insp += r->inspect_requests; pdr += r->purge_dry_runs;
+    pgr += r->purge_glob_requests;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -2330,6 +2443,7 @@ std::string Proxy::stats_json() {
     << ",\"soft_purge_requests\":" << spr << ",\"softened_objects\":" << sob
     << ",\"tag_purge_requests\":" << tpr << ",\"tag_purged_objects\":" << tpo
     << ",\"tag_softened_objects\":" << tso << ",\"tagged_fills\":" << tgf
+    << ",\"purge_glob_requests\":" << pgr
     << ",\"inspect_requests\":" << insp << ",\"purge_dry_runs\":" << pdr
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]

@@ -76,10 +76,14 @@ struct ProxyConfig {
   // request's header of this name (the URL is ignored) and removes every object that
   // carries one of them; with `X-Purge-Soft: 1` and grace they are made stale instead. A
   // stored tag block is stripped from a hit whether or not the option is set.
+  // `PURGE` with `X-Purge-Mode: glob` (no option of its own: `purge` governs it) takes the
+  // URL's key as a pattern in which '*' matches any run of bytes and removes, or with
+  // `X-Purge-Soft: 1` and grace softens, every object whose key up to its first 0x1f matches
+  // it from end to end (keyed.h), Vary variants with their URL.
   std::string tag_header;
   // "off" (the default: /_shellac/objects is an ordinary URL), "loopback" or "any": who may
-  // GET /_shellac/objects, the listing of what is cached (by ?prefix=, ?key=, ?tag=a,b or
-  // everything, &limit= and &after= to page). Read-only.
+  // GET /_shellac/objects, the listing of what is cached (by ?prefix=, ?key=, ?tag=a,b,
+  // ?glob=PATTERN or everything, &limit= and &after= to page). Read-only.
   std::string inspect = "off";
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
@@ -144,6 +148,8 @@ class Proxy {
   uint64_t purge_generation() const { return purge_gen_.load(std::memory_order_acquire); }
   void note_purge(const std::string& pattern, bool prefix);
   void note_purge_tags(const std::vector<uint64_t>& hashes);
+  // a glob purge: a fetch whose base_key the compiled pattern matches is refused
+  void note_purge_glob(std::shared_ptr<const KeyedGlob> glob);
   // `key`: the key the object would be stored under; `base_key`: its URL key (an exact
   // purge of the URL covers every variant)
   // `tags`: the object's tag hashes (null: it has none), `overflow`: it named too many — a
@@ -175,6 +181,7 @@ class Proxy {
     bool prefix = false;
     bool by_tag = false;  // a tag purge: `tags` holds its hashes, the pattern is unused
     std::vector<uint64_t> tags;
+    std::shared_ptr<const KeyedGlob> glob;  // a glob purge: the compiled pattern, else null
   };
   std::atomic<uint64_t> purge_gen_{0};
   std::mutex purge_mu_;

@@ -786,12 +786,55 @@ class CacheShard:
                                      out.data_ptr(), self._s())
         return int(out.item())  # (waits for the stream)
 
+    def _glob_image(self, pattern: bytes) -> torch.Tensor:
+        # (ValueError on a refused pattern: empty, stars only, a dangling backslash, over a limit)
+        img = np.frombuffer(core().keyed_glob_image(bytes(pattern)), dtype=np.uint8)
+        return torch.from_numpy(img.copy()).to(self.device)
+
+    def remove_keyed_glob(self, pattern: bytes, now: Optional[int] = None) -> tuple[int, int]:
+        """Purge by glob: removes every live object whose stored key, up to its first ``0x1f``
+        byte (the separator before a Vary variant's suffix), matches ``pattern``: ``*`` is any
+        run of bytes (``/`` included), ``\\`` makes the next byte literal, every other byte is
+        literal, and the match is anchored at both ends. At most 8 stars and 1024 literal
+        bytes; an empty pattern, stars only (that is ``flush``) and a dangling ``\\`` raise
+        ``ValueError``. Returns ``(objects removed, their item bytes)``; synchronises, like
+        ``remove_keyed_prefix``. On a GPU shard ``k_purge_glob`` does the scan."""
+        image = self._glob_image(pattern)
+        now = self.now() if now is None else now
+        if not self.is_gpu:
+            removed, nbytes = self._impl.remove_keyed_glob(bytes(pattern), now)
+            return int(removed), int(nbytes)
+        out = torch.empty(2, dtype=torch.int64, device=self.device)
+        self._impl.remove_keyed_glob(image.data_ptr(), image.numel(), now, out.data_ptr(),
+                                     self._s())
+        removed, nbytes = out.tolist()  # (waits for the stream)
+        return int(removed), int(nbytes)
+
+    def soften_keyed_glob(self, pattern: bytes, stale_at: int, expire_cap: int = 0,
+                          now: Optional[int] = None) -> int:
+        """Soft purge by glob: ``remove_keyed_glob``'s matcher with ``soften_keyed_prefix``'s
+        action and contract (``flags = stale_at``, the expiry capped at ``expire_cap`` and
+        never extended, the count of live matches). Synchronises; on a GPU shard
+        ``k_soften_glob`` does the scan."""
+        image = self._glob_image(pattern)
+        now = self.now() if now is None else now
+        stale_at, expire_cap = int(stale_at) & 0xFFFFFFFF, int(expire_cap)
+        if expire_cap and expire_cap <= now:
+            raise ValueError("soft purge: the expiry cap must lie after now")
+        if not self.is_gpu:
+            return int(self._impl.soften_keyed_glob(bytes(pattern), stale_at, expire_cap, now))
+        out = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._impl.soften_keyed_glob(image.data_ptr(), image.numel(), stale_at, expire_cap, now,
+                                     out.data_ptr(), self._s())
+        return int(out.item())  # (waits for the stream)
+
     def list_keyed(self, prefix: Optional[bytes] = None, tags: Optional[Sequence[bytes]] = None,
                    exact: bool = False, start: int = 0, limit: int = 100, key_cap: int = 256,
-                   now: Optional[int] = None) -> dict:
+                   now: Optional[int] = None, glob: Optional[bytes] = None) -> dict:
         """List the live keyed objects whose stored key starts with ``prefix`` (``exact``:
-        equals it), or that carry one of ``tags`` (``remove_keyed_tags``' matcher), or, with
-        neither, all of them. Read-only: the index, the log and the counters stay as they
+        equals it), or that carry one of ``tags`` (``remove_keyed_tags``' matcher), or whose
+        key matches ``glob`` (``remove_keyed_glob``'s matcher; not with ``exact``), or, with
+        none of them, all of them. Read-only: the index, the log and the counters stay as they
         are. Returns ``{"matched", "bytes", "next", "rows"}``: the live matches in the whole
         shard and their item bytes (what a hard purge of the same pattern would remove), and
         up to ``limit`` (0..MAX_LIST_ROWS; 0 only counts) row dicts for the matches at index
@@ -809,6 +852,8 @@ class CacheShard:
         c = core()
         if prefix is not None and tags is not None:
             raise ValueError("list by prefix or by tags, not both")
+        if glob is not None and (prefix is not None or tags is not None):
+            raise ValueError("list by prefix, by tags or by glob, not two of them")
         if exact and prefix is None:
             raise ValueError("exact needs a key")
         limit, key_cap, start = int(limit), int(key_cap), int(start)
@@ -828,25 +873,32 @@ class CacheShard:
         elif tags is not None:
             hashes = self._tag_list(tags)
             mode = c.LIST_TAGS
+        elif glob is not None:
+            glob = bytes(glob)
+            image = self._glob_image(glob)
+            mode = c.LIST_GLOB
         now = self.now() if now is None else now
         rows = torch.zeros((max(limit, 1), c.LIST_ROW_BYTES), dtype=torch.uint8, device=self.device)
         keys = torch.zeros((max(limit, 1), key_cap), dtype=torch.uint8, device=self.device)
         out = torch.zeros(4, dtype=torch.int64, device=self.device)
         if self.is_gpu:
-            image = lst = None
+            lst, plen = None, 0
             if mode == c.LIST_PREFIX:
                 img = np.frombuffer(c.keyed_prefix_image(prefix), dtype=np.uint8)
                 image = torch.from_numpy(img.copy()).to(self.device)
+                plen = len(prefix)
+            elif mode == c.LIST_GLOB:
+                plen = image.numel()      # (the compiled pattern's bytes)
             elif mode == c.LIST_TAGS:
                 lst = torch.from_numpy(np.array(hashes, dtype=np.uint64).view(np.int64))
                 lst = lst.to(self.device)
-            self._impl.list_keyed(mode, 0 if image is None else image.data_ptr(),
-                                  len(prefix) if image is not None else 0, bool(exact),
+            self._impl.list_keyed(mode, image.data_ptr() if plen else 0, plen, bool(exact),
                                   0 if lst is None else lst.data_ptr(), len(hashes), start, limit,
                                   key_cap, now, rows.data_ptr(), keys.data_ptr(), out.data_ptr(),
                                   self._s())
         else:
-            self._impl.list_keyed(mode, prefix or b"", bool(exact), hashes, start, limit, key_cap,
+            self._impl.list_keyed(mode, glob if mode == c.LIST_GLOB else prefix or b"",
+                                  bool(exact), hashes, start, limit, key_cap,
                                   now, rows.data_ptr(), keys.data_ptr(), out.data_ptr())
         matched, nbytes, listed, nxt = (int(x) for x in out.tolist())  # (waits for the stream)
         r64 = rows.cpu().numpy().view(np.uint64)

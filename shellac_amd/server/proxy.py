@@ -166,7 +166,10 @@ class Server:
         ``PURGE`` request is forwarded upstream like any other method), ``"loopback"``
         (clients on 127.0.0.0/8; others get 403) or ``"any"``. ``PURGE <url>`` removes the
         URL's object and all its Vary variants; with ``X-Purge-Mode: prefix`` every object
-        whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU). With
+        whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU); with
+        ``X-Purge-Mode: glob`` every object whose key, up to a Vary variant's separator,
+        matches the URL's key as a pattern in which ``*`` is any run of bytes and everything
+        else is literal (at most 8 stars and 1024 literal bytes; ``k_purge_glob``). With
         ``X-Purge-Soft: 1`` and ``grace`` the same objects are kept and made stale instead:
         the next request is served from the stale copy and revalidated in the background,
         and their lives are capped at ``grace`` seconds from now (never extended). Without
@@ -180,7 +183,7 @@ class Server:
         ``k_purge_tags``); with ``X-Purge-Soft: 1`` and ``grace`` they are made stale
         instead. A response naming more than 32 distinct tags matches every tag purge.
         ``inspect``: who may ``GET /_shellac/objects`` (``"off"``, ``"loopback"``, ``"any"``): the
-        read-only listing of what is cached by ``?prefix=``, ``?key=``, ``?tag=a,b`` or
+        read-only listing of what is cached by ``?prefix=``, ``?key=``, ``?tag=a,b``, ``?glob=`` or
         everything, ``&limit=`` objects a page, ``&after=`` the page before's ``next``. A
         ``PURGE`` with ``X-Purge-Dry-Run: 1`` (under the ``purge`` rule) answers what the purge
         would remove and removes nothing."""
@@ -313,6 +316,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "forwarded upstream), loopback (127.0.0.0/8 only, others get 403) or "
                         "any. 'PURGE /url' drops the URL and its Vary variants; with the header "
                         "'X-Purge-Mode: prefix' everything under that URL prefix; with "
+                        "'X-Purge-Mode: glob' everything whose key matches the URL with '*' as "
+                        "a wildcard (e.g. '/img/*/thumb_*.jpg', with the Vary variants); with "
                         "'X-Purge-Soft: 1' and --grace the objects are kept and made stale "
                         "instead (served at once, revalidated in the background, gone at most "
                         "--grace seconds later)")
@@ -324,7 +329,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "--grace: makes them stale). Default: off")
     p.add_argument("--inspect", choices=["off", "loopback", "any"], default="off",
                    help="who may GET /_shellac/objects, the read-only listing of cached objects "
-                        "by ?prefix=, ?key=, ?tag=a,b or all (&limit=N&after=CURSOR to page). "
+                        "by ?prefix=, ?key=, ?tag=a,b, ?glob=PATTERN or all (&limit=N&after=CURSOR "
+                        "to page). "
                         "'PURGE' with 'X-Purge-Dry-Run: 1' answers what a purge would hit. "
                         "Default: off (the URL is forwarded like any other)")
     p.add_argument("--grace", type=int, default=0, metavar="S",
