@@ -215,6 +215,50 @@ void TieredBackend::get(const std::string& key, const Digest& d, Executor* ex, G
   });
 }
 
+PartValue slice_cache_value(bool hit, CacheValue v, const SliceSpec& spec) {
+  PartValue p;
+  if (!hit || !v.data) return p;
+  p.flags = v.flags;
+  p.ttl_left = v.ttl_left;
+  // v.data is the stored payload: [optional tag block | response]
+  const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data->data());
+  const size_t n = v.data->size();
+  const uint64_t* hs;
+  unsigned nt;
+  bool over;
+  const size_t h = parse_tag_block(v.data->data(), n, &hs, &nt, &over);
+  size_t head_len = 0;
+  if (spec.kind >= kSliceWhole || !slice_find_head_end(b + h, n - h, &head_len)) {
+    p.status = kSliceWholeObj;
+    p.window = std::move(v.data);
+    return p;
+  }
+  p.body_len = n - h - head_len;
+  uint64_t len = 0;
+  p.status = resolve_window(spec.kind, spec.a, spec.b, p.body_len, &p.first, &len) ? kSliceOk
+                                                                                   : kSliceUnsat;
+  p.head = v.data->sub(h, head_len);
+  p.window = v.data->sub(h + head_len + p.first, len);
+  return p;
+}
+
+void TieredBackend::get_part(const std::string& key, const Digest& d, const SliceSpec& spec,
+                             Executor* ex, PartCallback done) {
+  CacheBackend* l2 = l2_.get();
+  l1_->get(key, d, ex, [this, key, d, spec, ex, l2, done = std::move(done)](bool hit,
+                                                                           CacheValue v) mutable {
+    if (hit) {
+      l1_hits_.fetch_add(1, std::memory_order_relaxed);
+      done(slice_cache_value(true, std::move(v), spec));
+      return;
+    }
+    l2->get_part(key, d, spec, ex, [this, done = std::move(done)](PartValue p) {
+      (p.status != kSliceMiss ? l2_hits_ : misses_).fetch_add(1, std::memory_order_relaxed);
+      done(std::move(p));
+    });
+  });
+}
+
 void TieredBackend::set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
                         uint32_t ttl_s) {
   l2_->set(key, d, value, flags, ttl_s);

@@ -40,6 +40,7 @@
 #include "net.h"
 #include "object_cache.h"
 #include "presence_filter.h"
+#include "slice.h"
 #include "stream_buf.h"
 
 namespace shellac {
@@ -63,6 +64,19 @@ struct CacheValue {
   int64_t ttl_left = -1;  // seconds of life left: -1 unknown, 0 never expires
 };
 using GetCallback = std::function<void(bool hit, CacheValue v)>;
+// The answer of a sliced GET (slice.h): part of one stored HTTP response.
+struct PartValue {
+  uint32_t status = kSliceMiss;  // kSliceMiss / kSliceOk / kSliceUnsat / kSliceWholeObj
+  Bytes head;    // kSliceOk, kSliceUnsat: the payload from "HTTP/" through the blank line
+  Bytes window;  // the window's bytes; kSliceWholeObj: the whole value, as get() returns it
+  uint64_t body_len = 0, first = 0;
+  uint32_t flags = 0;
+  int64_t ttl_left = -1;  // as CacheValue's
+};
+using PartCallback = std::function<void(PartValue v)>;
+// A whole value, as get() answered it, sliced on the host: what every tier without a sliced
+// GET of its own answers, and what a tier that cuts on the GPU must equal.
+PartValue slice_cache_value(bool hit, CacheValue v, const SliceSpec& spec);
 using DelCallback = std::function<void(bool found)>;
 // Prefix purge: objects removed, or -1 if the tier cannot scan its keys.
 using PurgeCallback = std::function<void(int64_t removed)>;
@@ -96,6 +110,16 @@ class CacheBackend {
   virtual ~CacheBackend() = default;
   // `done` runs on `ex`'s thread (inline for synchronous backends).
   virtual void get(const std::string& key, const Digest& d, Executor* ex, GetCallback done) = 0;
+  // Sliced GET: the head and one byte window (`spec`, slice.h) of the HTTP response stored
+  // under `key`; a value that is no sliceable HTTP response, and a kSliceWhole spec, come back
+  // whole (kSliceWholeObj). Ordered and answered as get(). The default gets the whole value
+  // and cuts it on the host; HbmBackend cuts on the GPU and moves only the part.
+  virtual void get_part(const std::string& key, const Digest& d, const SliceSpec& spec,
+                        Executor* ex, PartCallback done) {
+    get(key, d, ex, [spec, done = std::move(done)](bool hit, CacheValue v) {
+      done(slice_cache_value(hit, std::move(v), spec));
+    });
+  }
   virtual void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
                    uint32_t ttl_s) = 0;
   virtual void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) = 0;
@@ -332,12 +356,14 @@ struct HbmBackendConfig {
 };
 
 // What an HbmBackend request asks of its shard's batcher. A flight runs its requests by kind,
-// in this order: GETs, SETs, DELETEs, touches, hot-replica fills, prefix purges (a barrier
+// in this order: GETs, slices, SETs, DELETEs, touches, hot-replica fills, prefix purges (a barrier
 // only reports that its flight has finished).
 // A list is a control request of its own kind: it writes nothing, so it marks no fill, no
 // shard purge_dirty and no purge generation; it is queued behind the writes queued before it
 // and launched at the end of its flight, as a purge.
-enum class ReqKind : uint8_t { Get, Set, Del, Barrier, Fill, Purge, Touch, List };
+// A slice (get_part) is a read, planned and ordered as a GET: behind the earlier writes of its
+// key, routed to a hot replica as a GET is; it goes through the batcher only.
+enum class ReqKind : uint8_t { Get, Set, Del, Barrier, Fill, Purge, Touch, List, Slice };
 // changes a key's object: ordered against the key's other requests, counted as pending
 constexpr bool is_write(ReqKind k) {
   return k == ReqKind::Set || k == ReqKind::Del || k == ReqKind::Touch;
@@ -367,6 +393,11 @@ class HbmBackend : public CacheBackend {
   explicit HbmBackend(const HbmBackendConfig& cfg);
   ~HbmBackend() override;
   void get(const std::string& key, const Digest& d, Executor* ex, GetCallback done) override;
+  // A ReqKind::Slice request, routed as a GET and never sent reactor-direct: a flight's slices
+  // are one HbmCache::get_keyed_slices launch into a pinned arena, and the answer's head and
+  // window are slices of that arena. A shard out of service is a miss.
+  void get_part(const std::string& key, const Digest& d, const SliceSpec& spec, Executor* ex,
+                PartCallback done) override;
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
@@ -445,6 +476,8 @@ class HbmBackend : public CacheBackend {
     GetCallback gcb;
     DelCallback dcb;
     TouchCallback tcb;
+    SliceSpec spec{};  // Slice: the window asked for
+    PartCallback pcb;
     // control requests (is_ctl): runs on the batcher thread once the request's flight has
     // finished on the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
@@ -528,6 +561,7 @@ class HbmBackend : public CacheBackend {
   // list_objects' walk: asks the next shard in service, or answers
   void list_step(std::shared_ptr<ListWalk> w);
   std::atomic<uint64_t> lists_{0};
+  std::atomic<uint64_t> slices_{0};  // get_part calls taken
   // ---- hot-object spreading (hot_refresh_locked documents the protocol)
   std::unique_ptr<HostRouter> router_;  // ketama owners + the published hot table
   bool hot_on_ = false;
@@ -571,6 +605,10 @@ class TieredBackend : public CacheBackend {
   TieredBackend(std::shared_ptr<CacheBackend> l1, std::shared_ptr<CacheBackend> l2,
                 uint32_t promote_ttl_s = 60, uint64_t promote_max = 32 << 10);
   void get(const std::string& key, const Digest& d, Executor* ex, GetCallback done) override;
+  // An L1 hit is sliced on the host; an L1 miss asks L2 with get_part. A partial answer never
+  // fills L1 (not even a kSliceWholeObj one: a promotion belongs to get()).
+  void get_part(const std::string& key, const Digest& d, const SliceSpec& spec, Executor* ex,
+                PartCallback done) override;
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;

@@ -269,6 +269,34 @@ void HbmBackend::get(const std::string& key, const Digest& d, Executor* ex, GetC
   enqueue(k, std::move(r));
 }
 
+void HbmBackend::get_part(const std::string& key, const Digest& d, const SliceSpec& spec,
+                          Executor* ex, PartCallback done) {
+  slices_.fetch_add(1, std::memory_order_relaxed);
+  const int k = route_get(d);
+  if (k < 0) {  // every shard ejected
+    no_shard_misses_.fetch_add(1, std::memory_order_relaxed);
+    done(PartValue{});
+    return;
+  }
+  Dev& dv = *devs_[k];
+  if (devs_.size() > 1)
+    dv.routed_gets[tl_sample_slot % Dev::kCtrShards].v.fetch_add(1, std::memory_order_relaxed);
+  if (cfg_.presence_filter && !dv.restoring.load(std::memory_order_acquire) &&
+      !std::atomic_load(&dv.filt)->maybe(d)) {
+    dv.filt_skips.fetch_add(1, std::memory_order_relaxed);  // never stored: no GPU batch
+    done(PartValue{});
+    return;
+  }
+  Req r;
+  r.kind = ReqKind::Slice;
+  r.d = d;
+  r.key = key;
+  r.spec = spec;
+  r.ex = ex;
+  r.pcb = std::move(done);
+  enqueue(k, std::move(r));  // (the batcher only: the edge server does not cut)
+}
+
 // A write goes to its owner and, for a hot object, is written through to every other shard in
 // service (write_targets; the replicas must not outlive, or die before, the owner's copy).
 // Each copy counts as pending (write_begin) until its flight is reaped or it is failed.
@@ -656,6 +684,7 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_softened_objects", sum(&Dev::softened_objects));
   out->emplace_back("hbm_tag_purges", by_tag);
   out->emplace_back("hbm_lists", lists_.load());
+  out->emplace_back("hbm_slices", slices_.load());
   out->emplace_back("hbm_tag_purged_objects", sum(&Dev::tag_purged_objects));
   out->emplace_back("hbm_tag_softened_objects", sum(&Dev::tag_softened_objects));
   out->emplace_back("hbm_glob_purges", by_glob);

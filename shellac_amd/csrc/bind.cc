@@ -66,6 +66,18 @@ PYBIND11_MODULE(_shellac_core, m) {
   m.attr("MAX_GLOB_LITERAL") = (int)kMaxGlobLiteral;
   m.attr("LIST_ROW_BYTES") = (int)sizeof(ListRow);
   m.attr("MAX_LIST_ROWS") = (int)kMaxListRows;
+  m.attr("SLICE_HEAD") = (int)kSliceHead;
+  m.attr("SLICE_RANGE") = (int)kSliceRange;
+  m.attr("SLICE_FROM") = (int)kSliceFrom;
+  m.attr("SLICE_SUFFIX") = (int)kSliceSuffix;
+  m.attr("SLICE_WHOLE") = (int)kSliceWhole;
+  m.attr("SLICE_MISS") = (int)kSliceMiss;
+  m.attr("SLICE_OK") = (int)kSliceOk;
+  m.attr("SLICE_UNSAT") = (int)kSliceUnsat;
+  m.attr("SLICE_WHOLE_OBJ") = (int)kSliceWholeObj;
+  m.attr("SLICE_HEAD_MAX") = (int)kSliceHeadMax;
+  m.attr("SLICE_ROW_BYTES") = (int)sizeof(SliceRow);
+  m.attr("SLICE_SPEC_BYTES") = (int)sizeof(SliceSpec);
 
   m.def("digest", [](py::bytes b) {
     std::string s = b;
@@ -122,6 +134,18 @@ PYBIND11_MODULE(_shellac_core, m) {
     for (unsigned i = 0; i < nt; ++i) out.push_back(tag_block_hash(hs, i));
     return py::make_tuple(strip, out, over);
   }, "(bytes to strip, hashes, overflow) of the tag block at the start of a payload");
+  m.def("resolve_window", [](uint32_t kind, uint64_t a, uint64_t b, uint64_t body_len) {
+    uint64_t first = 0, len = 0;
+    const bool ok = resolve_window(kind, a, b, body_len, &first, &len);
+    return py::make_tuple(ok, first, len);
+  }, "(satisfiable, first, length) of a window spec over a body of body_len bytes (slice.h)");
+  m.def("slice_layout", [](py::bytes value) -> py::object {
+    const std::string v = value;
+    uint32_t ho = 0, bo = 0;
+    if (!slice_layout(reinterpret_cast<const uint8_t*>(v.data()), v.size(), &ho, &bo))
+      return py::none();
+    return py::make_tuple(ho, bo);
+  }, "(head_off, body_off) of a sliceable keyed value, else None (slice.h)");
   m.def("bucket_pair", [](uint64_t lo, uint64_t hi, uint64_t nbuckets) {
     const Digest d{lo, hi};
     return std::vector<uint64_t>{bucket1(d, nbuckets - 1), bucket2(d, nbuckets - 1)};
@@ -329,6 +353,20 @@ PYBIND11_MODULE(_shellac_core, m) {
       }, py::arg("mode"), py::arg("image"), py::arg("plen"), py::arg("exact"), py::arg("tags"),
          py::arg("ntags"), py::arg("start"), py::arg("limit"), py::arg("key_cap"), py::arg("now"),
          py::arg("rows"), py::arg("keys"), py::arg("out"), py::arg("stream"))
+      // spec: n x SLICE_SPEC_BYTES, rows: n x SLICE_ROW_BYTES, res: 2 words {hits, bytes}
+      // (device or mapped pinned memory); asynchronous on the stream
+      .def("get_keyed_slices", [](HbmCache& c, uintptr_t keys, uintptr_t key_bytes,
+                                  uintptr_t key_offs, uintptr_t spec, int64_t n, uintptr_t rows,
+                                  uintptr_t out, uint64_t out_cap, uintptr_t res, uint32_t now,
+                                  uintptr_t s, uint64_t reserve) {
+        py::gil_scoped_release nogil;
+        c.get_keyed_slices(P<const Digest>(keys), P<const uint8_t>(key_bytes),
+                           P<const int64_t>(key_offs), P<const SliceSpec>(spec), n,
+                           P<SliceRow>(rows), P<uint8_t>(out), out_cap, P<uint64_t>(res), now, S(s),
+                           reserve);
+      }, py::arg("keys"), py::arg("key_bytes"), py::arg("key_offs"), py::arg("spec"), py::arg("n"),
+         py::arg("rows"), py::arg("out"), py::arg("out_cap"), py::arg("res"), py::arg("now"),
+         py::arg("stream"), py::arg("reserve") = 0)
       // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
       .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
@@ -592,6 +630,19 @@ PYBIND11_MODULE(_shellac_core, m) {
       }, py::arg("mode"), py::arg("prefix"), py::arg("exact"), py::arg("tags"), py::arg("start"),
          py::arg("limit"), py::arg("key_cap"), py::arg("now"), py::arg("rows"), py::arg("keys"),
          py::arg("out"))
+      // host buffers as HbmCache.get_keyed_slices'
+      .def("get_keyed_slices", [](HostCache& c, uintptr_t keys, uintptr_t key_bytes,
+                                  uintptr_t key_offs, uintptr_t spec, int64_t n, uintptr_t rows,
+                                  uintptr_t out, uint64_t out_cap, uintptr_t res, uint32_t now,
+                                  uint64_t reserve) {
+        py::gil_scoped_release nogil;
+        c.get_keyed_slices(P<const Digest>(keys), P<const uint8_t>(key_bytes),
+                           P<const int64_t>(key_offs), P<const SliceSpec>(spec), n,
+                           P<SliceRow>(rows), P<uint8_t>(out), out_cap, P<uint64_t>(res), now,
+                           reserve);
+      }, py::arg("keys"), py::arg("key_bytes"), py::arg("key_offs"), py::arg("spec"), py::arg("n"),
+         py::arg("rows"), py::arg("out"), py::arg("out_cap"), py::arg("res"), py::arg("now"),
+         py::arg("reserve") = 0)
       .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
                        uint32_t now) {

@@ -453,6 +453,53 @@ void bind_net(py::module_& m) {
         }
         return out;
       })
+      // sliced GETs (CacheBackend::get_part), every one issued at once, then waited for.
+      // specs: (kind, a, b) tuples with kind a SLICE_* number; one dict per key: {status (a
+      // SLICE_* status number), head, window, body_len, first, flags, ttl}. `digest_of`: look
+      // every key up under that key's digest (a forged collision)
+      .def("get_parts", [](BackendHandle& h, std::vector<std::string> keys,
+                           std::vector<std::tuple<uint32_t, uint64_t, uint64_t>> specs,
+                           py::object digest_of) {
+        const size_t n = keys.size();
+        if (specs.size() != n) throw py::value_error("one window spec per key");
+        const bool forged = !digest_of.is_none();
+        const std::string o = forged ? digest_of.cast<std::string>() : std::string();
+        std::vector<PartValue> vals(n);
+        std::mutex mu;
+        std::condition_variable cv;
+        size_t left = n;
+        {
+          py::gil_scoped_release nogil;
+          for (size_t i = 0; i < n; ++i) {
+            const std::string& dk = forged ? o : keys[i];
+            const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(dk.data()), dk.size());
+            SliceSpec sp{};
+            sp.kind = std::get<0>(specs[i]);
+            sp.a = std::get<1>(specs[i]);
+            sp.b = std::get<2>(specs[i]);
+            h.be->get_part(keys[i], d, sp, &g_inline, [&, i](PartValue v) {
+              std::lock_guard<std::mutex> lk(mu);
+              vals[i] = std::move(v);
+              if (--left == 0) cv.notify_all();
+            });
+          }
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return left == 0; });
+        }
+        py::list out;
+        for (const PartValue& v : vals) {
+          py::dict d;
+          d["status"] = v.status;
+          d["head"] = v.head ? py::bytes(v.head->data(), v.head->size()) : py::bytes();
+          d["window"] = v.window ? py::bytes(v.window->data(), v.window->size()) : py::bytes();
+          d["body_len"] = v.body_len;
+          d["first"] = v.first;
+          d["flags"] = v.flags;
+          d["ttl"] = v.ttl_left;
+          out.append(d);
+        }
+        return out;
+      }, py::arg("keys"), py::arg("specs"), py::arg("digest_of") = py::none())
       .def("flush", [](BackendHandle& h) { h.be->flush(); })
       .def("stats", [](BackendHandle& h) {
         StatList st;
@@ -585,11 +632,12 @@ void bind_net(py::module_& m) {
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
                        uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge,
                        uint32_t grace, const std::string& tag_header,
-                       const std::string& inspect) {
+                       const std::string& inspect, bool partial_hits) {
              ProxyConfig c;
              c.grace = grace;
              c.tag_header = tag_header;
              c.inspect = inspect;
+             c.partial_hits = partial_hits;
              SH_CHECK(purge == "off" || purge == "loopback" || purge == "any",
                       "purge must be off, loopback or any");
              c.purge = purge;
@@ -644,7 +692,7 @@ void bind_net(py::module_& m) {
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
            py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
            py::arg("purge") = "off", py::arg("grace") = 0, py::arg("tag_header") = "",
-           py::arg("inspect") = "off")
+           py::arg("inspect") = "off", py::arg("partial_hits") = false)
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)

@@ -215,7 +215,7 @@ struct PostGroups {
 // One batch in flight on a GPU.
 struct Flight {
   std::vector<HbmBackend::Req> reqs;
-  std::vector<uint32_t> gets, sets, dels, touches;  // request indices by kind
+  std::vector<uint32_t> gets, sets, dels, touches, slices;  // request indices by kind
   std::vector<uint32_t> ctls;              // barriers, hot-replica fills and purges
   std::vector<uint32_t> urow;              // GET request -> GPU row (host coalescing)
   size_t rows = 0;                         // distinct GET digests
@@ -232,9 +232,17 @@ struct Flight {
   // list | 4 result words | rows | key areas], at the offsets below
   Mapped list_buf;
   size_t list_out_off = 0, list_rows_off = 0, list_keys_off = 0;
+  // launch_slices: [digests | key offsets | window specs | result rows | result words | key
+  // bytes] of the flight's slices, one row per request, at the offsets below; their bytes land
+  // in an arena of their own
+  Mapped slice_buf;
+  size_t slice_offs_off = 0, slice_spec_off = 0, slice_rows_off = 0, slice_res_off = 0,
+         slice_kb_off = 0;
+  std::shared_ptr<ArenaPool::Arena> slice_arena;
   void release_mapped() {
     for (Mapped* m : {&keys, &offs, &set_keys, &set_vals, &set_voff, &set_meta, &del_keys,
-                      &del_found, &touch_rows, &touch_kbytes, &purge_img, &purge_out, &list_buf})
+                      &del_found, &touch_rows, &touch_kbytes, &purge_img, &purge_out, &list_buf,
+                      &slice_buf})
       m->release();
   }
   std::vector<uint32_t> trow;
@@ -358,6 +366,7 @@ struct HbmBackend::Dev {
   uint32_t pend_flush = 0;
   void track_writes(Flight& f, int dir);
   double avg_row_bytes = 4096;
+  double avg_slice_bytes = 8192;  // a slice row's bytes in its arena (head and window granules)
   // flushes requested and not yet finished on the GPU (any thread reads it: a
   // reactor-direct GET waits for them by going through the batcher)
   std::atomic<uint32_t> flush_pend{0};
@@ -372,7 +381,7 @@ struct HbmBackend::Dev {
       migrated{0}, migrate_ns{0}, direct_jobs{0}, direct_reqs{0}, direct_fallbacks{0},
       direct_overflows{0}, direct_timeouts{0}, direct_ns{0}, purged_objects{0},
       purged_bytes{0}, touch_reqs{0}, softened_objects{0}, tag_purged_objects{0},
-      tag_softened_objects{0}, glob_purged_objects{0}, glob_softened_objects{0};
+      tag_softened_objects{0}, glob_purged_objects{0}, glob_softened_objects{0}, slice_reqs{0};
 
   void loop();
   bool take_batch(std::vector<Req>* out, bool* do_flush, bool* rebuilding);
@@ -386,6 +395,9 @@ struct HbmBackend::Dev {
   void launch_fills(Flight& f);
   void launch_purges(Flight& f);
   void launch_lists(Flight& f);
+  void launch_slices(Flight& f);
+  void run_slices(Flight& f);
+  void deliver_slices(Flight& f);
   void deliver_list(Flight& f, Req& r);
   bool try_reap(Flight& f, bool block);
   void regather(Flight& f, uint64_t total);
@@ -415,6 +427,7 @@ struct HbmBackend::Dev {
     for (auto& f : flights) {
       f->release_mapped();
       f->arena.reset();
+      f->slice_arena.reset();
       if (f->ev) (void)hipEventDestroy(f->ev);
     }
     direct_offs.release();

@@ -200,13 +200,14 @@ void HbmBackend::Dev::loop() {
 // ---------------------------------------------------------------------------------
 void HbmBackend::Dev::launch(Flight& f) {
   TraceRange tr("hbm_backend.launch");
-  for (auto* v : {&f.gets, &f.sets, &f.dels, &f.touches, &f.ctls}) v->clear();
+  for (auto* v : {&f.gets, &f.sets, &f.dels, &f.touches, &f.slices, &f.ctls}) v->clear();
   for (uint32_t i = 0; i < f.reqs.size(); ++i) {
     switch (f.reqs[i].kind) {
       case ReqKind::Get: f.gets.push_back(i); break;
       case ReqKind::Set: f.sets.push_back(i); break;
       case ReqKind::Del: f.dels.push_back(i); break;
       case ReqKind::Touch: f.touches.push_back(i); break;
+      case ReqKind::Slice: f.slices.push_back(i); break;
       case ReqKind::Barrier:
       case ReqKind::Fill:
       case ReqKind::Purge:
@@ -219,6 +220,7 @@ void HbmBackend::Dev::launch(Flight& f) {
   f.active = true;
   f.served = false;
   launch_gets(f);
+  launch_slices(f);
   launch_sets(f);
   launch_dels(f);
   launch_touches(f);
@@ -267,6 +269,47 @@ void HbmBackend::Dev::launch_gets(Flight& f) {
   else
     cache->small_get(f.keys.dev<Digest>(), (int64_t)f.rows, f.arena->d, f.arena->cap,
                      f.offs.dev<uint64_t>(), f.tnow, stream, f.slot);
+}
+
+// Slices (get_part): reads, on the stream right after the flight's GETs and before its writes.
+// One row per request, everything in mapped memory; the rows' bytes land in an arena of their
+// own, sized from the running average (asked again if it falls short, deliver_slices).
+// They are answered when the flight's event has completed, that is behind the flight's SETs,
+// DELETEs, touches and any purge or list scan that shares the flight, whereas a GET is
+// answered as soon as its completion slot fires: a part batched with a scan waits for it.
+void HbmBackend::Dev::launch_slices(Flight& f) {
+  const size_t n = f.slices.size();
+  if (!n) return;
+  const SlicePlan p = plan_slice_rows(f.reqs, f.slices);
+  f.slice_offs_off = align_up(n * sizeof(Digest), 16);
+  f.slice_spec_off = f.slice_offs_off + align_up((n + 1) * 8, 16);
+  f.slice_rows_off = f.slice_spec_off + align_up(n * sizeof(SliceSpec), 16);
+  f.slice_res_off = f.slice_rows_off + n * sizeof(SliceRow);
+  f.slice_kb_off = f.slice_res_off + 16;
+  f.slice_buf.ensure(f.slice_kb_off + p.kbytes.size() + 16);
+  uint8_t* const hb = f.slice_buf.host<uint8_t>();
+  for (size_t j = 0; j < n; ++j) {
+    const Req& r = f.reqs[f.slices[j]];
+    reinterpret_cast<Digest*>(hb)[j] = r.d;
+    reinterpret_cast<SliceSpec*>(hb + f.slice_spec_off)[j] = r.spec;
+  }
+  std::memcpy(hb + f.slice_offs_off, p.offs.data(), (n + 1) * 8);
+  std::memcpy(hb + f.slice_kb_off, p.kbytes.data(), p.kbytes.size());
+  f.slice_arena = pool->take((size_t)(avg_slice_bytes * 1.5 * (double)n) + (64u << 10));
+  run_slices(f);
+  slice_reqs += n;
+}
+
+void HbmBackend::Dev::run_slices(Flight& f) {
+  uint8_t* const db = f.slice_buf.dev<uint8_t>();
+  std::memset(f.slice_buf.host<uint8_t>() + f.slice_res_off, 0, 16);
+  cache->get_keyed_slices(reinterpret_cast<const Digest*>(db), db + f.slice_kb_off,
+                          reinterpret_cast<const int64_t*>(db + f.slice_offs_off),
+                          reinterpret_cast<const SliceSpec*>(db + f.slice_spec_off),
+                          (int64_t)f.slices.size(),
+                          reinterpret_cast<SliceRow*>(db + f.slice_rows_off), f.slice_arena->d,
+                          f.slice_arena->cap, reinterpret_cast<uint64_t*>(db + f.slice_res_off),
+                          f.tnow, stream);
 }
 
 // SET: [klen | key | payload] values packed into mapped staging the SET kernels read
@@ -544,6 +587,7 @@ bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
     HB_OK(e);
   }
   if (f.active) {
+    deliver_slices(f);
     deliver_dels(f);
     deliver_touches(f);
     finish_ctls(f);
@@ -552,6 +596,7 @@ bool HbmBackend::Dev::try_reap(Flight& f, bool block) {
   f.active = false;
   f.reqs.clear();
   f.arena.reset();  // hits hold their own references
+  f.slice_arena.reset();
   return true;
 }
 
@@ -650,6 +695,61 @@ void HbmBackend::Dev::deliver_gets(Flight& f) {
   pg.flush();
 }
 
+// The flight's event has completed: its slices' rows and bytes are in host memory. Bytes that
+// outgrew the arena (none were written) are asked for again into a bigger one under regather's
+// condition (nothing has run since that could have changed what the rows saw), else the
+// slices answer "miss". Asking again runs k_slice_plan again, so those rows count twice in
+// get_ops / get_hits / get_bytes, as a regathered GET batch's do. A hit's head and window are
+// slices of the arena, which stays alive while any response built from it does; the GPU
+// matched the key, and the host checks it again against the bytes that arrived.
+void HbmBackend::Dev::deliver_slices(Flight& f) {
+  const size_t n = f.slices.size();
+  if (!n) return;
+  const uint8_t* const hb = f.slice_buf.host<uint8_t>();
+  const uint64_t* const res = reinterpret_cast<const uint64_t*>(hb + f.slice_res_off);
+  avg_slice_bytes = 0.9 * avg_slice_bytes + 0.1 * ((double)res[kSliceBytes] / (double)n);
+  bool have = res[kSliceBytes] <= f.slice_arena->cap;
+  if (!have && f.sets.empty() && f.dels.empty() && f.touches.empty() && inflight == 1) {
+    regathers++;
+    f.slice_arena = pool->take(res[kSliceBytes] + (64u << 10));
+    run_slices(f);
+    HB_OK(hipStreamSynchronize(stream));
+    have = res[kSliceBytes] <= f.slice_arena->cap;
+  }
+  if (!have) arena_misses += n;
+  const SliceRow* const rows = reinterpret_cast<const SliceRow*>(hb + f.slice_rows_off);
+  const uint8_t* const base = f.slice_arena->h;
+  std::shared_ptr<const void> owner = f.slice_arena;
+  PostGroups pg;
+  for (size_t j = 0; j < n; ++j) {
+    Req& r = f.reqs[f.slices[j]];
+    const SliceRow& row = rows[j];
+    PartValue p;
+    if (have && row.status != kSliceMiss) {
+      const char* const v = reinterpret_cast<const char*>(base + row.out_off);
+      size_t po = 0;
+      if (!keyed_match(v, row.vlen, r.key, &po)) {
+        key_mismatch.fetch_add(1, std::memory_order_relaxed);
+      } else {
+        p.status = row.status;
+        p.flags = row.flags;
+        p.ttl_left = row.expire ? (int64_t)row.expire - (int64_t)f.tnow : 0;
+        if (row.status == kSliceWholeObj) {
+          p.window = ByteRef(owner, v + po, row.vlen - po);
+        } else {
+          p.body_len = row.body_len;
+          p.first = row.win_first;
+          p.head = ByteRef(owner, v + row.head_off, row.body_off - row.head_off);
+          p.window = ByteRef(owner, v + row.head_bytes + row.skew, row.win_len);
+        }
+      }
+    }
+    if (r.pcb)
+      pg.answer(r.ex, [cb = std::move(r.pcb), p = std::move(p)]() mutable { cb(std::move(p)); });
+  }
+  pg.flush();
+}
+
 // Every GET of flight f answers "miss" (its records did not fit the arena).
 void HbmBackend::Dev::overflow_misses(Flight& f) {
   arena_misses += f.gets.size();
@@ -699,6 +799,9 @@ void HbmBackend::Dev::fail_requests(std::vector<Req>& reqs, bool unlaunched) {
       case ReqKind::Touch:
         if (r.tcb) pg.answer(r.ex, [cb = std::move(r.tcb)]() { cb(0); });
         break;
+      case ReqKind::Slice:
+        if (r.pcb) pg.answer(r.ex, [cb = std::move(r.pcb)]() { cb(PartValue{}); });
+        break;
       case ReqKind::Barrier:
       case ReqKind::Fill:
       case ReqKind::Purge:
@@ -719,12 +822,13 @@ void HbmBackend::Dev::fail_flight(Flight& f) {
     fail_requests(f.reqs, false);
   } else {
     std::vector<Req> rest;
-    for (const auto* v : {&f.dels, &f.touches, &f.ctls})
+    for (const auto* v : {&f.dels, &f.touches, &f.slices, &f.ctls})
       for (uint32_t i : *v) rest.push_back(std::move(f.reqs[i]));
     fail_requests(rest, false);
   }
   f.got = true;
   f.gets.clear();
+  f.slices.clear();
   f.dels.clear();
   f.touches.clear();
   f.ctls.clear();

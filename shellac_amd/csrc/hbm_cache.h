@@ -21,6 +21,7 @@
 
 #include "keyed.h"
 #include "layout.h"
+#include "slice.h"
 
 namespace shellac {
 
@@ -320,6 +321,27 @@ class HbmCache {
                   const uint64_t* tags, uint32_t ntags, uint64_t start_slot, uint32_t limit,
                   uint32_t key_cap, uint32_t now, ListRow* rows, uint8_t* keys, uint64_t* out,
                   hipStream_t s);
+  // Sliced GET (slice.h): row i asks for the window spec[i] of the keyed value stored under
+  // keys[i] with exactly the key key_bytes[key_offs[i] .. key_offs[i + 1]) (touch()'s packed
+  // layout; required). rows[i] says what was found (kSliceMiss: no live entry, or another
+  // key's record) and where the row's bytes start in `out`: the value's first head_bytes bytes
+  // (through the end of its HTTP head, rounded up to a granule), then the 16-byte granules of
+  // the value that cover the window. A value that is not a sliceable HTTP response, and a
+  // kSliceWhole row, come back whole (kSliceWholeObj). res = {rows that hit, total bytes of
+  // `out`}; when the total exceeds out_cap nothing is written to `out`, and `rows` and `res`
+  // are still complete (gather's contract). n <= kSmallGetMax. Hits set the CLOCK reference
+  // bit and count in get_ops / get_hits / get_bytes (the bytes returned: the value through its
+  // head's end plus the window, or the whole value) as a GET's. `reserve` as lookup()'s.
+  // All arrays are device or mapped pinned memory. Asynchronous and ordered on `s`; the
+  // segment lists, the scan's scratch and the result words are one workspace per shard,
+  // allocated on the first call (that call allocates): a call on another stream than the one
+  // before waits, on the device, for that one's event, so calls on several streams are safe
+  // and run one after the other. See k_slice_plan for what holds beside a SET chain on
+  // another stream.
+  void get_keyed_slices(const Digest* keys, const uint8_t* key_bytes, const int64_t* key_offs,
+                        const SliceSpec* spec, int64_t n, SliceRow* rows, uint8_t* out,
+                        uint64_t out_cap, uint64_t* res, uint32_t now, hipStream_t s,
+                        uint64_t reserve = 0);
   // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
   // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
   // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte
@@ -499,6 +521,12 @@ class HbmCache {
   CacheCounters* ctr_ = nullptr;     // device counters (64 shards)
   unsigned long long* scratch_ = nullptr;  // device scratch for reductions
   uint8_t* list_ws_ = nullptr;       // list_keyed: match bitmap, tile counts and bases
+  // get_keyed_slices: result words, segment sources, lengths, offsets, the scan's scratch
+  uint8_t* slice_ws_ = nullptr;
+  size_t slice_tmp_bytes_ = 0;
+  // recorded behind each call on its stream: the workspace's next user on another stream waits
+  hipEvent_t slice_done_ = nullptr;
+  hipStream_t slice_stream_ = nullptr;
   uint64_t* part_ = nullptr;         // per-workgroup sums: GET sizes, SET sizes, SET counts
   uint64_t* host_buf_ = nullptr;     // pinned scratch for small D2H reads
   uint64_t* host_slots_ = nullptr;   // pinned coherent slots the GPU writes totals into

@@ -55,6 +55,11 @@
 //                  wave's match ballot goes into a bitmap, each tile's count into an array.
 //   k_list_tiles   one workgroup scans the tile counts; k_list_emit gives every match its
 //                  rank from them and writes the first `limit` rows and keys in slot order.
+//   k_slice_plan   the sliced GET (slice.h), one wave per row: k_touch's key-exact probe, the
+//                  tag block stepped over, the end of the HTTP head searched 1 KiB per wave
+//                  pass, one byte window resolved; two segments per row for k_segcopy.
+//   k_slice_offsets the rows' out_off from the scanned segment lengths, the hit count, and
+//                  no copy at all when the total exceeds the output's capacity.
 //   k_expand(_out), k_small_get, k_delete, k_sweep, k_export, k_digest, k_route*,
 //   k_permute, k_mfma_hello.
 #include <hip/hip_runtime.h>
@@ -4350,6 +4355,216 @@ __global__ __launch_bounds__(kBlock) void k_records_to_set(
 }
 
 // ---------------------------------------------------------------------------------
+// Sliced GET (slice.h): the head and one byte window of a stored HTTP response
+// ---------------------------------------------------------------------------------
+// k_slice_plan, one wave per row, kBlock / 64 rows per workgroup. The wave
+//   1. probes the digest's two buckets as k_touch does (each 16-lane group reads both lines,
+//      every group computes the same winner: the newest live entry, what a GET finds);
+//   2. reads the record's header and requires the entry's own record (digest, vlen, magic);
+//   3. compares the stored key with the row's key bytes, one 16-B granule per lane
+//      (k_touch's key-exact test): a digest collision is a miss;
+//   4. sets the entry's CLOCK reference bit, as a GET hit does;
+//   5. steps over the tag block (parse_tag_block's rules) and tests "HTTP/";
+//   6. searches CR LF CR LF from head_off: per pass each lane loads one 16-B granule (1 KiB
+//      per wave), takes the next granule's first dword from its neighbour lane (the last lane
+//      loads it), tests its 16 start positions, and a ballot finds the lowest match. The loop
+//      ends at the first pass with a match, at vlen, or kSliceHeadMax bytes past head_off;
+//   7. resolves the window (resolve_window) and writes the SliceRow (out_off = 0) and the
+//      row's two segments: source offsets into the log and lengths, for segcopy_sized.
+// k_slice_offsets then writes out_off from the scanned lengths, counts the hits, and empties
+// every segment when the total does not fit out_cap (gather's contract: nothing is copied).
+//
+// What it relies on. Exactness (every row answers from the object that was stored before the
+// call and is live) comes from stream order against whole SET chains, or from a `reserve` that
+// covers the SETs queued beside it. Beside appends on another stream without `reserve` it
+// stays memory-safe, and a row never carries another object's bytes under kSliceOk or
+// kSliceUnsat as long as the record is not overwritten while the wave reads it: liveness is
+// judged at the furthest byte the queued appends have claimed (k_touch's max(head, claim),
+// plus `reserve`), the record must carry the entry's digest, vlen and the magic word and the
+// stored key must equal the row's key before the search starts, and every read is an aligned
+// granule below align_up(vlen, 16) of a record with vlen <= max_item and a 16-B-aligned loc
+// (inside the log's slack). A record that an append not covered by `reserve` overwrites
+// between the plan and the copy comes back torn, as after lookup + gather; such a row's
+// fields still describe the object that was planned. It writes the index only by the atomicOr
+// of kRefBit (a GET's), and the log not at all.
+constexpr int kSliceWaves = kBlock / 64;
+
+__global__ __launch_bounds__(kBlock) void k_slice_plan(
+    const Digest* __restrict__ keys, const uint8_t* __restrict__ kbytes,
+    const int64_t* __restrict__ koffs, const SliceSpec* __restrict__ spec, int64_t n,
+    Entry* __restrict__ index, uint64_t mask, const uint8_t* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr,
+    uint64_t reserve, uint64_t cap, uint32_t max_item, uint32_t now, SliceRow* __restrict__ rows,
+    uint64_t* __restrict__ seg_src, uint64_t* __restrict__ seg_len,
+    CacheCounters* __restrict__ ctr) {
+  const int lane = threadIdx.x & 63;
+  const int l16 = lane & 15;
+  const int gbase = lane & 48;
+  const bool even = (l16 & 1) == 0;
+  const uint64_t hs = *head_ptr, hc = *claim_ptr;
+  const uint64_t head = (hc > hs ? hc : hs) + reserve;
+  unsigned long long ops = 0, hits = 0, bytes = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kSliceWaves + (threadIdx.x >> 6); i < n;
+       i += (int64_t)gridDim.x * kSliceWaves) {
+    SliceRow r = SliceRow{};  // a miss
+    uint64_t src0 = kSegSkip, src1 = kSegSkip;
+    do {  // (every condition below is uniform in the wave)
+      const Digest d = keys[i];
+      const uint64_t b = (l16 < 8) ? bucket1(d, mask) : bucket2(d, mask);
+      const uint4 v = reinterpret_cast<const uint4*>(index + b * kEntriesPerBucket)[l16 & 7];
+      // even lane: d0, d1 | odd lane: loc, vlen | expire << 32
+      const uint64_t a = pack2(v.x, v.y), c = pack2(v.z, v.w);
+      const uint64_t pa = __shfl_xor(a, 1), pc = __shfl_xor(c, 1);
+      const bool live = even && a == d.lo && c == d.hi &&
+                        entry_live(pa, (uint32_t)(pc >> 32), head, cap, now);
+      uint64_t hl = live ? pa : 0;
+      int hw = l16;
+#pragma unroll
+      for (int sh = 1; sh < 16; sh <<= 1) {
+        const uint64_t ol = __shfl_xor(hl, sh);
+        const int ow = __shfl_xor(hw, sh);
+        if (ol > hl || (ol == hl && ow < hw)) {
+          hl = ol;
+          hw = ow;
+        }
+      }
+      if (hl == 0) break;  // no live entry
+      const uint64_t ve = __shfl(pc, gbase + hw);  // the winner's {vlen | expire} word
+      const uint32_t vlen = entry_vlen((uint32_t)ve);
+      if (vlen > max_item || ((hl - 1) & 15)) break;
+      const uint64_t recoff = (hl - 1) % cap;
+      const uint4* const rec = reinterpret_cast<const uint4*>(log + recoff);
+      const uint4 ha = rec[0], hb = rec[1];
+      // the entry's own record: digest, vlen and magic (ItemHeader's words)
+      if (pack2(ha.x, ha.y) != d.lo || pack2(ha.z, ha.w) != d.hi || hb.x != vlen ||
+          hb.w != kItemMagic)
+        break;
+      const int64_t k0 = koffs[i], klen64 = koffs[i + 1] - k0;
+      if (klen64 < 0 || klen64 > (int64_t)kMaxKeyedKey || kKeyedPrefix + klen64 > vlen) break;
+      const uint32_t klen = (uint32_t)klen64;
+      {
+        const uint8_t* const kb = kbytes + k0;
+        const uint32_t kgran = (uint32_t)((kKeyedPrefix + klen + 15) >> 4);
+        bool eq = true;
+        for (uint32_t g = lane; g < kgran && eq; g += 64) {
+          const uint4 w = rec[2 + g];
+          const uint32_t p = g * 16;
+          eq = (((w.x ^ touch_key_word(kb, klen, p)) & touch_word_mask(klen, p)) |
+                ((w.y ^ touch_key_word(kb, klen, p + 4)) & touch_word_mask(klen, p + 4)) |
+                ((w.z ^ touch_key_word(kb, klen, p + 8)) & touch_word_mask(klen, p + 8)) |
+                ((w.w ^ touch_key_word(kb, klen, p + 12)) & touch_word_mask(klen, p + 12))) == 0u;
+        }
+        if (__ballot(!eq)) break;  // another key's record (or no keyed one)
+      }
+      if (lane == 0 && !((uint32_t)ve & kRefBit)) {
+        Entry* const slot = index +
+                            (hw < 8 ? bucket1(d, mask) : bucket2(d, mask)) * kEntriesPerBucket +
+                            ((hw & 7) >> 1);
+        atomicOr(&slot->vlen, kRefBit);
+      }
+      // the value's bytes; every index below is < vlen
+      const uint8_t* const val = log + recoff + kItemHeaderBytes;
+      const uint32_t ngr = (vlen + 15) >> 4;  // the value's granules inside the record
+      const SliceSpec sp = spec[i];
+      uint32_t head_off = (uint32_t)kKeyedPrefix + klen, body_off = 0;
+      bool sliceable = false;
+      if (sp.kind < kSliceWhole) {
+        const uint32_t o = head_off;
+        if (o + 2 <= vlen && val[o] == kTagMarker) {
+          const uint32_t nt = val[o + 1];
+          if (nt == kTagOverflow)
+            head_off = o + 2;
+          else if (nt <= kMaxObjectTags && o + 2 + 8 * nt <= vlen)
+            head_off = o + 2 + 8 * nt;
+        }
+        bool http = head_off + 5 <= vlen;
+        if (http)
+          http = val[head_off] == 'H' && val[head_off + 1] == 'T' && val[head_off + 2] == 'T' &&
+                 val[head_off + 3] == 'P' && val[head_off + 4] == '/';
+        if (http) {
+          // a match at value offset p needs head_off <= p and p + 4 <= lim
+          const uint32_t lim = min(vlen, head_off + kSliceHeadMax);
+          const uint4* const vg = rec + 2;
+          for (uint32_t g0 = head_off >> 4; g0 * 16 + 4 <= lim; g0 += 64) {
+            const uint32_t g = g0 + lane;
+            uint4 w = make_uint4(0u, 0u, 0u, 0u);
+            if (g < ngr) w = vg[g];
+            uint32_t nx = __shfl_down(w.x, 1);
+            if (lane == 63) nx = g + 1 < ngr ? vg[g + 1].x : 0u;
+            const uint32_t ww[5] = {w.x, w.y, w.z, w.w, nx};
+            uint32_t hit = 16;
+#pragma unroll
+            for (int j = 15; j >= 0; --j) {
+              const uint64_t two = pack2(ww[j >> 2], ww[(j >> 2) + ((j & 3) ? 1 : 0)]);
+              const uint32_t four = (uint32_t)(two >> (8 * (j & 3)));
+              const uint32_t p = g * 16 + j;
+              if (four == 0x0a0d0a0du && p >= head_off && p + 4 <= lim) hit = j;
+            }
+            const unsigned long long m = __ballot(hit < 16);
+            if (m) {
+              const int src = __ffsll((long long)m) - 1;
+              body_off = (g0 + (uint32_t)src) * 16 + (uint32_t)__shfl((int)hit, src) + 4;
+              sliceable = true;
+              break;
+            }
+          }
+        }
+      }
+      slice_make_row(&r, sp.kind, sp.a, sp.b, vlen, hb.y, (uint32_t)(ve >> 32), sliceable,
+                     head_off, body_off);
+      src0 = recoff + kItemHeaderBytes;
+      src1 = src0 + ((r.body_off + r.win_first) & ~15u);
+    } while (false);
+    if (lane == 0) {
+      rows[i] = r;
+      const uint32_t wb = slice_window_bytes(r.skew, r.win_len);
+      seg_src[2 * i] = r.status != kSliceMiss ? src0 : kSegSkip;
+      seg_len[2 * i] = r.head_bytes;
+      seg_src[2 * i + 1] = wb ? src1 : kSegSkip;
+      seg_len[2 * i + 1] = wb;
+      ++ops;
+      if (r.status != kSliceMiss) {
+        ++hits;
+        bytes += slice_row_payload(r);
+      }
+    }
+  }
+  block_count(ctr, ops, &CacheCounters::get_ops, hits, &CacheCounters::get_hits, bytes,
+              &CacheCounters::get_bytes);
+}
+
+// After the scan of the 2n segment lengths (dst_off[0..2n], dst_off[2n] = the total): row i's
+// out_off = dst_off[2i]; acc[kSliceHits] += the rows that hit (one add per workgroup),
+// acc[kSliceBytes] = the total; a total past out_cap empties every segment.
+__global__ __launch_bounds__(kBlock) void k_slice_offsets(
+    SliceRow* __restrict__ rows, int64_t n, const uint64_t* __restrict__ dst_off,
+    uint64_t* __restrict__ seg_len, uint64_t out_cap, unsigned long long* __restrict__ acc) {
+  const uint64_t total = dst_off[2 * n];
+  const bool fits = total <= out_cap;
+  unsigned long long hits = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kBlock) {
+    rows[i].out_off = dst_off[2 * i];
+    if (seg_len[2 * i]) ++hits;  // (a hit's segment 0 is never empty)
+    if (!fits) {
+      seg_len[2 * i] = 0;
+      seg_len[2 * i + 1] = 0;
+    }
+  }
+  __shared__ unsigned long long s_res[kBlock / 64];
+  hits = wave_sum(hits);
+  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = hits;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t0 = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
+    if (t0) atomicAdd(&acc[kSliceHits], t0);
+    if (blockIdx.x == 0) acc[kSliceBytes] = total;
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // MFMA hello (platform smoke)
 // ---------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -4606,6 +4821,8 @@ HbmCache::~HbmCache() {
   (void)hipFree(ctr_);
   (void)hipFree(scratch_);
   (void)hipFree(list_ws_);
+  (void)hipFree(slice_ws_);
+  if (slice_done_) (void)hipEventDestroy(slice_done_);
   (void)hipFree(done_ctr_);
   (void)hipFree(lb_state_);
   (void)hipFree(part_);
@@ -5590,6 +5807,55 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
     }
   }
   HIP_OK(hipMemcpyAsync(out, acc, kListWords * sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
+void HbmCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
+                                const int64_t* key_offs, const SliceSpec* spec, int64_t n,
+                                SliceRow* rows, uint8_t* out, uint64_t out_cap, uint64_t* res,
+                                uint32_t now, hipStream_t s, uint64_t reserve) {
+  TraceRange tr("hbm.slices");
+  SH_CHECK(n >= 0 && n <= kSmallGetMax, "sliced GET batch too large");
+  SH_CHECK(res, "sliced GET needs result words");
+  SH_CHECK(n == 0 || (keys && key_bytes && key_offs && spec && rows),
+           "sliced GET needs digests, key bytes with their offsets, window specs and rows");
+  SH_CHECK(n == 0 || out || out_cap == 0, "sliced GET needs an output buffer");
+  std::lock_guard<std::mutex> lk(mu_);
+  DeviceGuard g(cfg_.device);
+  // [result words | segment sources | segment lengths (+ the scan's zero) | destination
+  // offsets (+ the total) | the scan's scratch], sized for kSmallGetMax rows on first use
+  constexpr size_t kSegs = 2 * (size_t)kSmallGetMax;
+  constexpr size_t kAccBytes = 16, kSrcBytes = kSegs * 8, kLenBytes = (kSegs + 2) * 8;
+  if (!slice_ws_) {
+    slice_tmp_bytes_ = device_scan_tmp_bytes((int64_t)kSegs);
+    HIP_OK(hipMalloc(&slice_ws_, kAccBytes + kSrcBytes + 2 * kLenBytes + slice_tmp_bytes_));
+    HIP_OK(hipEventCreateWithFlags(&slice_done_, hipEventDisableTiming));
+  } else if (s != slice_stream_) {
+    // the call before, on another stream, may still use the workspace
+    HIP_OK(hipStreamWaitEvent(s, slice_done_, 0));
+  }
+  unsigned long long* const acc = reinterpret_cast<unsigned long long*>(slice_ws_);
+  uint64_t* const seg_src = reinterpret_cast<uint64_t*>(slice_ws_ + kAccBytes);
+  uint64_t* const seg_len = seg_src + kSegs;
+  uint64_t* const dst_off = seg_len + kSegs + 2;
+  void* const tmp = dst_off + kSegs + 2;
+  HIP_OK(hipMemsetAsync(acc, 0, kSliceWords * sizeof(unsigned long long), s));
+  if (n > 0) {
+    // (the scan reads 2n + 1 lengths: the last one is its zero)
+    HIP_OK(hipMemsetAsync(seg_len + 2 * n, 0, sizeof(uint64_t), s));
+    hipLaunchKernelGGL(k_slice_plan, dim3(grid_for(n, kSliceWaves, kMaxGrid)), dim3(kBlock), 0, s,
+                       keys, key_bytes, key_offs, spec, n, index_, cfg_.nbuckets - 1, log_,
+                       cur_head(), claim_ptr(), reserve, cfg_.log_bytes, cfg_.max_item, now, rows,
+                       seg_src, seg_len, ctr_);
+    HIP_OK(hipGetLastError());
+    device_exclusive_scan(seg_len, dst_off, 2 * n, tmp, slice_tmp_bytes_, s);
+    hipLaunchKernelGGL(k_slice_offsets, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), 0, s,
+                       rows, n, dst_off, seg_len, out_cap, acc);
+    HIP_OK(hipGetLastError());
+    segcopy_sized(log_, seg_src, dst_off, seg_len, 2 * n, out, s, out_cap);
+  }
+  HIP_OK(hipMemcpyAsync(res, acc, kSliceWords * sizeof(uint64_t), hipMemcpyDefault, s));
+  HIP_OK(hipEventRecord(slice_done_, s));
+  slice_stream_ = s;
 }
 
 uint64_t HbmCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now, hipStream_t s) {

@@ -23,9 +23,9 @@ struct TakeScratch {
 };
 
 // How many requests at the front of `q` form the next flight (at least 1 of a non-empty
-// queue, at most max(max_batch, 1)). A flight runs its GETs, then its SETs and DELETEs, then
-// its touches, then a fill or a purge, so:
-//  * a GET queued behind a write of its key ends the flight before itself (read-your-writes
+// queue, at most max(max_batch, 1)). A flight runs its GETs and slices, then its SETs and
+// DELETEs, then its touches, then a fill or a purge, so:
+//  * a GET or a slice queued behind a write of its key ends the flight before itself (read-your-writes
 //    for a client that re-reads right after a fill: it goes into the next flight, which is
 //    ordered after this one);
 //  * a SET or DELETE queued behind a touch of its key ends the flight before itself (a touch
@@ -41,6 +41,7 @@ inline size_t plan_take(const std::vector<HbmReq>& q, int max_batch, TakeScratch
     const HbmReq& r = q[i];
     switch (r.kind) {
       case ReqKind::Get:
+      case ReqKind::Slice:  // (a read: planned as a GET)
         if (!s.writes.empty() && s.writes.count(r.d.lo)) return i;
         break;
       case ReqKind::Set:
@@ -94,6 +95,26 @@ inline size_t coalesce_gets(const std::vector<HbmReq>& reqs, const std::vector<u
     }
   }
   return n;
+}
+
+// ---- slice rows ---------------------------------------------------------------------------
+// A flight's slices as the rows of one HbmCache::get_keyed_slices launch: one row per request,
+// in request order (requests of one key may ask for different windows), the rows' key bytes
+// packed with their n + 1 offsets.
+struct SlicePlan {
+  std::string kbytes;
+  std::vector<int64_t> offs;
+};
+inline SlicePlan plan_slice_rows(const std::vector<HbmReq>& reqs,
+                                 const std::vector<uint32_t>& slices) {
+  SlicePlan p;
+  p.offs.reserve(slices.size() + 1);
+  p.offs.push_back(0);
+  for (uint32_t i : slices) {
+    p.kbytes += reqs[i].key;
+    p.offs.push_back((int64_t)p.kbytes.size());
+  }
+  return p;
 }
 
 // ---- touch rows ---------------------------------------------------------------------------

@@ -689,6 +689,68 @@ void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t
   }
 }
 
+void HostCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
+                                 const int64_t* key_offs, const SliceSpec* spec, int64_t n,
+                                 SliceRow* rows, uint8_t* out, uint64_t out_cap,
+                                 uint64_t res[kSliceWords], uint32_t now, uint64_t reserve) {
+  SH_CHECK(n >= 0 && res, "sliced GET needs result words");
+  SH_CHECK(n == 0 || (keys && key_bytes && key_offs && spec && rows),
+           "sliced GET needs digests, key bytes with their offsets, window specs and rows");
+  std::lock_guard<std::mutex> lk(mu_);
+  std::vector<const uint8_t*> vals((size_t)n, nullptr);
+  uint64_t hits = 0, total = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    SliceRow& r = rows[i];
+    r = SliceRow{};  // a miss
+    r.out_off = total;
+    ctr_.get_ops++;
+    const Digest& d = keys[i];
+    // the newest live entry of the digest (what a GET finds)
+    Entry* e = nullptr;
+    for (uint64_t b : {bucket1(d, mask_), bucket2(d, mask_)})
+      for (uint32_t k = 0; k < kEntriesPerBucket; ++k) {
+        Entry& x = index_[b * kEntriesPerBucket + k];
+        if (x.d0 == d.lo && x.d1 == d.hi &&
+            entry_live(x.loc, x.expire, head_ + reserve, log_bytes_, now) && (!e || x.loc > e->loc))
+          e = &x;
+      }
+    if (!e) continue;
+    const uint32_t vlen = entry_vlen(e->vlen);
+    if (vlen > max_item_ || ((e->loc - 1) & 15)) continue;
+    const uint8_t* const rec = log_ + (e->loc - 1) % log_bytes_;
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    if (h.magic != kItemMagic || h.d0 != e->d0 || h.d1 != e->d1 || h.vlen != vlen) continue;
+    const int64_t klen = key_offs[i + 1] - key_offs[i];
+    if (klen < 0 || klen > (int64_t)kMaxKeyedKey || kKeyedPrefix + (uint64_t)klen > vlen) continue;
+    const uint8_t* const v = rec + kItemHeaderBytes;
+    uint16_t kl;
+    std::memcpy(&kl, v, kKeyedPrefix);
+    if (kl != klen || (klen && std::memcmp(v + kKeyedPrefix, key_bytes + key_offs[i], (size_t)klen)))
+      continue;  // another key's record: a miss
+    e->vlen |= kRefBit;
+    slice_value_row(&r, spec[i], v, vlen, h.flags, e->expire);
+    r.out_off = total;  // (slice_value_row starts from an empty row)
+    total += slice_row_bytes(r);
+    vals[(size_t)i] = v;
+    ++hits;
+    ctr_.get_hits++;
+    ctr_.get_bytes += slice_row_payload(r);
+  }
+  res[kSliceHits] = hits;
+  res[kSliceBytes] = total;
+  if (total > out_cap) return;
+  for (int64_t i = 0; i < n; ++i) {
+    const SliceRow& r = rows[i];
+    if (r.status == kSliceMiss) continue;
+    const uint8_t* const v = vals[(size_t)i];
+    // (both copies stay below align_up(vlen, 16): inside the record)
+    std::memcpy(out + r.out_off, v, r.head_bytes);
+    const uint32_t wb = slice_window_bytes(r.skew, r.win_len);
+    if (wb) std::memcpy(out + r.out_off + r.head_bytes, v + ((r.body_off + r.win_first) & ~15u), wb);
+  }
+}
+
 uint64_t HostCache::export_keys(Digest* out, uint64_t out_cap, uint32_t now) {
   std::lock_guard<std::mutex> lk(mu_);
   uint64_t m = 0;

@@ -12,6 +12,7 @@
 
 #include "keyed.h"
 #include "layout.h"
+#include "slice.h"
 
 namespace shellac {
 
@@ -71,6 +72,13 @@ class HostCache {
   void touch(const Digest* keys, const uint32_t* expire, const uint32_t* flags,
              const uint8_t* key_bytes, const int64_t* key_offs, int64_t n, uint8_t* hit,
              uint32_t now);
+  // Sliced GET (HbmCache::get_keyed_slices, whose semantic reference this is): the same rows,
+  // the same bytes in `out` (nothing when the total exceeds out_cap), the same result words,
+  // reference bit and counters. Built on slice.h.
+  void get_keyed_slices(const Digest* keys, const uint8_t* key_bytes, const int64_t* key_offs,
+                        const SliceSpec* spec, int64_t n, SliceRow* rows, uint8_t* out,
+                        uint64_t out_cap, uint64_t res[kSliceWords], uint32_t now,
+                        uint64_t reserve = 0);
   void flush();
   // Tests: see HbmCache::debug_bucket / debug_set_entry.
   std::vector<uint64_t> debug_bucket(uint64_t b);

@@ -225,6 +225,10 @@ struct Slot {
   Digest d{};
   bool lookup = false, head = false, client_gzip = false;
   bool vary_probe = false;  // `key` is a variant key (second lookup after a marker)
+  // --partial-hits: the request asks the tier for the object's head and the window `spec`
+  // (a Range GET, or a HEAD under policy rfc, which has lookup == false)
+  bool part = false;
+  SliceSpec spec{};
   // request headers, kept for the miss path when a response may Vary (policy rfc)
   std::shared_ptr<const std::vector<Header>> req_headers;
   Bytes vary_marker;  // --grace: the URL's marker a variant lookup went through
@@ -309,6 +313,10 @@ class Reactor : public Executor {
       soft_purge_requests{0}, softened_objects{0}, tag_purge_requests{0},
       tag_purged_objects{0}, tag_softened_objects{0}, tagged_fills{0}, inspect_requests{0},
       purge_dry_runs{0}, purge_glob_requests{0};
+  // --partial-hits: Range requests asked of the cache, their 206 and 416 answers, HEADs
+  // answered from the cache, and requests answered from a whole GET after all
+  std::atomic<uint64_t> range_requests{0}, range_206{0}, range_416{0}, head_hits{0},
+      partial_fallbacks{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -343,6 +351,9 @@ class Reactor : public Executor {
   void on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
                         const std::string* list);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
+  void ask_part(Slot* s, uint64_t cid);
+  void on_part(uint64_t cid, uint64_t seq, PartValue p);
+  bool answer_part(Client* c, Slot* s, const PartValue& p);
   void forward(Client* c, Slot* s);
   static std::string upstream_request(HttpParser& q);
   std::unique_ptr<HttpParser> take_parser();
@@ -368,7 +379,8 @@ class Reactor : public Executor {
   std::unordered_map<std::string, double> reval_retry_at_;
   void flush_client(Client* c);
   void flush_upstream(Upstream* u);
-  void complete_slot(Client* c, Slot* s, Bytes data);
+  // `tail` (optional): bytes sent right after `data`, shared, not copied (a 206's window)
+  void complete_slot(Client* c, Slot* s, Bytes data, Bytes tail = nullptr);
   void deliver(Client* c, Slot* s, Bytes obj);
   void fail_pend(Pend& p, int code, const char* reason);
   void release_waiters(const std::string& key, Bytes obj);
@@ -734,10 +746,23 @@ void Reactor::on_request(Client* c) {
   s->d = digest_bytes(reinterpret_cast<const uint8_t*>(s->key.data()), s->key.size());
   s->lookup = px_->cfg_.cache_enabled &&
               (cfg_.policy == "reference" || method == "GET") && !q.header("authorization");
-  if (s->lookup) s->req = std::move(c->req);  // serialized only if the cache misses
+  if (cfg_.partial_hits && px_->cfg_.cache_enabled && !q.header("authorization")) {
+    if (s->lookup && method == "GET") {
+      const std::string* rg = q.header("range");
+      s->part = rg && !q.header("if-range") && parse_single_range(rg->data(), rg->size(), &s->spec);
+    } else if (!s->lookup && s->head && cfg_.policy == "rfc") {
+      s->spec = SliceSpec{};
+      s->spec.kind = kSliceHead;
+      s->part = true;
+    }
+  }
+  if (s->lookup || s->part) s->req = std::move(c->req);  // serialized only if the cache misses
   else s->fwd = upstream_request(q);
   c->slots.push_back(std::move(s));
-  if (sp->lookup) {
+  if (sp->part) {
+    if (!sp->head) range_requests++;
+    ask_part(sp, c->id);
+  } else if (sp->lookup) {
     const uint64_t cid = c->id, seq = sp->seq;
     px_->backend_->get(sp->key, sp->d, this, [this, cid, seq](bool hit, CacheValue v) {
       on_cache(cid, seq, hit, std::move(v));
@@ -1228,6 +1253,120 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
   forward(c, s);
 }
 
+// ---- partial hits (ProxyConfig::partial_hits) -------------------------------------------
+void Reactor::ask_part(Slot* s, uint64_t cid) {
+  const uint64_t seq = s->seq;
+  px_->backend_->get_part(s->key, s->d, s->spec, this, [this, cid, seq](PartValue p) {
+    on_part(cid, seq, std::move(p));
+  });
+}
+
+// The tier's answer to a Range GET or a HEAD. Answered here: 206, 416, a HEAD's stored head.
+// Everything else goes the way it goes without the option: a Range GET as a miss or, through
+// a whole GET, as a hit (on_cache); a HEAD upstream, its response not cached.
+void Reactor::on_part(uint64_t cid, uint64_t seq, PartValue p) {
+  Client* c = find_client(cid);
+  if (!c) return;
+  Slot* s = find_slot(c, seq);
+  if (!s || s->ready) return;
+  const bool head_only = !s->lookup;  // a HEAD under policy rfc
+  if (p.status == kSliceWholeObj && p.window && cfg_.policy == "rfc" && !s->vary_probe && s->req) {
+    // the URL's Vary marker (behind a tag block or not): the variant is asked for the same way
+    Bytes m = p.window;
+    const uint64_t* hs;
+    unsigned nt;
+    bool over;
+    if (const size_t strip = parse_tag_block(m->data(), m->size(), &hs, &nt, &over))
+      m = m.sub(strip, m->size() - strip);
+    if (is_vary_marker(m->view())) {
+      s->key = vary_key(s->base_key, marker_names(m->view()), s->req->headers());
+      s->d = digest_bytes(reinterpret_cast<const uint8_t*>(s->key.data()), s->key.size());
+      s->vary_probe = true;
+      if (cfg_.grace) s->vary_marker = m;
+      ask_part(s, cid);
+      return;
+    }
+  }
+  if ((p.status == kSliceOk || p.status == kSliceUnsat) && answer_part(c, s, p)) return;
+  if (p.status != kSliceMiss) partial_fallbacks++;
+  if (head_only) {  // forwarded, as every HEAD is without the option
+    s->key = s->base_key;
+    forward(c, s);
+    return;
+  }
+  if (p.status == kSliceMiss) {
+    on_cache(cid, seq, false, CacheValue{});
+  } else if (p.status == kSliceWholeObj) {  // the whole value is here already
+    CacheValue v;
+    v.data = std::move(p.window);
+    v.flags = p.flags;
+    v.ttl_left = p.ttl_left;
+    on_cache(cid, seq, true, std::move(v));
+  } else {
+    px_->backend_->get(s->key, s->d, this, [this, cid, seq](bool hit, CacheValue v) {
+      on_cache(cid, seq, hit, std::move(v));
+    });
+  }
+}
+
+// Answers the request from the stored head and the window if that is exact; false: it is not.
+bool Reactor::answer_part(Client* c, Slot* s, const PartValue& p) {
+  const std::string_view hv = p.head->view();
+  const bool head_only = !s->lookup;
+  // an object already stale under --grace needs the whole object (revalidate)
+  if (cfg_.grace && p.flags && unix_now() >= p.flags) return false;
+  if (!object_header(hv, "transfer-encoding:").empty()) return false;
+  const std::string cl = object_header(hv, "content-length:");
+  if (cl.empty() || cl.find_first_not_of("0123456789") != std::string::npos ||
+      std::strtoull(cl.c_str(), nullptr, 10) != p.body_len)
+    return false;
+  if (!head_only) {
+    // "HTTP/1.x 200 ..."
+    const size_t sp = hv.find(' ');
+    if (sp == std::string_view::npos || hv.substr(sp + 1, 3) != "200" ||
+        (hv.size() > sp + 4 && hv[sp + 4] != ' ' && hv[sp + 4] != '\r'))
+      return false;
+    if (!s->client_gzip && cfg_.policy == "rfc" && object_is_gzip(hv)) return false;
+  }
+  hits++;
+  if (s->vary_probe) vary_hits++;
+  if (head_only) {
+    head_hits++;
+    complete_slot(c, s, p.head);
+    return true;
+  }
+  if (p.status == kSliceUnsat) {
+    range_416++;
+    complete_slot(c, s, std::make_shared<const std::string>(
+                            "HTTP/1.1 416 Range Not Satisfiable\r\nServer: " + cfg_.server_name +
+                            "\r\nContent-Range: bytes */" + std::to_string(p.body_len) +
+                            "\r\nContent-Length: 0\r\nConnection: keep-alive\r\n\r\n"));
+    return true;
+  }
+  // 206: the stored header lines, the window's length and where it lies
+  std::string out = "HTTP/1.1 206 Partial Content\r\n";
+  out.reserve(hv.size() + 96);
+  size_t pos = hv.find("\r\n");
+  while (pos != std::string_view::npos && pos + 2 < hv.size()) {
+    const size_t ls = pos + 2, le = hv.find("\r\n", ls);
+    if (le == std::string_view::npos || le == ls) break;  // the blank line
+    const std::string_view line = hv.substr(ls, le - ls);
+    const std::string low = to_lower(std::string(line.substr(0, line.find(':'))));
+    if (low != "content-length" && low != "content-range") {
+      out.append(line);
+      out += "\r\n";
+    }
+    pos = le;
+  }
+  const uint64_t len = p.window ? p.window->size() : 0;
+  out += "Content-Length: " + std::to_string(len) + "\r\nContent-Range: bytes " +
+         std::to_string(p.first) + "-" + std::to_string(p.first + len - 1) + "/" +
+         std::to_string(p.body_len) + "\r\n\r\n";
+  range_206++;
+  complete_slot(c, s, std::make_shared<const std::string>(std::move(out)), p.window);
+  return true;
+}
+
 // The last response on a connection announces the close (cached objects carry
 // "Connection: keep-alive" from the fill, Server.py:414-415).
 static Bytes with_connection_close(const Bytes& obj) {
@@ -1303,10 +1442,11 @@ void Reactor::deliver(Client* c, Slot* s, Bytes obj) {
   complete_slot(c, s, std::move(obj));
 }
 
-void Reactor::complete_slot(Client* c, Slot* s, Bytes data) {
+void Reactor::complete_slot(Client* c, Slot* s, Bytes data, Bytes tail) {
   if (s->req) give_parser(std::move(s->req));
   if (s->close_after && data) data = with_connection_close(data);
   s->out.write_shared(std::move(data));
+  if (tail && tail->size()) s->out.write_shared(std::move(tail));
   s->out.close();
   s->ready = true;
   const double us = (now_s() - s->t0) * 1e6;
@@ -1970,7 +2110,7 @@ void Reactor::rewrite_response_headers(HttpParser& r) {
   r.set_header("server", cfg_.server_name);
   r.set_header("keep-alive", "timeout=5, max=100");
   r.set_header("connection", "keep-alive");
-  r.remove_header("accept-ranges");
+  if (!cfg_.partial_hits) r.remove_header("accept-ranges");  // (with it, ranges are served)
 }
 
 bool Reactor::maybe_stream(Upstream* u) {
@@ -2388,6 +2528,7 @@ std::string Proxy::stats_json() {
            gcc = 0, sets = 0, bad = 0, uf = 0, rt = 0, col = 0, stm = 0, stp = 0, lmax = 0,
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
            sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0, insp = 0, pdr = 0, pgr = 0;
+  uint64_t ph[5] = {};  // --partial-hits
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -2410,6 +2551,8 @@ std::string Proxy::stats_json() {
     tso += r->tag_softened_objects; tgf += r->tagged_fills;
     insp += r->inspect_requests; pdr += r->purge_dry_runs;
     pgr += r->purge_glob_requests;
+    ph[0] += r->range_requests; ph[1] += r->range_206; ph[2] += r->range_416;
+    ph[3] += r->head_hits; ph[4] += r->partial_fallbacks;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -2445,6 +2588,9 @@ std::string Proxy::stats_json() {
     << ",\"tag_softened_objects\":" << tso << ",\"tagged_fills\":" << tgf
     << ",\"purge_glob_requests\":" << pgr
     << ",\"inspect_requests\":" << insp << ",\"purge_dry_runs\":" << pdr
+    << ",\"range_requests\":" << ph[0] << ",\"range_206\":" << ph[1]
+    << ",\"range_416\":" << ph[2] << ",\"head_hits\":" << ph[3]
+    << ",\"partial_fallbacks\":" << ph[4]
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
     << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]

@@ -85,6 +85,19 @@ struct ProxyConfig {
   // GET /_shellac/objects, the listing of what is cached (by ?prefix=, ?key=, ?tag=a,b,
   // ?glob=PATTERN or everything, &limit= and &after= to page). Read-only.
   std::string inspect = "off";
+  // Partial hits (off by default: every request is answered as without it). A cache-eligible
+  // GET with `Range: bytes=` holding exactly one range and no `If-Range`, and under policy rfc
+  // a HEAD, ask the tier for the object's head and one byte window (CacheBackend::get_part;
+  // the HBM tier cuts them on the GPU) and are answered from the cache: 206 Partial Content
+  // with Content-Range, 416 with `Content-Range: bytes */length`, or the stored head without
+  // a body. Several ranges, other units, invalid specs and If-Range ignore the header (200, as
+  // RFC 9110 allows). What cannot be answered exactly from head and window (a stored status
+  // other than 200, Transfer-Encoding, a Content-Length that is not the body's, a gzip-coded
+  // object for a client that did not ask for gzip, an object already stale under grace, a
+  // value that is no sliceable response) is answered as without the option after a whole GET
+  // (`partial_fallbacks`). A HEAD miss is forwarded and its response not cached, as without
+  // it. Fills keep the origin's Accept-Ranges header instead of dropping it.
+  bool partial_hits = false;
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
   bool key_host = false;

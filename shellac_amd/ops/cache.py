@@ -148,6 +148,58 @@ def unpack_records(out: torch.Tensor, off: torch.Tensor, size: torch.Tensor) -> 
     return res
 
 
+SLICE_KINDS = {"head": 0, "range": 1, "from": 2, "suffix": 3, "whole": 4}  # slice.h kSlice*
+SLICE_STATUS = ("miss", "ok", "unsat", "whole")  # slice.h kSliceMiss ..
+# u32 words of a SliceRow (slice.h); out_off is the u64 at bytes 48..55
+_SLICE_WORDS = ("status", "vlen", "flags", "expire", "head_off", "body_off", "body_len", "skew",
+                "win_first", "win_len", "head_bytes")
+
+
+def pack_slice_specs(specs) -> np.ndarray:
+    """Window specs -> uint8 [n, 24] rows of ``{u32 kind, u64 a, u64 b}`` (``SliceSpec``).
+    A spec is ``(kind,)``, ``(kind, a)`` or ``(kind, a, b)``, kind a name of ``SLICE_KINDS``
+    or its number."""
+    arr = np.zeros((len(specs), 3), dtype=np.uint64)
+    for i, s in enumerate(specs):
+        s = tuple(s) if isinstance(s, (tuple, list)) else (s,)
+        kind = SLICE_KINDS[s[0]] if isinstance(s[0], str) else int(s[0])
+        arr[i] = (kind, int(s[1]) if len(s) > 1 else 0, int(s[2]) if len(s) > 2 else 0)
+    return arr.view(np.uint8).reshape(len(specs), 24)
+
+
+def slice_rows(rows: torch.Tensor) -> list:
+    """Decode ``get_keyed_slices`` result rows -> one dict of the ``SliceRow`` fields per row."""
+    r = rows.cpu().numpy()
+    r32 = r.view(np.uint32).reshape(-1, 16)
+    r64 = r.view(np.uint64).reshape(-1, 8)
+    res = []
+    for i in range(r32.shape[0]):
+        f = {name: int(r32[i, k]) for k, name in enumerate(_SLICE_WORDS)}
+        f["out_off"] = int(r64[i, 6])
+        res.append(f)
+    return res
+
+
+def unpack_slices(rows: torch.Tensor, out: torch.Tensor) -> list:
+    """Decode a sliced GET (``CacheShard.get_slices``' dicts) from its rows and response
+    buffer; only a row's meaningful bytes are read, not its granules' padding."""
+    o = out.cpu().numpy()
+    res = []
+    for f in slice_rows(rows):
+        st, base = SLICE_STATUS[f["status"]], f["out_off"]
+        head = window = b""
+        if st == "whole":
+            window = o[base:base + f["vlen"]].tobytes()
+        elif st != "miss":
+            head = o[base + f["head_off"]:base + f["body_off"]].tobytes()
+            w0 = base + f["head_bytes"] + f["skew"]
+            window = o[w0:w0 + f["win_len"]].tobytes()
+        res.append({"status": st, "head": head, "window": window, "body_len": f["body_len"],
+                    "first": f["win_first"], "vlen": f["vlen"], "flags": f["flags"],
+                    "expire": f["expire"]})
+    return res
+
+
 def coalesce(keys: torch.Tensor, table: Optional[torch.Tensor] = None):
     """GET coalescing (request collapsing inside a batch). Returns ``first`` (int32
     [n]): the row that serves row i — one row per distinct digest claims it with a CAS
@@ -692,6 +744,85 @@ class CacheShard:
             kb = (torch.from_numpy(buf.copy()).to(self.device),
                   torch.from_numpy(offs).to(self.device))
         return [bool(x) for x in self.touch(d, ex, key_bytes=kb).tolist()]
+
+    # -- sliced GET -----------------------------------------------------------------
+    def get_keyed_slices(self, keys: torch.Tensor, key_bytes, specs: torch.Tensor,
+                         out: torch.Tensor, now: Optional[int] = None, reserve_bytes: int = 0):
+        """Sliced GET (``csrc/slice.h``; ``k_slice_plan`` on a GPU shard): row i asks for the
+        window ``specs[i]`` of the keyed value stored under ``keys[i]`` (int64 [n, 2]) with
+        exactly the key ``key_bytes`` names (``(uint8 buffer, int64 offsets[n + 1])``, as
+        ``touch``). ``specs``: uint8 [n, SLICE_SPEC_BYTES] from ``pack_slice_specs``; ``out``: the
+        uint8 response buffer. Returns ``(rows, res)``: uint8 [n, SLICE_ROW_BYTES] result rows
+        and int64 [2] ``{rows that hit, total bytes}``; a row's bytes start at its ``out_off``:
+        the value's first ``head_bytes`` bytes, then the 16-byte granules that cover the window.
+        When the total exceeds ``out.numel()`` nothing is written to ``out``; rows and totals
+        are complete. ``n`` <= SMALL_GET_MAX. Asynchronous on the current stream; a shard's
+        sliced GETs share one workspace, so calls on different streams run one after the other
+        (the later one waits for the earlier one's event on the device)."""
+        c = core()
+        self._check(keys, "keys")
+        self._check(specs, "specs")
+        self._check(out, "out")
+        n = keys.shape[0]
+        buf, offs = key_bytes
+        self._check(buf, "key bytes")
+        self._check(offs, "key offsets")
+        if buf.dtype != torch.uint8 or offs.dtype != torch.int64 or offs.numel() != n + 1:
+            raise TypeError("key_bytes must be (uint8 buffer, int64 offsets[n + 1])")
+        if specs.dtype != torch.uint8 or specs.numel() != n * c.SLICE_SPEC_BYTES:
+            raise TypeError("specs must be uint8 [n, SLICE_SPEC_BYTES] from pack_slice_specs")
+        if out.dtype != torch.uint8:
+            raise TypeError("out must be uint8")
+        if n > c.SMALL_GET_MAX:
+            raise ValueError("sliced GET: at most %d rows a call" % c.SMALL_GET_MAX)
+        rows = torch.zeros((n, c.SLICE_ROW_BYTES), dtype=torch.uint8, device=self.device)
+        res = torch.zeros(2, dtype=torch.int64, device=self.device)
+        now = self.now() if now is None else now
+        args = (keys.data_ptr(), buf.data_ptr(), offs.data_ptr(), specs.data_ptr(), n,
+                rows.data_ptr(), out.data_ptr(), out.numel(), res.data_ptr(), now)
+        if self.is_gpu:
+            self._impl.get_keyed_slices(*args, self._s(), int(reserve_bytes))
+        else:
+            self._impl.get_keyed_slices(*args, int(reserve_bytes))
+        return rows, res
+
+    def get_slices(self, keys: Sequence[bytes], specs, now: Optional[int] = None,
+                   reserve_bytes: int = 0, out_cap: Optional[int] = None) -> list:
+        """Sliced GET for byte-string keys: the HTTP head and one byte window of each stored
+        response, cut by the shard (the rest of the object is not moved). ``specs[i]`` is
+        ``("head",)``, ``("range", a, b)`` (body bytes a..b inclusive, b clamped),
+        ``("from", a)``, ``("suffix", a)`` (the last a bytes) or ``("whole",)``. Returns one
+        dict per row: ``{status, head, window, body_len, first, vlen, flags, expire}`` with
+        ``status`` one of ``"miss"``, ``"ok"``, ``"unsat"`` (the head, an empty window) and
+        ``"whole"`` (a ``("whole",)`` row, or a value that is no sliceable HTTP response:
+        ``window`` holds the whole stored value, ``head`` is empty). ``head`` is the payload
+        from ``HTTP/`` through the blank line. Works on GPU and CPU shards. Synchronises.
+        ``out_cap``: the response buffer's bytes; by default it grows until the batch fits (a
+        batch that did not fit is asked again, and counted again); an explicit one that is too
+        small raises ``ValueError``."""
+        c = core()
+        keys = [bytes(k) for k in keys]
+        n = len(keys)
+        if len(specs) != n:
+            raise ValueError("one window spec per key")
+        if n == 0:
+            return []
+        d = digest_strings(keys, self.device)
+        buf, offs = pack_bytes(keys)
+        buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, np.uint8)
+        kb = (torch.from_numpy(buf.copy()).to(self.device), torch.from_numpy(offs).to(self.device))
+        sp = torch.from_numpy(pack_slice_specs(specs)).to(self.device)
+        cap = (1 << 20) if out_cap is None else int(out_cap)
+        while True:
+            out = torch.zeros(max(cap, 16), dtype=torch.uint8, device=self.device)[:cap]
+            rows, res = self.get_keyed_slices(d, kb, sp, out, now, reserve_bytes)
+            total = int(res.tolist()[1])  # (waits for the stream)
+            if total <= cap:
+                break
+            if out_cap is not None:
+                raise ValueError("sliced GET: the batch needs %d bytes, out_cap is %d" % (total, cap))
+            cap = total
+        return unpack_slices(rows, out)
 
     def remove_keyed_prefix(self, prefix: bytes, now: Optional[int] = None) -> tuple[int, int]:
         """Prefix purge: remove every live object whose stored key starts with ``prefix``

@@ -156,7 +156,8 @@ class Server:
                  cpus: Sequence[int] = (), spin_us: int = 0, gzip_gpu: int = -1,
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
                  max_inflate_bytes: int = 64 << 20, purge: str = "off", grace: int = 0,
-                 tag_header: str = "", inspect: str = "off", **backend_opts):
+                 tag_header: str = "", inspect: str = "off", partial_hits: bool = False,
+                 **backend_opts):
         """``grace`` (seconds, 0 = off): keep cached objects that long past their TTL; a hit
         in that window is served stale at once while one background request per key
         revalidates it upstream (``If-None-Match`` / ``If-Modified-Since``) — a 304 extends
@@ -186,7 +187,20 @@ class Server:
         read-only listing of what is cached by ``?prefix=``, ``?key=``, ``?tag=a,b``, ``?glob=`` or
         everything, ``&limit=`` objects a page, ``&after=`` the page before's ``next``. A
         ``PURGE`` with ``X-Purge-Dry-Run: 1`` (under the ``purge`` rule) answers what the purge
-        would remove and removes nothing."""
+        would remove and removes nothing.
+
+        ``partial_hits`` (default off: every request is answered as without it): a cacheable
+        ``GET`` with ``Range: bytes=`` holding exactly one range and no ``If-Range``, and under
+        policy rfc a ``HEAD``, are answered from the cache through the tier's sliced GET (on
+        the HBM tier ``k_slice_plan`` finds the head's end and cuts the window on the GPU, so
+        only the head and the window leave HBM): ``206 Partial Content`` with
+        ``Content-Range``, ``416`` with ``Content-Range: bytes */length``, or the stored head
+        without a body. Several ranges, other units, invalid specs and ``If-Range`` ignore the
+        header (``200``). What cannot be answered exactly from head and window (a stored
+        status other than 200, ``Transfer-Encoding``, a gzip-coded object for a client without
+        ``Accept-Encoding: gzip``, an object already stale under ``grace``) is answered from a
+        whole GET and counted as ``partial_fallbacks``. Fills keep the origin's
+        ``Accept-Ranges`` header."""
         if purge not in ("off", "loopback", "any"):
             raise ValueError("purge must be 'off', 'loopback' or 'any'")
         if inspect not in ("off", "loopback", "any"):
@@ -211,7 +225,7 @@ class Server:
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
             max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
             purge=purge, grace=int(grace), tag_header=str(tag_header or ""),
-            inspect=inspect)
+            inspect=inspect, partial_hits=bool(partial_hits))
         self._started = False
 
     @property
@@ -333,6 +347,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "to page). "
                         "'PURGE' with 'X-Purge-Dry-Run: 1' answers what a purge would hit. "
                         "Default: off (the URL is forwarded like any other)")
+    p.add_argument("--partial-hits", action="store_true",
+                   help="answer Range requests (one 'bytes=' range, no If-Range) and, under "
+                        "--policy rfc, HEAD requests from the cache: 206 with Content-Range, 416, "
+                        "or the stored head without a body; on --cache hbm the GPU finds the "
+                        "head's end and cuts the window, so only those bytes leave HBM. Fills "
+                        "keep Accept-Ranges. Default: off (a hit is always the whole response, "
+                        "a HEAD goes upstream)")
     p.add_argument("--grace", type=int, default=0, metavar="S",
                    help="serve cached objects up to S seconds past their TTL while one "
                         "background request per key revalidates them upstream (If-None-Match / "
@@ -391,6 +412,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
                  max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
                  grace=args.grace, tag_header=args.tag_header, inspect=args.inspect,
+                 partial_hits=args.partial_hits,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,
