@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU time of a prefix purge (k_purge_prefix) against the index-only scan (k_sweep).
+"""GPU time of a prefix purge (k_keyed_scan<PrefixMatch, RemoveAction>) against the index-only scan (k_sweep).
 
 One CacheShard is filled with N keyed objects ([u16 klen | key | payload], 1 KiB payloads,
 URL-shaped keys of 40-80 bytes over 16 path families `/f00/` .. `/f15/`), for N = 1M and
@@ -14,7 +14,7 @@ Each: median, min, max of the runs, the bytes the kernel must touch (32 B per in
 one 64-B read per live entry scanned, the further 16-B key granules of matching records)
 and the bandwidth that implies. Prints one JSON line per N.
 
---soft: the soft purge (k_soften_prefix, soften_keyed_prefix with an expiry cap, so that a
+--soft: the soft purge (k_keyed_scan<PrefixMatch, SoftenAction>, soften_keyed_prefix with an expiry cap, so that a
 match costs the entry's CAS and both header stores) is measured first on the same filled
 shard, with the same shapes: it removes nothing, so every family run scans the full shard.
 Its line ("op": "soft", the same fields; purge_match_removed holds the objects softened)
@@ -22,7 +22,7 @@ is printed before the hard purge's ("op": "hard").
 
 --tags: every object carries a tag block of 4 tags between its key and its payload (keyed.h:
 [0x02 | 4 | 4 x u64]; one hash names the object's family, three are its own), and the purge by
-tag (k_purge_tags / k_soften_tags) is measured beside the prefix purge on the same shard:
+tag (k_keyed_scan<TagMatch, RemoveAction> / k_keyed_scan<TagMatch, SoftenAction>) is measured beside the prefix purge on the same shard:
 "op": "soft-tags" (it removes nothing) and "hard-tags", with the same fields. A tag purge of
 one family's hash matches the same 1/16 of the objects as the prefix purge of that family; a
 list of one hash no object carries matches nothing. All no-match runs, of every op, are timed
@@ -37,7 +37,7 @@ yardstick: both read the same lines; "count_over_purge" is the ratio of the medi
 list of one family (1/16 of the objects) with limit 100 and with the maximum (4096 rows, 128-byte
 key areas).
 
---glob: the purge by URL glob (k_purge_glob, HbmCache::remove_keyed_glob) is measured on the same
+--glob: the purge by URL glob (k_keyed_scan<GlobMatch, RemoveAction>, HbmCache::remove_keyed_glob) is measured on the same
 full shard, before anything is removed ("op": "glob"), timed in turn with the hard prefix purge
 that matches nothing (its yardstick, in the same run): a glob with a literal head that matches
 nothing (`/nothing/*`: the head-granule reject, the prefix scan's reads), and one with a tail

@@ -271,7 +271,7 @@ class HbmCache {
   // the number of live matching entries, whether or not their words changed. Uses scratch
   // words of its own (one soft purge at a time per shard). Exact when ordered against whole
   // SET chains; refused while a phase-1 batch waits for its phase 2, as touch(). See
-  // k_soften_prefix for what holds beside a SET chain on another stream.
+  // k_keyed_scan (SoftenAction) for what holds beside a SET chain on another stream.
   void soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exact, uint32_t stale_at,
                            uint32_t expire_cap, uint32_t now, uint64_t* out, hipStream_t s);
   // Tag purge of keyed values: removes every live entry whose stored value carries, at value
@@ -520,6 +520,24 @@ class HbmCache {
   uint64_t* next_head() const { return head_ + (hsel_ ^ 1); }
   CacheCounters* ctr_ = nullptr;     // device counters (64 shards)
   unsigned long long* scratch_ = nullptr;  // device scratch for reductions
+  // Its words, a 16-B block of its own per operation: the results of different operations
+  // queued on a shard do not meet (one call at a time per operation and shard).
+  enum ScratchWord : int {
+    kScratchSweep = 0,  // sweep: live entries, live bytes; export_keys: the rows written
+    kScratchPurgePrefix = 4,
+    kScratchSoftenPrefix = 6,
+    kScratchPurgeTags = 8,
+    kScratchSoftenTags = 10,
+    kScratchList = 12,  // kListWords words
+    kScratchPurgeGlob = 16,
+    kScratchSoftenGlob = 18,
+    kScratchWords = 20
+  };
+  // The launch of k_keyed_scan<Matcher, Action> over the whole index: the result words at
+  // `word` cleared, the scan, its Action::kWords result words copied to `out`, all on `s`.
+  template <class Matcher, class Action>
+  void keyed_scan(const Matcher& m, const Action& act, uint32_t now, ScratchWord word,
+                  uint64_t* out, hipStream_t s);
   uint8_t* list_ws_ = nullptr;       // list_keyed: match bitmap, tile counts and bases
   // get_keyed_slices: result words, segment sources, lengths, offsets, the scan's scratch
   uint8_t* slice_ws_ = nullptr;

@@ -32,26 +32,19 @@
 //   All per-op counters are block-reduced and added to one of 64 counter
 //   shards (one atomic per block per field; same-address fan-in measured at
 //   ~12 ns/atomic would otherwise serialise a 64K-wave probe into milliseconds).
-//   k_purge_prefix one lane per index slot (k_sweep's traversal): a live entry's record is
-//                  read from the log and the entry removed if its stored key starts with
-//                  the pattern (16-B granules against a host-prepared, shifted image).
 //   k_touch        16 lanes per key (k_delete's probe): the newest live entry's expiry is
 //                  replaced in place by a CAS that keeps the CLOCK bit, and the record
 //                  header's expiry / flags with it; with key bytes only a record whose
 //                  stored key is exactly the row's (16-B granules, one per lane).
-//   k_soften_prefix k_purge_prefix's scan and matcher (by prefix or exact key), k_touch's
-//                  action: a matching live entry is kept, its record's flags become the
-//                  given freshness time and its expiry is capped (never extended), by a CAS
-//                  that keeps the CLOCK bit and stores into the record header.
-//   k_purge_tags   k_purge_prefix's scan and action with a tag matcher: a record whose tag
-//                  block (keyed.h, at value byte 2 + klen) holds one of up to 64 hashes, or
-//                  the overflow block, is removed; unaligned hashes come from aligned dwords.
-//   k_soften_tags  the same matcher with k_soften_prefix's action.
-//   k_purge_glob   k_purge_prefix's scan and action with a glob matcher: a record whose key,
-//                  up to its first 0x1f, matches a compiled '*' pattern (keyed.h) from end to
-//                  end: head on granule 0, tail at the subject's end, middles leftmost in order.
-//   k_soften_glob  the same matcher with k_soften_prefix's action.
-//   k_list_scan    the purges' scans and matchers, read-only, by tiles of kBlock slots: each
+//   k_keyed_scan   purge and soft purge, one lane per index slot (k_sweep's traversal): a live
+//                  entry's record is read from the log and, if the instance's matcher passes
+//                  its stored keyed value (a key prefix or exact key against a host-prepared
+//                  image in 16-B granules; a tag block holding one of up to 64 hashes; the key
+//                  up to its first 0x1f against a compiled '*' pattern), the instance's action
+//                  applied: the entry removed (a CAS of its loc), or kept, its record's flags
+//                  set and its expiry capped (k_touch's CAS, which keeps the CLOCK bit, then
+//                  the record header). One instance per (matcher, action).
+//   k_list_scan    the same per-slot test, read-only, by tiles of kBlock slots: each
 //                  wave's match ballot goes into a bitmap, each tile's count into an array.
 //   k_list_tiles   one workgroup scans the tile counts; k_list_emit gives every match its
 //                  rank from them and writes the first `limit` rows and keys in slot order.
@@ -3037,115 +3030,18 @@ __global__ __launch_bounds__(kBlock) void k_sweep(Entry* __restrict__ index, uin
   }
 }
 
-// Prefix purge: remove every live entry whose stored *keyed* value ([u16 klen | key |
-// payload], keyed.h) has a key that starts with the pattern. One lane per index slot, as
-// k_sweep: the index is a coalesced 32-B-per-lane stream; each live entry costs one
-// dependent, scattered read of its record (header 32 B + the first value granule, which
-// holds klen and key bytes 0..13 and rejects nearly every non-matching record); only the
-// survivors read the further granules. `img` is the host-prepared pattern image of keyed.h
-// (granule masks, then the pattern shifted by the 2-byte klen word), `ngran` its pattern
-// granules; the granules after the first are staged in LDS up to kPurgeLdsGranules and read
-// from global memory (one address per wave: a broadcast) beyond that.
-//
-// What it relies on. Exactness (every matching object stored before the call is removed,
-// nothing else) comes from stream order against appends: the backend queues it between SET
-// chains. Beside a concurrent append on another stream it stays memory-safe and never
-// removes a live non-matching object, through the header re-check (as k_edge_server's
-// claim / re-check): the record must still carry the entry's digest, vlen and the magic
-// word, every read stays inside [record, record + item_bytes(vlen)) with vlen <= max_item
-// (inside the log's slack), and the removal is a CAS of the very loc that was read — a
-// record an append tore while it was compared belongs to an entry the append is about to
-// kill anyway, and an entry a SET re-pointed meanwhile keeps its new loc.
-// The item-start ring and the log are untouched (as after k_delete): the CLOCK hand skips
-// ring entries whose index entry is gone, and a detached hand's move-CAS of a purged entry
-// loses (reinsert_lost).
-constexpr int kPurgeLdsGranules = 64;  // 1 KiB: prefixes up to 1022 bytes compare from LDS
-
+// One 16-B granule of a stored keyed value against a pattern granule under a byte mask (the
+// pattern images of keyed.h: prefix images and the head of a compiled glob).
 __device__ __forceinline__ bool purge_granule_eq(const uint4 v, const uint4 m, const uint4 p) {
   return (((v.x & m.x) ^ p.x) | ((v.y & m.y) ^ p.y) | ((v.z & m.z) ^ p.z) |
           ((v.w & m.w) ^ p.w)) == 0u;
-}
-
-__global__ __launch_bounds__(kBlock) void k_purge_prefix(
-    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
-    const uint4* __restrict__ img, uint32_t plen, uint32_t ngran,
-    unsigned long long* __restrict__ out, CacheCounters* __restrict__ ctr) {
-  // the two masks and the first pattern granules: one read of the image per workgroup (it
-  // may be mapped host memory)
-  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
-  const uint4* const s_pat = s_img + 2;
-  const uint4* const pat = img + 2;
-  for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
-    s_img[g] = img[g];
-  __syncthreads();
-  const uint4 m0 = s_img[0], mlast = s_img[1], p0 = s_pat[0];
-  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);  // the granules between: every byte
-  const uint64_t head = *head_ptr;
-  unsigned long long removed = 0, bytes = 0;
-  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
-       k += (uint64_t)gridDim.x * kBlock) {
-    Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < kKeyedPrefix + plen || vlen > max_item || ((loc - 1) & 15)) continue;
-    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    const uint4 v0 = rec[2];
-    const uint32_t klen = v0.x & 0xffffu;
-    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
-    if (!purge_granule_eq(v0, m0, p0)) continue;
-    bool eq = true;
-    for (uint32_t g = 1; g < ngran; ++g) {
-      const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_pat[g] : pat[g];
-      const uint4 v = rec[2 + g];
-      if (!purge_granule_eq(v, g + 1 == ngran ? mlast : ones, p)) {
-        eq = false;
-        break;
-      }
-    }
-    if (!eq) continue;
-    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
-                  0ull) == loc) {
-      ++removed;
-      bytes += item_bytes(vlen);
-    }
-  }
-  block_count(ctr, removed, &CacheCounters::purged);
-  // the result words: one add per word per workgroup, after its whole grid-stride loop (a
-  // matching purge with an add per wave spent ~0.4 ms on the same-address fan-in alone)
-  __shared__ unsigned long long s_res[2][kBlock / 64];
-  removed = wave_sum(removed);
-  bytes = wave_sum(bytes);
-  if ((threadIdx.x & 63) == 0) {
-    s_res[0][threadIdx.x >> 6] = removed;
-    s_res[1][threadIdx.x >> 6] = bytes;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0, t1 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-      t0 += s_res[0][k];
-      t1 += s_res[1][k];
-    }
-    if (t0) atomicAdd(&out[0], t0);
-    if (t1) atomicAdd(&out[1], t1);
-  }
 }
 
 // Touch: change an object's expiry (and optionally its flags) in place. 16 lanes per key,
 // as k_delete: the group reads the digest's two buckets (two 128-B lines), pair-lane
 // shuffles join the entry halves and a max-reduce keeps the newest live match (what a GET
 // finds). The entry's record header is then read (32 B) and, when key bytes are given, its
-// stored key compared in 16-B granules, one granule per lane (k_purge_prefix's checks); a row
+// stored key compared in 16-B granules, one granule per lane (k_keyed_scan's checks); a row
 // moves two index lines, the record header and the key's granules, and writes 8 + 4 (+ 4)
 // bytes — no value byte is read or written.
 //
@@ -3323,131 +3219,8 @@ __global__ __launch_bounds__(kBlock) void k_touch(
   block_count(ctr, touched, &CacheCounters::touched);
 }
 
-// Soft purge: end the freshness of every live entry whose stored keyed value has a key that
-// starts with (exact: equals) the pattern, and keep the object. k_purge_prefix's traversal
-// and matcher (one lane per index slot, the pattern image staged in LDS, the first granule
-// rejecting; `exact` costs one more compare on klen, the image is the same), k_touch's
-// action by the lane that owns the slot: the record's flags become `stale_at`, and where
-// `expire_cap` != 0 and the entry never expires or expires after it, the expiry becomes
-// expire_cap — in the entry by a CAS of the {vlen | expire} word that keeps kRefBit, then in
-// the record's ItemHeader (the CLOCK hand rebuilds a re-appended entry from the header, so
-// both places must agree). A life is only ever shortened. No value byte, loc or vlen
-// changes; the item-start ring and the log head are untouched. out[0] counts the live
-// matching entries, whether or not their words changed.
-//
-// What it relies on. Exactness (every matching object stored before the call and live is
-// softened, nothing else) comes from stream order against whole SET chains (StoreOpts::phase
-// == 0): the backend queues it between them. Beside a SET chain on another stream it stays
-// memory-safe and never changes the entry or the record of a non-matching object: it writes
-// into the log, so liveness is judged at the furthest byte the queued appends have claimed
-// (k_touch's max(head, claim): a record about to be overwritten is neither written nor
-// counted), the record must carry the entry's digest, vlen and the magic word, every access
-// stays inside [record, record + item_bytes(vlen)) with vlen <= max_item, and the expiry goes
-// in by a CAS of the very word that was read with the digest and the loc (only kRefBit may
-// differ and is kept). The word does not hold the digest, so the slot is read again after the
-// CAS: if it passed to another entry with an equal word in between, the same CAS puts the
-// old expiry back and the slot is neither written further nor counted. A detached CLOCK hand
-// rewrites the word from the value it staged: HbmCache::soften_keyed_prefix refuses while
-// one is pending.
-__global__ __launch_bounds__(kBlock) void k_soften_prefix(
-    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
-    uint32_t max_item, uint32_t now, const uint4* __restrict__ img, uint32_t plen, uint32_t ngran,
-    uint32_t exact, uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
-  __shared__ uint4 s_img[2 + kPurgeLdsGranules];
-  const uint4* const s_pat = s_img + 2;
-  const uint4* const pat = img + 2;
-  for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
-    s_img[g] = img[g];
-  __syncthreads();
-  const uint4 m0 = s_img[0], mlast = s_img[1], p0 = s_pat[0];
-  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
-  // the head the queued appends reach (equal to the head slot once they have run)
-  const uint64_t hs = *head_ptr, hc = *claim_ptr;
-  const uint64_t head = hc > hs ? hc : hs;
-  unsigned long long softened = 0;
-  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
-       k += (uint64_t)gridDim.x * kBlock) {
-    Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < kKeyedPrefix + plen || vlen > max_item || ((loc - 1) & 15)) continue;
-    uint8_t* const recb = log + (loc - 1) % cap;
-    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    const uint4 v0 = rec[2];
-    const uint32_t klen = v0.x & 0xffffu;
-    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
-    if (exact && klen != plen) continue;
-    if (!purge_granule_eq(v0, m0, p0)) continue;
-    bool eq = true;
-    for (uint32_t g = 1; g < ngran; ++g) {
-      const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_pat[g] : pat[g];
-      const uint4 v = rec[2 + g];
-      if (!purge_granule_eq(v, g + 1 == ngran ? mlast : ones, p)) {
-        eq = false;
-        break;
-      }
-    }
-    if (!eq) continue;
-    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
-    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
-      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
-      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
-      bool done = false;
-      for (int t = 0; t < kTouchCasTries; ++t) {
-        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
-        const unsigned long long prev = atomicCAS(w, expect, want);
-        if (prev == expect) {
-          done = true;
-          break;
-        }
-        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
-        expect = prev;
-      }
-      if (!done) continue;
-      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
-      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
-        // the slot passed to another entry with an equal word: put its expiry back
-        unsigned long long cur = want;
-        for (int t = 0; t < 2; ++t) {
-          const unsigned long long prev =
-              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
-          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
-          cur = prev;
-        }
-        continue;
-      }
-      h->expire = expire_cap;
-    }
-    h->flags = stale_at;
-    ++softened;
-  }
-  // the result word: one add per workgroup, after its whole grid-stride loop (k_purge_prefix)
-  __shared__ unsigned long long s_res[kBlock / 64];
-  softened = wave_sum(softened);
-  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
-    if (t0) atomicAdd(&out[0], t0);
-  }
-}
-
 // ---- purge by tag --------------------------------------------------------------------------
-// The matcher of k_purge_tags / k_soften_tags. `rec` is a record whose header was checked
+// The body of TagMatch, the tag matcher of the keyed scans. `rec` is a record whose header was checked
 // (digest, vlen, magic), `v0` its value granule 0, 4 <= vlen <= max_item. The tag block of
 // keyed.h sits at value byte o = 2 + klen: [0x02 | ntags | ntags x u64 LE]. Reads are aligned
 // 16-B granules (the block's two header bytes) and aligned dwords (the hashes, put together
@@ -3460,20 +3233,31 @@ __device__ __forceinline__ uint32_t granule_byte(const uint4 g, const uint32_t i
   return (w >> ((i & 3u) * 8u)) & 0xffu;
 }
 
-__device__ __forceinline__ bool tag_block_match(const uint4* __restrict__ rec, const uint32_t vlen,
-                                                const uint4 v0, const uint2* __restrict__ s_tags,
-                                                const uint32_t nlist) {
+// The tag block's two header bytes: its ntags byte (a count whose hashes lie inside the value,
+// or kTagOverflow), or kNoTagBlock where the value carries no well-formed block.
+constexpr uint32_t kNoTagBlock = ~0u;
+__device__ __forceinline__ uint32_t tag_block_ntags(const uint4* __restrict__ rec,
+                                                    const uint32_t vlen, const uint4 v0) {
   const uint32_t o = (uint32_t)kKeyedPrefix + (v0.x & 0xffffu);
-  if (o + 2 > vlen) return false;
+  if (o + 2 > vlen) return kNoTagBlock;
   const uint32_t ga = o >> 4, gb = (o + 1) >> 4;
   uint4 a = v0, b = v0;
   if (ga) a = rec[2 + ga];
   if (gb != ga) b = rec[2 + gb];
   else b = a;
-  if (granule_byte(a, o & 15u) != (uint32_t)kTagMarker) return false;
+  if (granule_byte(a, o & 15u) != (uint32_t)kTagMarker) return kNoTagBlock;
   const uint32_t nt = granule_byte(b, (o + 1) & 15u);
+  if (nt == kTagOverflow) return nt;
+  return nt > kMaxObjectTags || o + 2 + 8 * nt > vlen ? kNoTagBlock : nt;
+}
+
+__device__ __forceinline__ bool tag_block_match(const uint4* __restrict__ rec, const uint32_t vlen,
+                                                const uint4 v0, const uint2* __restrict__ s_tags,
+                                                const uint32_t nlist) {
+  const uint32_t nt = tag_block_ntags(rec, vlen, v0);
+  if (nt == kNoTagBlock) return false;
   if (nt == kTagOverflow) return true;
-  if (nt > kMaxObjectTags || o + 2 + 8 * nt > vlen) return false;
+  const uint32_t o = (uint32_t)kKeyedPrefix + (v0.x & 0xffffu);
   const uint32_t* const vw = reinterpret_cast<const uint32_t*>(rec + 2);  // the value's dwords
   const uint32_t sh = (o + 2) & 3u;
   uint32_t d = (o + 2) >> 2;
@@ -3491,173 +3275,8 @@ __device__ __forceinline__ bool tag_block_match(const uint4* __restrict__ rec, c
   return false;
 }
 
-// The purge list: read once per workgroup into LDS (it may be mapped host memory).
-__device__ __forceinline__ void stage_tag_list(uint2* s_tags, const uint2* __restrict__ tags,
-                                               const uint32_t nlist) {
-  for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s_tags[j] = tags[j];
-  __syncthreads();
-}
-
-// Tag purge: remove every live entry whose stored keyed value carries a tag block (keyed.h)
-// holding one of the `nlist` <= kMaxPurgeTags hashes in `tags`, or the overflow block.
-// k_purge_prefix's traversal (one lane per index slot, grid-stride), liveness, record
-// re-check and action (the CAS of loc to 0, `purged`, the two result words with one add per
-// word per workgroup); only the matcher differs (tag_block_match).
-//
-// What it relies on: what k_purge_prefix relies on. Exactness comes from stream order between
-// whole SET chains: the backend queues it between them. Beside an append on another stream
-// it only reads the log, inside [record, record + item_bytes(vlen)) with vlen <= max_item and
-// a 16-B-aligned loc (inside the log's slack), of a record that carried the entry's digest,
-// vlen and magic; the removal is a CAS of the very loc that was read, so a record torn while
-// it was compared belongs to an entry the append is about to kill, and an entry a SET
-// re-pointed keeps its new loc. The ring and the log are untouched.
-__global__ __launch_bounds__(kBlock) void k_purge_tags(
-    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
-    const uint2* __restrict__ tags, uint32_t nlist, unsigned long long* __restrict__ out,
-    CacheCounters* __restrict__ ctr) {
-  __shared__ uint2 s_tags[kMaxPurgeTags];
-  stage_tag_list(s_tags, tags, nlist);
-  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
-  const uint64_t head = *head_ptr;
-  unsigned long long removed = 0, bytes = 0;
-  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
-       k += (uint64_t)gridDim.x * kBlock) {
-    Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < kKeyedPrefix + 2 || vlen > max_item || ((loc - 1) & 15)) continue;
-    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    if (!tag_block_match(rec, vlen, rec[2], s_tags, nlist)) continue;
-    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
-                  0ull) == loc) {
-      ++removed;
-      bytes += item_bytes(vlen);
-    }
-  }
-  block_count(ctr, removed, &CacheCounters::purged);
-  __shared__ unsigned long long s_res[2][kBlock / 64];
-  removed = wave_sum(removed);
-  bytes = wave_sum(bytes);
-  if ((threadIdx.x & 63) == 0) {
-    s_res[0][threadIdx.x >> 6] = removed;
-    s_res[1][threadIdx.x >> 6] = bytes;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0, t1 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-      t0 += s_res[0][k];
-      t1 += s_res[1][k];
-    }
-    if (t0) atomicAdd(&out[0], t0);
-    if (t1) atomicAdd(&out[1], t1);
-  }
-}
-
-// Soft tag purge: k_purge_tags' scan and matcher, k_soften_prefix's action, word for word:
-// the record's flags become `stale_at` and an expiry of never or after `expire_cap` becomes
-// expire_cap, in the entry by a CAS of the {vlen | expire} word that keeps kRefBit (bounded
-// retries, the slot read again afterwards and the old expiry put back if it passed to another
-// entry), then in the record's ItemHeader. out[0] counts the live matches, whether or not
-// their words changed; no CacheCounters field.
-//
-// What it relies on: what k_soften_prefix relies on. Exactness comes from stream order
-// between whole SET chains. Beside a SET chain on another stream it stays memory-safe and
-// leaves non-matching objects alone: it writes into the log, so liveness is judged at
-// max(head, claim) (a record the queued appends will overwrite is neither written nor
-// counted), the record must carry the entry's digest, vlen and magic, every access stays
-// inside [record, record + item_bytes(vlen)), and the expiry goes in by a CAS of the word
-// read with the digest and the loc. HbmCache::soften_keyed_tags refuses while a detached
-// CLOCK hand is pending (it rewrites that word from a staged value).
-__global__ __launch_bounds__(kBlock) void k_soften_tags(
-    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
-    uint32_t max_item, uint32_t now, const uint2* __restrict__ tags, uint32_t nlist,
-    uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
-  __shared__ uint2 s_tags[kMaxPurgeTags];
-  stage_tag_list(s_tags, tags, nlist);
-  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
-  // the head the queued appends reach (equal to the head slot once they have run)
-  const uint64_t hs = *head_ptr, hc = *claim_ptr;
-  const uint64_t head = hc > hs ? hc : hs;
-  unsigned long long softened = 0;
-  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
-       k += (uint64_t)gridDim.x * kBlock) {
-    Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < kKeyedPrefix + 2 || vlen > max_item || ((loc - 1) & 15)) continue;
-    uint8_t* const recb = log + (loc - 1) % cap;
-    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    if (!tag_block_match(rec, vlen, rec[2], s_tags, nlist)) continue;
-    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
-    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
-      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
-      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
-      bool done = false;
-      for (int t = 0; t < kTouchCasTries; ++t) {
-        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
-        const unsigned long long prev = atomicCAS(w, expect, want);
-        if (prev == expect) {
-          done = true;
-          break;
-        }
-        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
-        expect = prev;
-      }
-      if (!done) continue;
-      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
-      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
-        // the slot passed to another entry with an equal word: put its expiry back
-        unsigned long long cur = want;
-        for (int t = 0; t < 2; ++t) {
-          const unsigned long long prev =
-              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
-          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
-          cur = prev;
-        }
-        continue;
-      }
-      h->expire = expire_cap;
-    }
-    h->flags = stale_at;
-    ++softened;
-  }
-  __shared__ unsigned long long s_res[kBlock / 64];
-  softened = wave_sum(softened);
-  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
-    if (t0) atomicAdd(&out[0], t0);
-  }
-}
-
 // ---- purge by glob -------------------------------------------------------------------------
-// The matcher of k_purge_glob / k_soften_glob / k_list_scan<kListGlob>: keyed.h's glob
+// The body of GlobMatch, the glob matcher of the keyed scans: keyed.h's glob
 // algorithm on a record whose header was checked (digest, vlen, magic); `v0` its value
 // granule 0, `s_img` the compiled pattern (KeyedGlob: eight header granules, then the literal
 // bytes) staged in LDS. Tests in order of cost, since a wave costs what its slowest lane
@@ -3669,7 +3288,7 @@ __global__ __launch_bounds__(kBlock) void k_soften_tags(
 // of registers (glob_byte keeps the last granule); the literals are bytes of LDS.
 // Memory safety: every byte read is value byte b < 2 + klen <= vlen, in granule b >> 4, which
 // starts below align_up(vlen, 16): inside [record + 32, record + item_bytes(vlen)) with vlen
-// <= max_item, the bounds the prefix kernels rely on. Work per record: at most klen x (longest
+// <= max_item, the bounds keyed_record establishes. Work per record: at most klen x (longest
 // middle segment) byte compares, after one pass over the key for the separator.
 constexpr uint32_t kGlobLdsGranules = (uint32_t)(sizeof(KeyedGlob) / 16);
 
@@ -3745,171 +3364,283 @@ __device__ __forceinline__ bool glob_match(const uint4* __restrict__ rec, const 
   return true;
 }
 
-// The compiled pattern: read once per workgroup into LDS (it may be mapped host memory).
-__device__ __forceinline__ void stage_glob_image(uint4* s_img, const uint4* __restrict__ img,
-                                                 const uint32_t ngran) {
-  for (uint32_t g = threadIdx.x; g < ngran && g < kGlobLdsGranules; g += kBlock) s_img[g] = img[g];
-  __syncthreads();
+// ---- the keyed index scans -----------------------------------------------------------------
+// Purge, soft purge and listing walk the whole index, one lane per slot, as k_sweep: the index
+// is a coalesced 32-B-per-lane stream; each live entry costs one dependent, scattered read of
+// its record (header 32 B + the first value granule, which holds klen and key bytes 0..13 and
+// rejects nearly every non-matching record); only the survivors read further granules. A scan
+// is the product of a matcher (what the stored keyed value, [u16 klen | key | payload] of
+// keyed.h, must look like) and an action (what happens to a matching entry):
+//   PrefixMatch    the key starts with (exact: equals) the pattern of a host-prepared image
+//   TagMatch       the value's tag block holds one of the listed hashes (tag_block_match)
+//   GlobMatch      the key's subject matches a compiled glob (glob_match)
+//   AnyKeyedMatch  any plausible keyed value (the list only)
+//   RemoveAction   the entry's loc becomes 0; `removed` and their item bytes; `purged`
+//   SoftenAction   the entry's freshness ends and the object stays (soften_entry); one count
+// k_keyed_scan<Matcher, Action> is the purge / soft purge skeleton, k_list_scan<Matcher> the
+// read-only scan of the listing. One kernel instance per pair and no runtime switch between
+// matchers: each instance holds the registers and the static LDS of its own matcher only.
+//
+// What it relies on, every instance. Exactness (every matching object stored before the call
+// and live is acted on, nothing else) comes from stream order against whole SET chains
+// (StoreOpts::phase == 0): the backend queues the scan between them. Beside an append on
+// another stream it stays memory-safe and never acts on a live non-matching object, through
+// the header re-check of keyed_record (as k_edge_server's claim / re-check): no record byte is
+// read before the entry is live, vlen <= max_item and loc is 16-B aligned (inside the log's
+// slack); the record must still carry the entry's digest, vlen and the magic word before any
+// value granule past the first is read; and every read stays inside [record, record +
+// item_bytes(vlen)), each matcher for its own reads with vlen >= its vmin.
+// RemoveAction adds: liveness is judged at the published head; the log is only read; the
+// removal is a CAS of the very loc that was read, so a record an append tore while it was
+// compared belongs to an entry the append is about to kill anyway, and an entry a SET
+// re-pointed meanwhile keeps its new loc. The item-start ring and the log are untouched (as
+// after k_delete): the CLOCK hand skips ring entries whose index entry is gone, and a detached
+// hand's move-CAS of a purged entry loses (reinsert_lost).
+// SoftenAction adds: it writes into the log, so liveness is judged at the furthest byte the
+// queued appends have claimed (k_touch's max(head, claim): a record about to be overwritten
+// is neither written nor counted), and the expiry goes in by a CAS of the very {vlen |
+// expire} word that was read with the digest and the loc (only kRefBit, which a GET hit sets
+// meanwhile, may differ and is kept). The word does not hold the digest, so the slot is read
+// again after the CAS: if it passed to another entry with an equal word in between, the same
+// CAS puts the old expiry back and the slot is neither written further nor counted. A
+// detached CLOCK hand rewrites the word from the value it staged: HbmCache's soften_keyed_*
+// refuse while a phase-1 batch waits for its phase 2.
+constexpr int kPurgeLdsGranules = 64;  // 1 KiB: prefixes up to 1022 bytes compare from LDS
+
+// An index entry and its record. Byte: const uint8_t, or uint8_t where the action writes the
+// record's header.
+template <class Byte>
+struct KeyedRecord {
+  uint4 ea, eb;  // the entry: d0, d1 | loc, vlen (with kRefBit), expire
+  uint64_t loc;
+  uint32_t vlen;
+  Byte* recb;
+  __device__ const uint4* granules() const { return reinterpret_cast<const uint4*>(recb); }
+};
+
+// The record of entry `e` iff the entry is live at `head`, its own and of vmin..max_item value
+// bytes; nothing of r is to be used otherwise.
+template <class Byte>
+__device__ __forceinline__ bool keyed_record(const Entry* __restrict__ e, Byte* __restrict__ log,
+                                             const uint64_t head, const uint64_t cap,
+                                             const uint32_t max_item, const uint32_t now,
+                                             const uint32_t vmin, KeyedRecord<Byte>& r) {
+  r.ea = reinterpret_cast<const uint4*>(e)[0];
+  r.eb = reinterpret_cast<const uint4*>(e)[1];
+  r.loc = pack2(r.eb.x, r.eb.y);
+  r.vlen = entry_vlen(r.eb.z);
+  if (!entry_live(r.loc, r.eb.w, head, cap, now)) return false;
+  if (r.vlen < vmin || r.vlen > max_item || ((r.loc - 1) & 15)) return false;
+  r.recb = log + (r.loc - 1) % cap;
+  const uint4 ha = r.granules()[0], hb = r.granules()[1];
+  // the entry's own record: digest, vlen and magic (ItemHeader's words)
+  if (ha.x != r.ea.x || ha.y != r.ea.y || ha.z != r.ea.z || ha.w != r.ea.w || hb.x != r.vlen ||
+      hb.w != kItemMagic)
+    return false;
+  return true;
 }
 
-// Glob purge: remove every live entry whose stored keyed value has a key whose subject (the
-// key up to its first kVarySep) matches the compiled pattern `img` (`ngran` granules of it are
-// used). k_purge_prefix's traversal (one lane per index slot, grid-stride), liveness, record
-// re-check and action (the CAS of loc to 0, `purged`, the two result words with one add per
-// word per workgroup); only the matcher differs (glob_match, which also states the bound on
-// the work per record).
-//
-// What it relies on: what k_purge_prefix relies on, all of it unchanged. Exactness comes from
-// stream order between whole SET chains: the backend queues it between them. Beside an append
-// on another stream it only reads the log, inside [record, record + item_bytes(vlen)) with
-// vlen <= max_item and a 16-B-aligned loc (inside the log's slack), of a record that carried
-// the entry's digest, vlen and magic, and never removes a live non-matching object: the
-// removal is a CAS of the very loc that was read, so a record torn while it was compared
-// belongs to an entry the append is about to kill, and an entry a SET re-pointed keeps its new
-// loc. The ring and the log are untouched.
-__global__ __launch_bounds__(kBlock) void k_purge_glob(
-    Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
-    const uint4* __restrict__ img, uint32_t ngran, unsigned long long* __restrict__ out,
-    CacheCounters* __restrict__ ctr) {
-  __shared__ uint4 s_img[kGlobLdsGranules];
-  stage_glob_image(s_img, img, ngran);
-  const uint32_t vmin = (uint32_t)kKeyedPrefix + s_img[0].w;
-  const uint64_t head = *head_ptr;
-  unsigned long long removed = 0, bytes = 0;
-  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
-       k += (uint64_t)gridDim.x * kBlock) {
-    Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) continue;
-    const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    if (!glob_match(rec, vlen, rec[2], s_img)) continue;
-    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)loc,
-                  0ull) == loc) {
-      ++removed;
-      bytes += item_bytes(vlen);
+// The matchers. Each carries its kernel arguments, its LDS staging (read once per workgroup:
+// the pattern may be mapped host memory; the skeleton puts the barrier after stage()), the
+// least vlen a match can have and match() on a record keyed_record passed, `v0` its value
+// granule 0.
+struct PrefixMatch {
+  const uint4* __restrict__ img;  // keyed.h's image: the first and last granule's byte masks,
+                                  // then the pattern shifted by the 2-byte klen word
+  uint32_t plen, ngran, exact;
+  struct Lds {
+    uint4 img[2 + kPurgeLdsGranules];  // (further pattern granules are read from `img`: one
+                                       // address per wave, a broadcast)
+  };
+  __device__ void stage(Lds& s) const {
+    for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
+      s.img[g] = img[g];
+  }
+  __device__ uint32_t vmin(const Lds&) const { return (uint32_t)kKeyedPrefix + plen; }
+  __device__ bool match(const Lds& s, const uint4* __restrict__ rec, const uint32_t vlen,
+                        const uint4 v0) const {
+    const uint32_t klen = v0.x & 0xffffu;
+    if (klen < plen || kKeyedPrefix + klen > vlen) return false;
+    if (exact && klen != plen) return false;
+    if (!purge_granule_eq(v0, s.img[0], s.img[2])) return false;
+    const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);  // the granules between: every byte
+    for (uint32_t g = 1; g < ngran; ++g) {
+      const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s.img[2 + g] : img[2 + g];
+      if (!purge_granule_eq(rec[2 + g], g + 1 == ngran ? s.img[1] : ones, p)) return false;
     }
+    return true;
   }
-  block_count(ctr, removed, &CacheCounters::purged);
-  __shared__ unsigned long long s_res[2][kBlock / 64];
-  removed = wave_sum(removed);
-  bytes = wave_sum(bytes);
-  if ((threadIdx.x & 63) == 0) {
-    s_res[0][threadIdx.x >> 6] = removed;
-    s_res[1][threadIdx.x >> 6] = bytes;
+};
+
+struct TagMatch {
+  const uint2* __restrict__ tags;
+  uint32_t nlist;
+  struct Lds {
+    uint2 tags[kMaxPurgeTags];
+  };
+  __device__ void stage(Lds& s) const {
+    for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s.tags[j] = tags[j];
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0, t1 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-      t0 += s_res[0][k];
-      t1 += s_res[1][k];
+  __device__ uint32_t vmin(const Lds&) const { return (uint32_t)kKeyedPrefix + 2u; }
+  __device__ bool match(const Lds& s, const uint4* __restrict__ rec, const uint32_t vlen,
+                        const uint4 v0) const {
+    return tag_block_match(rec, vlen, v0, s.tags, nlist < kMaxPurgeTags ? nlist : kMaxPurgeTags);
+  }
+};
+
+struct GlobMatch {
+  const uint4* __restrict__ img;  // the compiled pattern (KeyedGlob)
+  uint32_t ngran;                 // its granules in use
+  struct Lds {
+    uint4 img[kGlobLdsGranules];
+  };
+  __device__ void stage(Lds& s) const {
+    for (uint32_t g = threadIdx.x; g < ngran && g < kGlobLdsGranules; g += kBlock) s.img[g] = img[g];
+  }
+  __device__ uint32_t vmin(const Lds& s) const { return (uint32_t)kKeyedPrefix + s.img[0].w; }
+  __device__ bool match(const Lds& s, const uint4* __restrict__ rec, const uint32_t vlen,
+                        const uint4 v0) const {
+    return glob_match(rec, vlen, v0, s.img);
+  }
+};
+
+struct AnyKeyedMatch {
+  struct Lds {};
+  __device__ void stage(Lds&) const {}
+  __device__ uint32_t vmin(const Lds&) const { return (uint32_t)kKeyedPrefix; }
+  __device__ bool match(const Lds&, const uint4* __restrict__, const uint32_t vlen,
+                        const uint4 v0) const {
+    const uint32_t klen = v0.x & 0xffffu;
+    return klen != 0 && kKeyedPrefix + klen <= vlen;  // (an empty key names no object)
+  }
+};
+
+// Soft purge of one matching entry, by the lane that owns the slot: the record's flags become
+// `stale_at`, and where `expire_cap` != 0 and the entry never expires or expires after it, the
+// expiry becomes expire_cap — in the entry by a CAS of the {vlen | expire} word that keeps
+// kRefBit, then in the record's ItemHeader (the CLOCK hand rebuilds a re-appended entry from
+// the header, so both places must agree). A life is only ever shortened. No value byte, loc or
+// vlen changes. False (nothing further written) if the entry was no longer the one read.
+__device__ __forceinline__ bool soften_entry(Entry* e, const KeyedRecord<uint8_t>& r,
+                                             const uint32_t stale_at, const uint32_t expire_cap) {
+  ItemHeader* const h = reinterpret_cast<ItemHeader*>(r.recb);
+  if (expire_cap && (r.eb.w == 0 || r.eb.w > expire_cap)) {
+    unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
+    unsigned long long expect = pack2(r.eb.z, r.eb.w), want = 0;
+    bool done = false;
+    for (int t = 0; t < kTouchCasTries; ++t) {
+      want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
+      const unsigned long long prev = atomicCAS(w, expect, want);
+      if (prev == expect) {
+        done = true;
+        break;
+      }
+      if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
+      expect = prev;
     }
-    if (t0) atomicAdd(&out[0], t0);
-    if (t1) atomicAdd(&out[1], t1);
+    if (!done) return false;
+    const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
+    const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (e0 != pack2(r.ea.x, r.ea.y) || e1 != pack2(r.ea.z, r.ea.w) || e2 != r.loc) {
+      // the slot passed to another entry with an equal word: put its expiry back
+      unsigned long long cur = want;
+      for (int t = 0; t < 2; ++t) {
+        const unsigned long long prev =
+            atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
+        if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
+        cur = prev;
+      }
+      return false;
+    }
+    h->expire = expire_cap;
   }
+  h->flags = stale_at;
+  return true;
 }
 
-// Soft glob purge: k_purge_glob's scan and matcher, k_soften_prefix's action, word for word:
-// the record's flags become `stale_at` and an expiry of never or after `expire_cap` becomes
-// expire_cap, in the entry by a CAS of the {vlen | expire} word that keeps kRefBit (bounded
-// retries, the slot read again afterwards and the old expiry put back if it passed to another
-// entry), then in the record's ItemHeader. A life is only ever shortened. out[0] counts the
-// live matches, whether or not their words changed; no CacheCounters field.
-//
-// What it relies on: what k_soften_prefix relies on, all of it unchanged. Exactness comes from
-// stream order between whole SET chains. Beside a SET chain on another stream it stays
-// memory-safe and leaves non-matching objects alone: it writes into the log, so liveness is
-// judged at max(head, claim) (a record the queued appends will overwrite is neither written
-// nor counted), the record must carry the entry's digest, vlen and magic, every access stays
-// inside [record, record + item_bytes(vlen)), and the expiry goes in by a CAS of the word read
-// with the digest and the loc. HbmCache::soften_keyed_glob refuses while a phase-1 batch waits
-// for its phase 2 (a detached CLOCK hand rewrites that word from a staged value).
-__global__ __launch_bounds__(kBlock) void k_soften_glob(
-    Entry* __restrict__ index, uint64_t nslots, uint8_t* __restrict__ log,
-    const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr, uint64_t cap,
-    uint32_t max_item, uint32_t now, const uint4* __restrict__ img, uint32_t ngran,
-    uint32_t stale_at, uint32_t expire_cap, unsigned long long* __restrict__ out) {
-  __shared__ uint4 s_img[kGlobLdsGranules];
-  stage_glob_image(s_img, img, ngran);
-  const uint32_t vmin = (uint32_t)kKeyedPrefix + s_img[0].w;
+// The actions. Each names the log bytes' type, the head liveness is judged at, its result
+// words, what it does to a matching entry and what it adds to CacheCounters.
+struct RemoveAction {
+  using Byte = const uint8_t;
+  static constexpr int kWords = 2;  // entries removed, their item bytes
+  CacheCounters* __restrict__ ctr;
+  __device__ uint64_t head(const uint64_t* __restrict__ head_ptr) const { return *head_ptr; }
+  __device__ void apply(Entry* e, const KeyedRecord<Byte>& r, unsigned long long* res) const {
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&e->loc), (unsigned long long)r.loc,
+                  0ull) == r.loc) {
+      ++res[0];
+      res[1] += item_bytes(r.vlen);
+    }
+  }
+  __device__ void count(const unsigned long long* res) const {
+    block_count(ctr, res[0], &CacheCounters::purged);
+  }
+};
+
+struct SoftenAction {
+  using Byte = uint8_t;
+  static constexpr int kWords = 1;  // the live matches, whether or not their words changed
+  const uint64_t* __restrict__ claim_ptr;
+  uint32_t stale_at, expire_cap;
   // the head the queued appends reach (equal to the head slot once they have run)
-  const uint64_t hs = *head_ptr, hc = *claim_ptr;
-  const uint64_t head = hc > hs ? hc : hs;
-  unsigned long long softened = 0;
+  __device__ uint64_t head(const uint64_t* __restrict__ head_ptr) const {
+    const uint64_t hs = *head_ptr, hc = *claim_ptr;
+    return hc > hs ? hc : hs;
+  }
+  __device__ void apply(Entry* e, const KeyedRecord<Byte>& r, unsigned long long* res) const {
+    if (soften_entry(e, r, stale_at, expire_cap)) ++res[0];
+  }
+  __device__ void count(const unsigned long long*) const {}  // (no CacheCounters field)
+};
+
+// The result words of a scan: one add per non-zero word per workgroup, after its whole loop (a
+// matching purge with an add per wave spent ~0.4 ms on the same-address fan-in alone). Every
+// thread of the block must call it.
+template <int N>
+__device__ __forceinline__ void block_result(unsigned long long (&v)[N],
+                                             unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_res[N][kBlock / 64];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    v[i] = wave_sum(v[i]);
+    if ((threadIdx.x & 63) == 0) s_res[i][threadIdx.x >> 6] = v[i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      unsigned long long t = 0;
+#pragma unroll
+      for (int k = 0; k < kBlock / 64; ++k) t += s_res[i][k];
+      if (t) atomicAdd(&out[i], t);
+    }
+  }
+}
+
+template <class Matcher, class Action>
+__global__ __launch_bounds__(kBlock) void k_keyed_scan(
+    Entry* __restrict__ index, uint64_t nslots, typename Action::Byte* __restrict__ log,
+    const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
+    const Matcher m, const Action act, unsigned long long* __restrict__ out) {
+  __shared__ typename Matcher::Lds lds;
+  m.stage(lds);
+  __syncthreads();
+  const uint32_t vmin = m.vmin(lds);
+  const uint64_t head = act.head(head_ptr);
+  unsigned long long res[Action::kWords] = {};
   for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nslots;
        k += (uint64_t)gridDim.x * kBlock) {
     Entry* const e = index + k;
-    const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-    const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-    const uint64_t loc = pack2(eb.x, eb.y);
-    const uint32_t vlen = entry_vlen(eb.z);
-    if (!entry_live(loc, eb.w, head, cap, now)) continue;
-    if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) continue;
-    uint8_t* const recb = log + (loc - 1) % cap;
-    const uint4* const rec = reinterpret_cast<const uint4*>(recb);
-    const uint4 ha = rec[0], hb = rec[1];
-    // the entry's own record: digest, vlen and magic (ItemHeader's words)
-    if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-        hb.w != kItemMagic)
-      continue;
-    if (!glob_match(rec, vlen, rec[2], s_img)) continue;
-    ItemHeader* const h = reinterpret_cast<ItemHeader*>(recb);
-    if (expire_cap && (eb.w == 0 || eb.w > expire_cap)) {
-      unsigned long long* const w = reinterpret_cast<unsigned long long*>(&e->vlen);
-      unsigned long long expect = pack2(eb.z, eb.w), want = 0;
-      bool done = false;
-      for (int t = 0; t < kTouchCasTries; ++t) {
-        want = (expect & 0xffffffffull) | ((unsigned long long)expire_cap << 32);
-        const unsigned long long prev = atomicCAS(w, expect, want);
-        if (prev == expect) {
-          done = true;
-          break;
-        }
-        if ((prev ^ expect) != (unsigned long long)kRefBit) break;  // not the entry that was read
-        expect = prev;
-      }
-      if (!done) continue;
-      const uint64_t* const q = reinterpret_cast<const uint64_t*>(e);
-      const uint64_t e0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t e2 = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (e0 != pack2(ea.x, ea.y) || e1 != pack2(ea.z, ea.w) || e2 != loc) {
-        // the slot passed to another entry with an equal word: put its expiry back
-        unsigned long long cur = want;
-        for (int t = 0; t < 2; ++t) {
-          const unsigned long long prev =
-              atomicCAS(w, cur, (cur & 0xffffffffull) | (expect & ~0xffffffffull));
-          if (prev == cur || (prev ^ cur) != (unsigned long long)kRefBit) break;
-          cur = prev;
-        }
-        continue;
-      }
-      h->expire = expire_cap;
-    }
-    h->flags = stale_at;
-    ++softened;
+    KeyedRecord<typename Action::Byte> r;
+    if (!keyed_record(e, log, head, cap, max_item, now, vmin, r)) continue;
+    const uint4* const rec = r.granules();
+    if (!m.match(lds, rec, r.vlen, rec[2])) continue;
+    act.apply(e, r, res);
   }
-  __shared__ unsigned long long s_res[kBlock / 64];
-  softened = wave_sum(softened);
-  if ((threadIdx.x & 63) == 0) s_res[threadIdx.x >> 6] = softened;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) t0 += s_res[k];
-    if (t0) atomicAdd(&out[0], t0);
-  }
+  act.count(res);
+  block_result(res, out);
 }
 
 // ---- listing -------------------------------------------------------------------------------
@@ -3918,11 +3649,10 @@ __global__ __launch_bounds__(kBlock) void k_soften_glob(
 // index-slot order, one ListRow (keyed.h) and one key area each. Slot order makes a cursor
 // exact (the next page starts at the slot after the last row), which an atomic reservation
 // as k_export's cannot give, so the operation is two passes over a match bitmap:
-//   k_list_scan   k_purge_prefix's traversal by *tiles* of kBlock consecutive slots (grid-
-//                 stride over tiles, as k_export), its liveness test, record re-check and
-//                 matchers: the pattern image (exact: klen == plen too, k_soften_prefix), the
-//                 tag list (tag_block_match), or all (any plausible keyed value: 2 + klen <=
-//                 vlen, with a key of at least one byte). Each wave stores its match ballot as
+//   k_list_scan   k_keyed_scan's per-slot test (keyed_record, then the instance's matcher:
+//                 PrefixMatch, TagMatch, GlobMatch or AnyKeyedMatch) by *tiles* of kBlock
+//                 consecutive slots (grid-stride over tiles, as k_export), liveness judged at
+//                 the published head. Each wave stores its match ballot as
 //                 one 64-bit word of the bitmap (one vector store by lane 0), each tile the
 //                 number of its matches at slots >= start_slot; matched and bytes (the whole
 //                 index, whatever start_slot is) go to the result words with one add per word
@@ -3947,44 +3677,6 @@ __global__ __launch_bounds__(kBlock) void k_soften_glob(
 // claimed (k_edge_server's seqlock: a batch raises the claim word before its append). A row
 // whose entry no longer passes, or whose record the claim now reaches, is written with
 // kListChanged and klen = 0, never dropped, so the ranks of the other rows stay as counted.
-template <uint32_t mode>
-__device__ __forceinline__ bool list_slot_matches(
-    const Entry* __restrict__ e, const uint8_t* __restrict__ log, const uint64_t head,
-    const uint64_t cap, const uint32_t max_item, const uint32_t now, const uint32_t plen,
-    const uint32_t ngran, const uint32_t exact, const uint4* s_img,
-    const uint4* __restrict__ pat, const uint2* s_tags, const uint32_t nlist,
-    uint32_t* vlen_out) {
-  const uint4 ea = reinterpret_cast<const uint4*>(e)[0];
-  const uint4 eb = reinterpret_cast<const uint4*>(e)[1];
-  const uint64_t loc = pack2(eb.x, eb.y);
-  const uint32_t vlen = entry_vlen(eb.z);
-  if (!entry_live(loc, eb.w, head, cap, now)) return false;
-  const uint32_t vmin = (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen
-                                                  : mode == kListTags ? 2u
-                                                  : mode == kListGlob ? s_img[0].w : 0u);
-  if (vlen < vmin || vlen > max_item || ((loc - 1) & 15)) return false;
-  const uint4* const rec = reinterpret_cast<const uint4*>(log + (loc - 1) % cap);
-  const uint4 ha = rec[0], hb = rec[1];
-  // the entry's own record: digest, vlen and magic (ItemHeader's words)
-  if (ha.x != ea.x || ha.y != ea.y || ha.z != ea.z || ha.w != ea.w || hb.x != vlen ||
-      hb.w != kItemMagic)
-    return false;
-  const uint4 v0 = rec[2];
-  const uint32_t klen = v0.x & 0xffffu;
-  if (kKeyedPrefix + klen > vlen) return false;
-  *vlen_out = vlen;
-  if (mode == kListAll) return klen != 0;  // (an empty key names no object)
-  if (mode == kListTags) return tag_block_match(rec, vlen, v0, s_tags, nlist);
-  if (mode == kListGlob) return glob_match(rec, vlen, v0, s_img);
-  if (klen < plen || (exact && klen != plen)) return false;
-  if (!purge_granule_eq(v0, s_img[0], s_img[2])) return false;
-  const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
-  for (uint32_t g = 1; g < ngran; ++g) {
-    const uint4 p = g < (uint32_t)kPurgeLdsGranules ? s_img[2 + g] : pat[g];
-    if (!purge_granule_eq(rec[2 + g], g + 1 == ngran ? s_img[1] : ones, p)) return false;
-  }
-  return true;
-}
 
 // The bits of a wave's match word at slots >= start_slot; k0 is the slot of its bit 0.
 __device__ __forceinline__ unsigned long long list_word_from(const unsigned long long m,
@@ -3994,42 +3686,34 @@ __device__ __forceinline__ unsigned long long list_word_from(const unsigned long
   return start_slot - k0 >= 64 ? 0ull : m & (~0ull << (start_slot - k0));
 }
 
-template <uint32_t mode>
+template <class Matcher>
 __global__ __launch_bounds__(kBlock) void k_list_scan(
     const Entry* __restrict__ index, uint64_t nslots, const uint8_t* __restrict__ log,
     const uint64_t* __restrict__ head_ptr, uint64_t cap, uint32_t max_item, uint32_t now,
-    const uint4* __restrict__ img, uint32_t plen, uint32_t ngran, uint32_t exact,
-    const uint2* __restrict__ tags, uint32_t nlist, uint64_t start_slot,
-    unsigned long long* __restrict__ bitmap, uint32_t* __restrict__ tile_cnt,
-    unsigned long long* __restrict__ acc) {
-  __shared__ uint4 s_img[mode == kListGlob ? kGlobLdsGranules : 2 + kPurgeLdsGranules];
-  __shared__ uint2 s_tags[kMaxPurgeTags];
+    const Matcher m, uint64_t start_slot, unsigned long long* __restrict__ bitmap,
+    uint32_t* __restrict__ tile_cnt, unsigned long long* __restrict__ acc) {
+  __shared__ typename Matcher::Lds lds;
   // per-wave counts of a tile, two sets taken in turn: one barrier per tile
   __shared__ unsigned int s_cnt[2][kBlock / 64];
-  if (mode == kListPrefix)
-    for (uint32_t g = threadIdx.x; g < 2 + ngran && g < 2u + kPurgeLdsGranules; g += kBlock)
-      s_img[g] = img[g];
-  if (mode == kListGlob)  // (ngran: the granules of the compiled pattern in use)
-    for (uint32_t g = threadIdx.x; g < ngran && g < kGlobLdsGranules; g += kBlock)
-      s_img[g] = img[g];
-  if (mode == kListTags)
-    for (uint32_t j = threadIdx.x; j < nlist && j < kMaxPurgeTags; j += kBlock) s_tags[j] = tags[j];
-  if (nlist > kMaxPurgeTags) nlist = kMaxPurgeTags;
+  m.stage(lds);
   __syncthreads();
+  const uint32_t vmin = m.vmin(lds);
   const uint64_t head = *head_ptr;
   const uint64_t ntiles = (nslots + kBlock - 1) / kBlock;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned long long matched = 0, bytes = 0;
+  unsigned long long res[2] = {};  // kListMatched, kListBytes
   int set = 0;
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, set ^= 1) {
     const uint64_t k = tile * kBlock + threadIdx.x;
-    uint32_t vlen = 0;
-    const bool hit = k < nslots &&
-                     list_slot_matches<mode>(index + k, log, head, cap, max_item, now, plen,
-                                             ngran, exact, s_img, img + 2, s_tags, nlist, &vlen);
+    KeyedRecord<const uint8_t> r;
+    bool hit = k < nslots && keyed_record(index + k, log, head, cap, max_item, now, vmin, r);
     if (hit) {
-      ++matched;
-      bytes += item_bytes(vlen);
+      const uint4* const rec = r.granules();
+      hit = m.match(lds, rec, r.vlen, rec[2]);
+    }
+    if (hit) {
+      ++res[0];
+      res[1] += item_bytes(r.vlen);
     }
     const unsigned long long m = __ballot(hit);
     if (lane == 0) {
@@ -4044,26 +3728,10 @@ __global__ __launch_bounds__(kBlock) void k_list_scan(
       tile_cnt[tile] = t;
     }
   }
-  // the result words: one add per word per workgroup, after its whole loop (k_purge_prefix)
-  __shared__ unsigned long long s_res[2][kBlock / 64];
-  matched = wave_sum(matched);
-  bytes = wave_sum(bytes);
-  if (lane == 0) {
-    s_res[0][w] = matched;
-    s_res[1][w] = bytes;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = 0, t1 = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-      t0 += s_res[0][k];
-      t1 += s_res[1][k];
-    }
-    if (t0) atomicAdd(&acc[kListMatched], t0);
-    if (t1) atomicAdd(&acc[kListBytes], t1);
-    if (blockIdx.x == 0) acc[kListNext] = nslots;  // (k_list_emit: the cursor, if rows remain)
-  }
+  static_assert(kListMatched == 0 && kListBytes == 1, "res: the first two result words");
+  block_result(res, acc);
+  // (k_list_emit: the cursor, if rows remain)
+  if (blockIdx.x == 0 && threadIdx.x == 0) acc[kListNext] = nslots;
   // the counts' padding up to a multiple of 4 (k_list_tiles reads 16-B groups): zero, on this
   // stream, every call
   if (blockIdx.x == 0 && threadIdx.x < ((ntiles + 3) & ~3ull) - ntiles)
@@ -4173,16 +3841,8 @@ __global__ __launch_bounds__(kBlock) void k_list_emit(
         uint4* const dst = reinterpret_cast<uint4*>(keys + (uint64_t)rank * key_cap);
         dst[0] = v0;
         for (uint32_t g = 1; g < ng; ++g) dst[g] = rec[2 + g];
-        // the tag block's two header bytes (tag_block_match's reads and checks)
-        if (o + 2 <= vlen) {
-          const uint32_t ga = o >> 4, gb = (o + 1) >> 4;
-          const uint4 a = ga ? rec[2 + ga] : v0;
-          const uint4 b = gb != ga ? rec[2 + gb] : a;
-          if (granule_byte(a, o & 15u) == (uint32_t)kTagMarker) {
-            const uint32_t nt = granule_byte(b, (o + 1) & 15u);
-            if (nt == kTagOverflow || (nt <= kMaxObjectTags && o + 2 + 8 * nt <= vlen)) ntags = nt;
-          }
-        }
+        const uint32_t nt = tag_block_ntags(rec, vlen, v0);
+        if (nt != kNoTagBlock) ntags = nt;
         // every load of the record has returned: is it still out of the appends' reach?
         __threadfence();
         uint64_t newest = 0;  // head slots 0 / 1 and the claim word 4
@@ -4754,7 +4414,7 @@ HbmCache::HbmCache(const ShardConfig& cfg) : cfg_(cfg) {
   HIP_OK(hipMalloc(&index_, cfg_.nbuckets * kBucketBytes));
   HIP_OK(hipMalloc(&head_, 64));
   HIP_OK(hipMalloc(&ctr_, kCtrShards * sizeof(CacheCounters)));
-  HIP_OK(hipMalloc(&scratch_, 160));
+  HIP_OK(hipMalloc(&scratch_, kScratchWords * sizeof(unsigned long long)));
   HIP_OK(hipMalloc(&done_ctr_, 64));
   HIP_OK(hipMemset(done_ctr_, 0, 64));
   const size_t lb_words = (size_t)(kSmallGetMax / kEdgeKeys + 1);
@@ -5608,22 +5268,32 @@ void HbmCache::sweep(uint32_t now, hipStream_t s, uint64_t* live_entries, uint64
   if (live_bytes) *live_bytes = host_buf_[1];
 }
 
+template <class Matcher, class Action>
+void HbmCache::keyed_scan(const Matcher& m, const Action& act, uint32_t now, ScratchWord word,
+                          uint64_t* out, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(mu_);
+  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
+  if (std::is_same<Action, SoftenAction>::value)
+    SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
+  DeviceGuard g(cfg_.device);
+  unsigned long long* const acc = scratch_ + word;
+  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
+  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
+  hipLaunchKernelGGL((k_keyed_scan<Matcher, Action>), dim3(grid_for((int64_t)nslots, kBlock, 4096)),
+                     dim3(kBlock), 0, s, index_, nslots, log_, cur_head(), cfg_.log_bytes,
+                     cfg_.max_item, now, m, act, acc);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out, acc, Action::kWords * sizeof(uint64_t), hipMemcpyDefault, s));
+}
+
 void HbmCache::remove_keyed_prefix(const uint8_t* image, uint32_t plen, uint32_t now,
                                    uint64_t* out, hipStream_t s) {
   TraceRange tr("hbm.purge_prefix");
   SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
   SH_CHECK(image && out, "purge needs a pattern image and a result buffer");
-  std::lock_guard<std::mutex> lk(mu_);
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 4;  // (words 0..1 are sweep's and export's)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_purge_prefix, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
-                     0, s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
-                     reinterpret_cast<const uint4*>(image), plen,
-                     (uint32_t)keyed_prefix_granules(plen), acc, ctr_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(PrefixMatch{reinterpret_cast<const uint4*>(image), plen,
+                         (uint32_t)keyed_prefix_granules(plen), 0u},
+             RemoveAction{ctr_}, now, kScratchPurgePrefix, out, s);
 }
 
 void HbmCache::soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exact,
@@ -5633,20 +5303,9 @@ void HbmCache::soften_keyed_prefix(const uint8_t* image, uint32_t plen, bool exa
   SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
   SH_CHECK(image && out, "purge needs a pattern image and a result buffer");
   SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
-  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 6;  // (0..1: sweep, export; 4..5: purge)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_soften_prefix, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
-                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
-                     cfg_.max_item, now, reinterpret_cast<const uint4*>(image), plen,
-                     (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u, stale_at, expire_cap,
-                     acc);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(PrefixMatch{reinterpret_cast<const uint4*>(image), plen,
+                         (uint32_t)keyed_prefix_granules(plen), exact ? 1u : 0u},
+             SoftenAction{claim_ptr(), stale_at, expire_cap}, now, kScratchSoftenPrefix, out, s);
 }
 
 void HbmCache::remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now,
@@ -5654,16 +5313,8 @@ void HbmCache::remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t 
   TraceRange tr("hbm.purge_tags");
   SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
   SH_CHECK(tags && out, "tag purge needs a tag list and a result buffer");
-  std::lock_guard<std::mutex> lk(mu_);
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 8;  // (0..7: sweep, export, the prefix purges)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_purge_tags, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock), 0,
-                     s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
-                     reinterpret_cast<const uint2*>(tags), ntags, acc, ctr_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(TagMatch{reinterpret_cast<const uint2*>(tags), ntags}, RemoveAction{ctr_}, now,
+             kScratchPurgeTags, out, s);
 }
 
 void HbmCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
@@ -5673,19 +5324,8 @@ void HbmCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t 
   SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
   SH_CHECK(tags && out, "tag purge needs a tag list and a result buffer");
   SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
-  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 10;  // (8..9: the hard tag purge)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_soften_tags, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
-                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
-                     cfg_.max_item, now, reinterpret_cast<const uint2*>(tags), ntags, stale_at,
-                     expire_cap, acc);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(TagMatch{reinterpret_cast<const uint2*>(tags), ntags},
+             SoftenAction{claim_ptr(), stale_at, expire_cap}, now, kScratchSoftenTags, out, s);
 }
 
 static bool glob_image_bytes_ok(uint32_t n) {
@@ -5697,16 +5337,8 @@ void HbmCache::remove_keyed_glob(const uint8_t* image, uint32_t image_bytes, uin
   TraceRange tr("hbm.purge_glob");
   SH_CHECK(image && glob_image_bytes_ok(image_bytes), "glob purge needs a compiled pattern");
   SH_CHECK(out, "glob purge needs a result buffer");
-  std::lock_guard<std::mutex> lk(mu_);
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 16;  // (0..15: sweep, export, the purges, list)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_purge_glob, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock), 0,
-                     s, index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
-                     reinterpret_cast<const uint4*>(image), image_bytes / 16, acc, ctr_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, 2 * sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(GlobMatch{reinterpret_cast<const uint4*>(image), image_bytes / 16},
+             RemoveAction{ctr_}, now, kScratchPurgeGlob, out, s);
 }
 
 void HbmCache::soften_keyed_glob(const uint8_t* image, uint32_t image_bytes, uint32_t stale_at,
@@ -5716,19 +5348,8 @@ void HbmCache::soften_keyed_glob(const uint8_t* image, uint32_t image_bytes, uin
   SH_CHECK(image && glob_image_bytes_ok(image_bytes), "glob purge needs a compiled pattern");
   SH_CHECK(out, "glob purge needs a result buffer");
   SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  // a detached hand's move rewrites an entry's {vlen | expire} word from the value it staged
-  SH_CHECK(!pend_.active, "soft purge while a phase-1 SET batch is pending");
-  DeviceGuard g(cfg_.device);
-  unsigned long long* const acc = scratch_ + 18;  // (16..17: the hard glob purge)
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), s));  // (a whole 16-B block)
-  const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
-  hipLaunchKernelGGL(k_soften_glob, dim3(grid_for((int64_t)nslots, kBlock, 4096)), dim3(kBlock),
-                     0, s, index_, nslots, log_, cur_head(), claim_ptr(), cfg_.log_bytes,
-                     cfg_.max_item, now, reinterpret_cast<const uint4*>(image), image_bytes / 16,
-                     stale_at, expire_cap, acc);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, acc, sizeof(uint64_t), hipMemcpyDefault, s));
+  keyed_scan(GlobMatch{reinterpret_cast<const uint4*>(image), image_bytes / 16},
+             SoftenAction{claim_ptr(), stale_at, expire_cap}, now, kScratchSoftenGlob, out, s);
 }
 
 void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bool exact,
@@ -5739,7 +5360,7 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
   const uint64_t nslots = cfg_.nbuckets * kEntriesPerBucket;
   SH_CHECK(mode == kListPrefix || mode == kListTags || mode == kListAll || mode == kListGlob,
            "list: unknown mode");
-  uint32_t ngran = (uint32_t)keyed_prefix_granules(0);  // (by tag, all: unused by the scan)
+  uint32_t ngran = 0;  // (the granules of the prefix image's pattern, or of the compiled glob)
   if (mode == kListPrefix) {
     SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "list prefix must hold 1..65535 bytes");
     SH_CHECK(image, "list by prefix needs a pattern image");
@@ -5748,17 +5369,9 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
     // (plen: the bytes of the compiled pattern in use, keyed_glob_used_bytes())
     SH_CHECK(image && glob_image_bytes_ok(plen), "list by glob needs a compiled pattern");
     ngran = plen / 16;
-    plen = 0;
-    exact = false;
-  } else {
-    plen = 0;
-    exact = false;
-  }
-  if (mode == kListTags) {
+  } else if (mode == kListTags) {
     SH_CHECK(ntags >= 1 && ntags <= kMaxPurgeTags, "list by tag takes 1..64 tags");
     SH_CHECK(tags, "list by tag needs a tag list");
-  } else {
-    ntags = 0;
   }
   SH_CHECK(limit <= kMaxListRows, "list: at most 4096 rows a call");
   SH_CHECK(key_cap >= kListKeyCapMin && key_cap <= kListKeyCapMax && key_cap % 16 == 0,
@@ -5781,17 +5394,20 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
   unsigned long long* const bitmap = reinterpret_cast<unsigned long long*>(list_ws_);
   uint32_t* const tile_cnt = reinterpret_cast<uint32_t*>(list_ws_ + bitmap_bytes);
   uint32_t* const tile_base = tile_cnt + ntiles4;
-  unsigned long long* const acc = scratch_ + 12;  // (0..11: sweep, export, the purges)
+  unsigned long long* const acc = scratch_ + kScratchList;
   HIP_OK(hipMemsetAsync(acc, 0, kListWords * sizeof(unsigned long long), s));
   // (one instance per matcher: the three in one kernel cost a wave per SIMD in registers)
-  const auto scan = mode == kListPrefix ? k_list_scan<kListPrefix>
-                    : mode == kListTags ? k_list_scan<kListTags>
-                    : mode == kListGlob ? k_list_scan<kListGlob> : k_list_scan<kListAll>;
-  hipLaunchKernelGGL(scan, dim3(grid_for((int64_t)ntiles, 1, 4096)), dim3(kBlock), 0, s,
-                     index_, nslots, log_, cur_head(), cfg_.log_bytes, cfg_.max_item, now,
-                     reinterpret_cast<const uint4*>(image), plen, ngran, exact ? 1u : 0u,
-                     reinterpret_cast<const uint2*>(tags), ntags, start_slot, bitmap, tile_cnt,
-                     acc);
+  const auto scan = [&](const auto& m) {
+    using Matcher = std::decay_t<decltype(m)>;
+    hipLaunchKernelGGL(k_list_scan<Matcher>, dim3(grid_for((int64_t)ntiles, 1, 4096)),
+                       dim3(kBlock), 0, s, index_, nslots, log_, cur_head(), cfg_.log_bytes,
+                       cfg_.max_item, now, m, start_slot, bitmap, tile_cnt, acc);
+  };
+  const uint4* const img = reinterpret_cast<const uint4*>(image);
+  if (mode == kListPrefix) scan(PrefixMatch{img, plen, ngran, exact ? 1u : 0u});
+  else if (mode == kListTags) scan(TagMatch{reinterpret_cast<const uint2*>(tags), ntags});
+  else if (mode == kListGlob) scan(GlobMatch{img, ngran});
+  else scan(AnyKeyedMatch{});
   HIP_OK(hipGetLastError());
   if (limit) {  // (0: the count-only form)
     hipLaunchKernelGGL(k_list_tiles, dim3(1), dim3(kBlock), 0, s, tile_cnt, ntiles4, tile_base,

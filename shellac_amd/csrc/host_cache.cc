@@ -375,193 +375,150 @@ void HostCache::sweep(uint32_t now, uint64_t* live_entries, uint64_t* live_bytes
   if (live_bytes) *live_bytes = bytes;
 }
 
-void HostCache::remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now,
-                                    uint64_t out[2]) {
-  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+// ---- the keyed index scans (HbmCache's k_keyed_scan / k_list_scan, whose reference these are)
+
+uint8_t* HostCache::keyed_record(uint64_t k, uint32_t now, uint32_t vmin, uint32_t* vlen_out) {
+  const Entry& e = index_[k];
+  if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) return nullptr;
+  const uint32_t vlen = entry_vlen(e.vlen);
+  // (vlen <= max_item and an aligned loc hold for every stored entry: they keep the reads
+  // of an entry debug_set_entry made up inside the log's slack)
+  if (vlen < vmin || vlen > max_item_ || ((e.loc - 1) & 15)) return nullptr;
+  uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
+  ItemHeader h;
+  std::memcpy(&h, rec, sizeof(h));
+  if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) return nullptr;
+  *vlen_out = vlen;
+  return rec;
+}
+
+template <class Match, class Act>
+void HostCache::keyed_scan(uint32_t now, Match match, Act act) {
+  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
+  const uint32_t vmin = match.vmin();
+  for (uint64_t k = 0; k < nslots; ++k) {
+    uint32_t vlen;
+    uint8_t* const rec = keyed_record(k, now, vmin, &vlen);
+    if (rec && match(rec + kItemHeaderBytes, vlen)) act(k, rec, vlen);
+  }
+}
+
+template <class Match>
+void HostCache::remove_keyed(uint32_t now, Match match, uint64_t out[2]) {
   std::lock_guard<std::mutex> lk(mu_);
   uint64_t removed = 0, bytes = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    Entry& e = index_[k];
-    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
-    const uint32_t vlen = entry_vlen(e.vlen);
-    // (vlen <= max_item and an aligned loc hold for every stored entry: they keep the reads
-    // of an entry debug_set_entry made up inside the log's slack)
-    if (vlen < kKeyedPrefix + plen || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
-    const uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
-    ItemHeader h;
-    std::memcpy(&h, rec, sizeof(h));
-    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
-    const uint8_t* const v = rec + kItemHeaderBytes;
-    uint16_t klen;
-    std::memcpy(&klen, v, kKeyedPrefix);
-    if (klen < plen || kKeyedPrefix + klen > vlen) continue;
-    if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
-    e.loc = 0;
+  keyed_scan(now, match, [&](uint64_t k, uint8_t*, uint32_t vlen) {
+    index_[k].loc = 0;
     ++removed;
     bytes += item_bytes(vlen);
-  }
+  });
   ctr_.purged += removed;
   if (out) {
     out[0] = removed;
     out[1] = bytes;
   }
+}
+
+template <class Match>
+uint64_t HostCache::soften_keyed(uint32_t now, Match match, uint32_t stale_at,
+                                 uint32_t expire_cap) {
+  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
+  std::lock_guard<std::mutex> lk(mu_);
+  uint64_t softened = 0;
+  keyed_scan(now, match, [&](uint64_t k, uint8_t* rec, uint32_t) {
+    Entry& e = index_[k];
+    ItemHeader h;
+    std::memcpy(&h, rec, sizeof(h));
+    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
+    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
+      e.expire = expire_cap;
+      h.expire = expire_cap;
+    }
+    h.flags = stale_at;
+    std::memcpy(rec, &h, sizeof(h));
+    ++softened;
+  });
+  return softened;
+}
+
+namespace {
+
+// The matchers: the least vlen a match can have, and whether the keyed value v[0..vlen) of a
+// record keyed_record passed matches.
+struct PrefixMatch {  // the stored key starts with (exact: equals) prefix[0..plen)
+  const uint8_t* prefix;
+  uint32_t plen;
+  bool exact;
+  uint32_t vmin() const { return (uint32_t)kKeyedPrefix + plen; }
+  bool operator()(const uint8_t* v, uint32_t vlen) const {
+    uint16_t klen;
+    std::memcpy(&klen, v, kKeyedPrefix);
+    if ((exact ? klen != plen : klen < plen) || kKeyedPrefix + klen > vlen) return false;
+    return std::memcmp(v + kKeyedPrefix, prefix, plen) == 0;
+  }
+};
+
+struct TagMatch {  // the value's tag block matches tags[0..ntags)
+  const uint64_t* tags;
+  uint32_t ntags;
+  uint32_t vmin() const { return (uint32_t)kKeyedPrefix + 2u; }
+  bool operator()(const uint8_t* v, uint32_t vlen) const {
+    return keyed_tags_match(v, vlen, tags, ntags);
+  }
+};
+
+struct GlobMatch {  // the stored key's subject matches the compiled pattern
+  const KeyedGlob& g;
+  uint32_t vmin() const { return (uint32_t)kKeyedPrefix + g.min_len; }
+  bool operator()(const uint8_t* v, uint32_t vlen) const {
+    return keyed_value_glob_matches(g, v, vlen);
+  }
+};
+
+struct AnyKeyedMatch {  // any plausible keyed value (an empty key names no object)
+  uint32_t vmin() const { return (uint32_t)kKeyedPrefix; }
+  bool operator()(const uint8_t* v, uint32_t vlen) const {
+    uint16_t klen;
+    std::memcpy(&klen, v, kKeyedPrefix);
+    return klen != 0 && kKeyedPrefix + klen <= vlen;
+  }
+};
+
+}  // namespace
+
+void HostCache::remove_keyed_prefix(const uint8_t* prefix, uint32_t plen, uint32_t now,
+                                    uint64_t out[2]) {
+  SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
+  remove_keyed(now, PrefixMatch{prefix, plen, false}, out);
 }
 
 uint64_t HostCache::soften_keyed_prefix(const uint8_t* prefix, uint32_t plen, bool exact,
                                         uint32_t stale_at, uint32_t expire_cap, uint32_t now) {
   SH_CHECK(plen >= 1 && plen <= kMaxKeyedKey, "purge prefix must hold 1..65535 bytes");
-  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  uint64_t softened = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    Entry& e = index_[k];
-    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
-    const uint32_t vlen = entry_vlen(e.vlen);
-    if (vlen < kKeyedPrefix + plen || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
-    uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
-    ItemHeader h;
-    std::memcpy(&h, rec, sizeof(h));
-    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
-    const uint8_t* const v = rec + kItemHeaderBytes;
-    uint16_t klen;
-    std::memcpy(&klen, v, kKeyedPrefix);
-    if ((exact ? klen != plen : klen < plen) || kKeyedPrefix + klen > vlen) continue;
-    if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
-    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
-    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
-      e.expire = expire_cap;
-      h.expire = expire_cap;
-    }
-    h.flags = stale_at;
-    std::memcpy(rec, &h, sizeof(h));
-    ++softened;
-  }
-  return softened;
-}
-
-// The record of slot k if the entry is live, its own (digest, vlen, magic) and a candidate for
-// the tag scan; else null.
-uint8_t* HostCache::tag_scan_record(uint64_t k, uint32_t now, uint32_t* vlen_out) {
-  Entry& e = index_[k];
-  if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) return nullptr;
-  const uint32_t vlen = entry_vlen(e.vlen);
-  if (vlen < kKeyedPrefix + 2 || vlen > max_item_ || ((e.loc - 1) & 15)) return nullptr;
-  uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
-  ItemHeader h;
-  std::memcpy(&h, rec, sizeof(h));
-  if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) return nullptr;
-  *vlen_out = vlen;
-  return rec;
+  return soften_keyed(now, PrefixMatch{prefix, plen, exact}, stale_at, expire_cap);
 }
 
 void HostCache::remove_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t now,
                                   uint64_t out[2]) {
   SH_CHECK(tags && ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
-  std::lock_guard<std::mutex> lk(mu_);
-  uint64_t removed = 0, bytes = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    uint32_t vlen;
-    const uint8_t* const rec = tag_scan_record(k, now, &vlen);
-    if (!rec || !keyed_tags_match(rec + kItemHeaderBytes, vlen, tags, ntags)) continue;
-    index_[k].loc = 0;
-    ++removed;
-    bytes += item_bytes(vlen);
-  }
-  ctr_.purged += removed;
-  if (out) {
-    out[0] = removed;
-    out[1] = bytes;
-  }
+  remove_keyed(now, TagMatch{tags, ntags}, out);
 }
 
 uint64_t HostCache::soften_keyed_tags(const uint64_t* tags, uint32_t ntags, uint32_t stale_at,
                                       uint32_t expire_cap, uint32_t now) {
   SH_CHECK(tags && ntags >= 1 && ntags <= kMaxPurgeTags, "tag purge takes 1..64 tags");
-  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  uint64_t softened = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    uint32_t vlen;
-    uint8_t* const rec = tag_scan_record(k, now, &vlen);
-    if (!rec || !keyed_tags_match(rec + kItemHeaderBytes, vlen, tags, ntags)) continue;
-    Entry& e = index_[k];
-    ItemHeader h;
-    std::memcpy(&h, rec, sizeof(h));
-    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
-    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
-      e.expire = expire_cap;
-      h.expire = expire_cap;
-    }
-    h.flags = stale_at;
-    std::memcpy(rec, &h, sizeof(h));
-    ++softened;
-  }
-  return softened;
-}
-
-// The record of slot k if the entry is live, its own and long enough for the pattern; else null.
-uint8_t* HostCache::glob_scan_record(uint64_t k, uint32_t now, const KeyedGlob& g,
-                                     uint32_t* vlen_out) {
-  Entry& e = index_[k];
-  if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) return nullptr;
-  const uint32_t vlen = entry_vlen(e.vlen);
-  if (vlen < kKeyedPrefix + g.min_len || vlen > max_item_ || ((e.loc - 1) & 15)) return nullptr;
-  uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
-  ItemHeader h;
-  std::memcpy(&h, rec, sizeof(h));
-  if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) return nullptr;
-  *vlen_out = vlen;
-  return rec;
+  return soften_keyed(now, TagMatch{tags, ntags}, stale_at, expire_cap);
 }
 
 void HostCache::remove_keyed_glob(const KeyedGlob& g, uint32_t now, uint64_t out[2]) {
   SH_CHECK(g.lit_bytes >= 1 && g.lit_bytes <= kMaxGlobLiteral, "glob purge needs a compiled pattern");
-  std::lock_guard<std::mutex> lk(mu_);
-  uint64_t removed = 0, bytes = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    uint32_t vlen;
-    const uint8_t* const rec = glob_scan_record(k, now, g, &vlen);
-    if (!rec || !keyed_value_glob_matches(g, rec + kItemHeaderBytes, vlen)) continue;
-    index_[k].loc = 0;
-    ++removed;
-    bytes += item_bytes(vlen);
-  }
-  ctr_.purged += removed;
-  if (out) {
-    out[0] = removed;
-    out[1] = bytes;
-  }
+  remove_keyed(now, GlobMatch{g}, out);
 }
 
 uint64_t HostCache::soften_keyed_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap,
                                       uint32_t now) {
   SH_CHECK(g.lit_bytes >= 1 && g.lit_bytes <= kMaxGlobLiteral, "glob purge needs a compiled pattern");
-  SH_CHECK(expire_cap == 0 || expire_cap > now, "soft purge: the expiry cap must lie after now");
-  std::lock_guard<std::mutex> lk(mu_);
-  uint64_t softened = 0;
-  const uint64_t nslots = nbuckets_ * kEntriesPerBucket;
-  for (uint64_t k = 0; k < nslots; ++k) {
-    uint32_t vlen;
-    uint8_t* const rec = glob_scan_record(k, now, g, &vlen);
-    if (!rec || !keyed_value_glob_matches(g, rec + kItemHeaderBytes, vlen)) continue;
-    Entry& e = index_[k];
-    ItemHeader h;
-    std::memcpy(&h, rec, sizeof(h));
-    // shorten only: the cap replaces "never" and any later expiry (vlen and kRefBit stay)
-    if (expire_cap && (e.expire == 0 || e.expire > expire_cap)) {
-      e.expire = expire_cap;
-      h.expire = expire_cap;
-    }
-    h.flags = stale_at;
-    std::memcpy(rec, &h, sizeof(h));
-    ++softened;
-  }
-  return softened;
+  return soften_keyed(now, GlobMatch{g}, stale_at, expire_cap);
 }
 
 void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, bool exact,
@@ -588,40 +545,20 @@ void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, 
   SH_CHECK(out && (limit == 0 || (rows && keys)), "list needs result words, rows and a key buffer");
   std::lock_guard<std::mutex> lk(mu_);
   uint64_t matched = 0, bytes = 0, listed = 0, next = nslots;
-  for (uint64_t k = 0; k < nslots; ++k) {
+  const auto row = [&](uint64_t k, uint8_t* rec, uint32_t vlen) {
+    ++matched;
+    bytes += item_bytes(vlen);
+    if (k < start_slot || limit == 0) return;
+    if (listed == limit) {  // further matches remain: the cursor is the slot after the last row
+      if (next == nslots) next = rows[limit - 1].slot + 1;
+      return;
+    }
     const Entry& e = index_[k];
-    if (!entry_live(e.loc, e.expire, head_, log_bytes_, now)) continue;
-    const uint32_t vlen = entry_vlen(e.vlen);
-    const uint32_t vmin =
-        (uint32_t)kKeyedPrefix + (mode == kListPrefix ? plen
-                                  : mode == kListTags ? 2u
-                                  : mode == kListGlob ? glob.min_len : 0u);
-    if (vlen < vmin || vlen > max_item_ || ((e.loc - 1) & 15)) continue;
-    const uint8_t* const rec = log_ + (e.loc - 1) % log_bytes_;
     ItemHeader h;
     std::memcpy(&h, rec, sizeof(h));
-    if (h.magic != kItemMagic || h.d0 != e.d0 || h.d1 != e.d1 || h.vlen != vlen) continue;
     const uint8_t* const v = rec + kItemHeaderBytes;
     uint16_t klen;
     std::memcpy(&klen, v, kKeyedPrefix);
-    if (kKeyedPrefix + klen > vlen) continue;
-    if (mode == kListPrefix) {
-      if (exact ? klen != plen : klen < plen) continue;
-      if (std::memcmp(v + kKeyedPrefix, prefix, plen) != 0) continue;
-    } else if (mode == kListTags) {
-      if (!keyed_tags_match(v, vlen, tags, ntags)) continue;
-    } else if (mode == kListGlob) {
-      if (!keyed_value_glob_matches(glob, v, vlen)) continue;
-    } else if (klen == 0) {
-      continue;  // (an empty key names no object)
-    }
-    ++matched;
-    bytes += item_bytes(vlen);
-    if (k < start_slot || limit == 0) continue;
-    if (listed == limit) {  // further matches remain: the cursor is the slot after the last row
-      if (next == nslots) next = rows[limit - 1].slot + 1;
-      continue;
-    }
     ListRow& r = rows[listed];
     std::memset(&r, 0, sizeof(r));
     r.slot = k;
@@ -638,7 +575,11 @@ void HostCache::list_keyed(uint32_t mode, const uint8_t* prefix, uint32_t plen, 
     const size_t need = (kKeyedPrefix + (size_t)klen + 15) / 16 * 16;
     std::memcpy(keys + listed * (uint64_t)key_cap, v, need < key_cap ? need : key_cap);
     ++listed;
-  }
+  };
+  if (mode == kListPrefix) keyed_scan(now, PrefixMatch{prefix, plen, exact}, row);
+  else if (mode == kListTags) keyed_scan(now, TagMatch{tags, ntags}, row);
+  else if (mode == kListGlob) keyed_scan(now, GlobMatch{glob}, row);
+  else keyed_scan(now, AnyKeyedMatch{}, row);
   out[kListMatched] = matched;
   out[kListBytes] = bytes;
   out[kListListed] = listed;

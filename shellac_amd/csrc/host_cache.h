@@ -108,8 +108,18 @@ class HostCache {
   uint64_t reinsert_max() const { return evict_ ? rmax_ : 0; }
 
  private:
-  uint8_t* tag_scan_record(uint64_t k, uint32_t now, uint32_t* vlen_out);
-  uint8_t* glob_scan_record(uint64_t k, uint32_t now, const KeyedGlob& g, uint32_t* vlen_out);
+  // The keyed index scans (purge, soft purge, listing). keyed_record: the record of slot k if
+  // its entry is live, its own (digest, vlen, magic) and of vmin..max_item value bytes, else
+  // null. keyed_scan: act(k, rec, vlen) for every slot, in slot order, whose record passes
+  // keyed_record with match.vmin() and whose keyed value passes match(v, vlen). remove_keyed
+  // and soften_keyed are the two actions the purges share, with their results and checks.
+  uint8_t* keyed_record(uint64_t k, uint32_t now, uint32_t vmin, uint32_t* vlen_out);
+  template <class Match, class Act>
+  void keyed_scan(uint32_t now, Match match, Act act);
+  template <class Match>
+  void remove_keyed(uint32_t now, Match match, uint64_t out[2]);
+  template <class Match>
+  uint64_t soften_keyed(uint32_t now, Match match, uint32_t stale_at, uint32_t expire_cap);
   struct Row {  // one SET row of a (possibly combined) batch
     Digest key;
     const uint8_t* val;

@@ -828,7 +828,7 @@ class CacheShard:
         """Prefix purge: remove every live object whose stored key starts with ``prefix``
         (1..65535 bytes; an empty prefix is ``flush``). Returns (objects removed, their
         item bytes); the objects are also counted in ``counters()["purged"]``. Synchronises,
-        like ``sweep``. On a GPU shard ``k_purge_prefix`` walks the index and compares the
+        like ``sweep``. On a GPU shard ``k_keyed_scan<PrefixMatch, RemoveAction>`` walks the index and compares the
         key bytes stored in the value log.
 
         Defined for *keyed* values only (``keyed(key, payload)``, what the proxy's backends
@@ -856,7 +856,7 @@ class CacheShard:
         shard's clock, and after ``now``): a life is only shortened. The value, its place and
         the CLOCK reference bit stay. Returns the number of live matching objects, whether
         or not their words changed. Synchronises, like ``remove_keyed_prefix``; on a GPU
-        shard ``k_soften_prefix`` does the scan. Defined for keyed values only."""
+        shard ``k_keyed_scan<PrefixMatch, SoftenAction>`` does the scan. Defined for keyed values only."""
         prefix = bytes(prefix)
         if not 1 <= len(prefix) <= 0xFFFF:
             raise ValueError("purge prefix must hold 1..65535 bytes")
@@ -886,7 +886,7 @@ class CacheShard:
         """Purge by surrogate key: removes every live object whose stored keyed value carries
         a tag block (``tagged``) naming one of ``tags`` (1..64 byte strings), or the overflow
         block. Returns ``(objects removed, their item bytes)``; synchronises, like
-        ``remove_keyed_prefix``. On a GPU shard ``k_purge_tags`` does the scan."""
+        ``remove_keyed_prefix``. On a GPU shard ``k_keyed_scan<TagMatch, RemoveAction>`` does the scan."""
         hashes = self._tag_list(tags)
         now = self.now() if now is None else now
         if not self.is_gpu:
@@ -903,7 +903,7 @@ class CacheShard:
         """Soft purge by surrogate key: ``remove_keyed_tags``' matcher with
         ``soften_keyed_prefix``'s action and contract (``flags = stale_at``, the expiry capped
         at ``expire_cap`` and never extended, the count of live matches). Synchronises; on a
-        GPU shard ``k_soften_tags`` does the scan."""
+        GPU shard ``k_keyed_scan<TagMatch, SoftenAction>`` does the scan."""
         hashes = self._tag_list(tags)
         now = self.now() if now is None else now
         stale_at, expire_cap = int(stale_at) & 0xFFFFFFFF, int(expire_cap)
@@ -929,7 +929,7 @@ class CacheShard:
         literal, and the match is anchored at both ends. At most 8 stars and 1024 literal
         bytes; an empty pattern, stars only (that is ``flush``) and a dangling ``\\`` raise
         ``ValueError``. Returns ``(objects removed, their item bytes)``; synchronises, like
-        ``remove_keyed_prefix``. On a GPU shard ``k_purge_glob`` does the scan."""
+        ``remove_keyed_prefix``. On a GPU shard ``k_keyed_scan<GlobMatch, RemoveAction>`` does the scan."""
         image = self._glob_image(pattern)
         now = self.now() if now is None else now
         if not self.is_gpu:
@@ -946,7 +946,7 @@ class CacheShard:
         """Soft purge by glob: ``remove_keyed_glob``'s matcher with ``soften_keyed_prefix``'s
         action and contract (``flags = stale_at``, the expiry capped at ``expire_cap`` and
         never extended, the count of live matches). Synchronises; on a GPU shard
-        ``k_soften_glob`` does the scan."""
+        ``k_keyed_scan<GlobMatch, SoftenAction>`` does the scan."""
         image = self._glob_image(pattern)
         now = self.now() if now is None else now
         stale_at, expire_cap = int(stale_at) & 0xFFFFFFFF, int(expire_cap)

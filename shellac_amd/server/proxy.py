@@ -170,7 +170,7 @@ class Server:
         whose key starts with the URL's key (on the HBM tier: a scan kernel per GPU); with
         ``X-Purge-Mode: glob`` every object whose key, up to a Vary variant's separator,
         matches the URL's key as a pattern in which ``*`` is any run of bytes and everything
-        else is literal (at most 8 stars and 1024 literal bytes; ``k_purge_glob``). With
+        else is literal (at most 8 stars and 1024 literal bytes; ``k_keyed_scan<GlobMatch, RemoveAction>``). With
         ``X-Purge-Soft: 1`` and ``grace`` the same objects are kept and made stale instead:
         the next request is served from the stale copy and revalidated in the background,
         and their lives are capped at ``grace`` seconds from now (never extended). Without
@@ -181,7 +181,7 @@ class Server:
         keys, e.g. ``Surrogate-Key``, ``xkey`` or ``Cache-Tag`` (separated by spaces, tabs or
         commas). ``PURGE`` with ``X-Purge-Mode: tag`` and that header naming 1..64 tags
         removes every object carrying one of them, whatever its URL (on the HBM tier:
-        ``k_purge_tags``); with ``X-Purge-Soft: 1`` and ``grace`` they are made stale
+        ``k_keyed_scan<TagMatch, RemoveAction>``); with ``X-Purge-Soft: 1`` and ``grace`` they are made stale
         instead. A response naming more than 32 distinct tags matches every tag purge.
         ``inspect``: who may ``GET /_shellac/objects`` (``"off"``, ``"loopback"``, ``"any"``): the
         read-only listing of what is cached by ``?prefix=``, ``?key=``, ``?tag=a,b``, ``?glob=`` or

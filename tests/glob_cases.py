@@ -1,7 +1,7 @@
 """Scenarios shared by tests/test_glob_purge.py (CPU) and tests/test_glob_purge_gpu.py: the
 Python model of the glob matcher (a regex on the key's base, the key up to its first 0x1f),
-and the runs the twins (HostCache on the CPU; k_purge_glob, k_soften_glob and
-k_list_scan<kListGlob> on the GPU) are checked with, in the hard, soft and list forms. Every
+and the runs the twins (HostCache on the CPU; k_keyed_scan<GlobMatch, RemoveAction>, k_keyed_scan<GlobMatch, SoftenAction> and
+k_list_scan<GlobMatch> on the GPU) are checked with, in the hard, soft and list forms. Every
 shard is compared with the model of what it holds itself."""
 import json
 import random

@@ -1,6 +1,6 @@
 """Scenarios shared by tests/test_purge.py (CPU) and tests/test_purge_gpu.py: keyed objects
 over a handful of path families, a Python model of a prefix purge, and the runs both twins
-(HostCache on the CPU, k_purge_prefix on the GPU) are checked with."""
+(HostCache on the CPU, k_keyed_scan<PrefixMatch, RemoveAction> on the GPU) are checked with."""
 import json
 import random
 import struct

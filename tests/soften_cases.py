@@ -1,6 +1,6 @@
 """Scenarios shared by tests/test_soft_purge.py (CPU) and tests/test_soft_purge_gpu.py: a
 Python model of a soft purge, helpers that read flags and header expiries back, and the runs
-both twins (HostCache on the CPU, k_soften_prefix on the GPU) are checked with. Every run
+both twins (HostCache on the CPU, k_keyed_scan<PrefixMatch, SoftenAction> on the GPU) are checked with. Every run
 takes explicit `now` values, so nothing here waits for a clock."""
 import json
 

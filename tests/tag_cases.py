@@ -1,6 +1,6 @@
 """Scenarios shared by tests/test_tag_purge.py (CPU) and tests/test_tag_purge_gpu.py: a Python
 model of the tag block and of a purge by tag, builders for tagged, hostile and truncated
-values, the runs the twins (HostCache on the CPU, k_purge_tags / k_soften_tags on the GPU) are
+values, the runs the twins (HostCache on the CPU, k_keyed_scan<TagMatch, RemoveAction> / k_keyed_scan<TagMatch, SoftenAction> on the GPU) are
 checked with, and a small origin that emits a tag header. Every engine run takes explicit
 `now` values, so nothing here waits for a clock."""
 import gzip

@@ -1,6 +1,6 @@
 """Purge, soft purge and listing by URL glob on the CPU: the host matcher against the regex
-model, HostCache's glob walks (the semantic reference of k_purge_glob / k_soften_glob /
-k_list_scan<kListGlob>) over the scenarios of tests/glob_cases.py, the DRAM, tiered and
+model, HostCache's glob walks (the semantic reference of k_keyed_scan<GlobMatch, RemoveAction> / k_keyed_scan<GlobMatch, SoftenAction> /
+k_list_scan<GlobMatch>) over the scenarios of tests/glob_cases.py, the DRAM, tiered and
 memcached tiers, the proxy's PURGE with X-Purge-Mode: glob and /_shellac/objects?glob= over
 DRAM, and the host-only code under sanitizers."""
 import itertools

@@ -1,5 +1,5 @@
-"""Purge, soft purge and listing by URL glob on the GPU: k_purge_glob / k_soften_glob /
-k_list_scan<kListGlob> against the host twin and the regex model over the scenarios of
+"""Purge, soft purge and listing by URL glob on the GPU: k_keyed_scan<GlobMatch, RemoveAction> / k_keyed_scan<GlobMatch, SoftenAction> /
+k_list_scan<GlobMatch> against the host twin and the regex model over the scenarios of
 tests/glob_cases.py, the HBM backend's glob requests with hot replicas, and the proxy's
 X-Purge-Mode: glob and /_shellac/objects?glob= over the HBM tier."""
 import time

@@ -1,4 +1,4 @@
-"""Cache invalidation on the GPU: k_purge_prefix against its host twin and a Python model,
+"""Cache invalidation on the GPU: k_keyed_scan<PrefixMatch, RemoveAction> against its host twin and a Python model,
 the HBM backend's purge request, hot replicas, and the proxy's PURGE over the HBM tier."""
 import time
 

@@ -1,4 +1,4 @@
-"""Soft purge on the GPU: k_soften_prefix against its host twin and the Python model, the
+"""Soft purge on the GPU: k_keyed_scan<PrefixMatch, SoftenAction> against its host twin and the Python model, the
 HBM backend's soft purge request, hot replicas, and the proxy's PURGE with X-Purge-Soft over
 the HBM tier."""
 import time

@@ -1,4 +1,4 @@
-"""Purge by surrogate key on the GPU: k_purge_tags / k_soften_tags against the host twin and
+"""Purge by surrogate key on the GPU: k_keyed_scan<TagMatch, RemoveAction> / k_keyed_scan<TagMatch, SoftenAction> against the host twin and
 the Python model, the HBM backend's tag purge request, hot replicas, a shard out of service,
 and the proxy's --tag-header over the HBM tier."""
 import time
