@@ -216,6 +216,10 @@ void TieredBackend::get(const std::string& key, const Digest& d, Executor* ex, G
 }
 
 PartValue slice_cache_value(bool hit, CacheValue v, const SliceSpec& spec) {
+  return slice_cache_value_if(hit, std::move(v), spec, PartCond{});
+}
+
+PartValue slice_cache_value_if(bool hit, CacheValue v, const SliceSpec& spec, const PartCond& cond) {
   PartValue p;
   if (!hit || !v.data) return p;
   p.flags = v.flags;
@@ -228,15 +232,27 @@ PartValue slice_cache_value(bool hit, CacheValue v, const SliceSpec& spec) {
   bool over;
   const size_t h = parse_tag_block(v.data->data(), n, &hs, &nt, &over);
   size_t head_len = 0;
-  if (spec.kind >= kSliceWhole || !slice_find_head_end(b + h, n - h, &head_len)) {
+  uint32_t kind = spec.kind;
+  const bool conditional = cond.kind != kCondNone;
+  bool not_modified = false;
+  bool whole = (kind >= kSliceWhole && !conditional) || !slice_find_head_end(b + h, n - h, &head_len);
+  if (!whole && conditional) {
+    const SliceCond c{cond.kind, cond.ncand, 0, (uint32_t)cond.records.size()};
+    const bool matched = cond_matches(b, (uint32_t)h, (uint32_t)(h + head_len), c,
+                                      reinterpret_cast<const uint8_t*>(cond.records.data()));
+    not_modified = cond_outcome(cond.kind, matched, &kind);
+    whole = kind >= kSliceWhole;
+  }
+  if (whole) {
     p.status = kSliceWholeObj;
     p.window = std::move(v.data);
     return p;
   }
   p.body_len = n - h - head_len;
   uint64_t len = 0;
-  p.status = resolve_window(spec.kind, spec.a, spec.b, p.body_len, &p.first, &len) ? kSliceOk
-                                                                                   : kSliceUnsat;
+  p.status = resolve_window(kind, spec.a, spec.b, p.body_len, &p.first, &len) ? kSliceOk
+                                                                              : kSliceUnsat;
+  if (not_modified) p.status = kSliceNotModified;
   p.head = v.data->sub(h, head_len);
   p.window = v.data->sub(h + head_len + p.first, len);
   return p;
@@ -253,6 +269,23 @@ void TieredBackend::get_part(const std::string& key, const Digest& d, const Slic
       return;
     }
     l2->get_part(key, d, spec, ex, [this, done = std::move(done)](PartValue p) {
+      (p.status != kSliceMiss ? l2_hits_ : misses_).fetch_add(1, std::memory_order_relaxed);
+      done(std::move(p));
+    });
+  });
+}
+
+void TieredBackend::get_part_if(const std::string& key, const Digest& d, const SliceSpec& spec,
+                                const PartCond& cond, Executor* ex, PartCallback done) {
+  CacheBackend* l2 = l2_.get();
+  l1_->get(key, d, ex, [this, key, d, spec, cond, ex, l2, done = std::move(done)](
+                           bool hit, CacheValue v) mutable {
+    if (hit) {
+      l1_hits_.fetch_add(1, std::memory_order_relaxed);
+      done(slice_cache_value_if(true, std::move(v), spec, cond));
+      return;
+    }
+    l2->get_part_if(key, d, spec, cond, ex, [this, done = std::move(done)](PartValue p) {
       (p.status != kSliceMiss ? l2_hits_ : misses_).fetch_add(1, std::memory_order_relaxed);
       done(std::move(p));
     });

@@ -40,6 +40,7 @@
 #include "net.h"
 #include "object_cache.h"
 #include "presence_filter.h"
+#include "conditional.h"
 #include "slice.h"
 #include "stream_buf.h"
 
@@ -66,8 +67,9 @@ struct CacheValue {
 using GetCallback = std::function<void(bool hit, CacheValue v)>;
 // The answer of a sliced GET (slice.h): part of one stored HTTP response.
 struct PartValue {
-  uint32_t status = kSliceMiss;  // kSliceMiss / kSliceOk / kSliceUnsat / kSliceWholeObj
-  Bytes head;    // kSliceOk, kSliceUnsat: the payload from "HTTP/" through the blank line
+  // kSliceMiss / kSliceOk / kSliceUnsat / kSliceWholeObj / kSliceNotModified (get_part_if)
+  uint32_t status = kSliceMiss;
+  Bytes head;    // all but miss and whole: the payload from "HTTP/" through the blank line
   Bytes window;  // the window's bytes; kSliceWholeObj: the whole value, as get() returns it
   uint64_t body_len = 0, first = 0;
   uint32_t flags = 0;
@@ -77,6 +79,13 @@ using PartCallback = std::function<void(PartValue v)>;
 // A whole value, as get() answered it, sliced on the host: what every tier without a sliced
 // GET of its own answers, and what a tier that cuts on the GPU must equal.
 PartValue slice_cache_value(bool hit, CacheValue v, const SliceSpec& spec);
+// The condition of a conditional sliced GET (conditional.h): a kind and its candidate records,
+// what parse_if_none_match / parse_if_modified_since / parse_if_range give.
+using PartCond = CondRequest;
+// slice_cache_value under a condition, decided on the host with conditional.h's functions: a
+// matched none_match / modified_since answers the head alone under kSliceNotModified, an
+// unmatched if_range_* the whole value.
+PartValue slice_cache_value_if(bool hit, CacheValue v, const SliceSpec& spec, const PartCond& cond);
 using DelCallback = std::function<void(bool found)>;
 // Prefix purge: objects removed, or -1 if the tier cannot scan its keys.
 using PurgeCallback = std::function<void(int64_t removed)>;
@@ -118,6 +127,16 @@ class CacheBackend {
                         Executor* ex, PartCallback done) {
     get(key, d, ex, [spec, done = std::move(done)](bool hit, CacheValue v) {
       done(slice_cache_value(hit, std::move(v), spec));
+    });
+  }
+  // Conditional sliced GET: get_part with the client's validators (`cond`), compared with the
+  // stored ETag / Last-Modified where the object lies, so one trip answers "not modified" (the
+  // head alone, kSliceNotModified), the window, or the whole object. The default gets the whole
+  // value and decides and cuts it on the host; HbmBackend decides on the GPU.
+  virtual void get_part_if(const std::string& key, const Digest& d, const SliceSpec& spec,
+                           const PartCond& cond, Executor* ex, PartCallback done) {
+    get(key, d, ex, [spec, cond, done = std::move(done)](bool hit, CacheValue v) {
+      done(slice_cache_value_if(hit, std::move(v), spec, cond));
     });
   }
   virtual void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
@@ -398,6 +417,10 @@ class HbmBackend : public CacheBackend {
   // window are slices of that arena. A shard out of service is a miss.
   void get_part(const std::string& key, const Digest& d, const SliceSpec& spec, Executor* ex,
                 PartCallback done) override;
+  // The same request carrying its condition: the flight's launch then passes one SliceCond per
+  // row and k_slice_plan decides each row on the GPU (counted in hbm_cond_slices).
+  void get_part_if(const std::string& key, const Digest& d, const SliceSpec& spec,
+                   const PartCond& cond, Executor* ex, PartCallback done) override;
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
@@ -477,6 +500,7 @@ class HbmBackend : public CacheBackend {
     DelCallback dcb;
     TouchCallback tcb;
     SliceSpec spec{};  // Slice: the window asked for
+    std::shared_ptr<const PartCond> cond;  // Slice: its condition (null: none)
     PartCallback pcb;
     // control requests (is_ctl): runs on the batcher thread once the request's flight has
     // finished on the GPU (ok) or was failed
@@ -562,6 +586,9 @@ class HbmBackend : public CacheBackend {
   void list_step(std::shared_ptr<ListWalk> w);
   std::atomic<uint64_t> lists_{0};
   std::atomic<uint64_t> slices_{0};  // get_part calls taken
+  std::atomic<uint64_t> cond_slices_{0};  // get_part_if calls that carried a condition
+  void part_request(const std::string& key, const Digest& d, const SliceSpec& spec,
+                    std::shared_ptr<const PartCond> cond, Executor* ex, PartCallback done);
   // ---- hot-object spreading (hot_refresh_locked documents the protocol)
   std::unique_ptr<HostRouter> router_;  // ketama owners + the published hot table
   bool hot_on_ = false;
@@ -609,6 +636,9 @@ class TieredBackend : public CacheBackend {
   // fills L1 (not even a kSliceWholeObj one: a promotion belongs to get()).
   void get_part(const std::string& key, const Digest& d, const SliceSpec& spec, Executor* ex,
                 PartCallback done) override;
+  // The same under a condition: an L1 hit is decided on the host, an L1 miss asks L2 with it.
+  void get_part_if(const std::string& key, const Digest& d, const SliceSpec& spec,
+                   const PartCond& cond, Executor* ex, PartCallback done) override;
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;

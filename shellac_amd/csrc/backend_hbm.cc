@@ -271,6 +271,19 @@ void HbmBackend::get(const std::string& key, const Digest& d, Executor* ex, GetC
 
 void HbmBackend::get_part(const std::string& key, const Digest& d, const SliceSpec& spec,
                           Executor* ex, PartCallback done) {
+  part_request(key, d, spec, nullptr, ex, std::move(done));
+}
+
+void HbmBackend::get_part_if(const std::string& key, const Digest& d, const SliceSpec& spec,
+                             const PartCond& cond, Executor* ex, PartCallback done) {
+  if (cond.kind == kCondNone) return part_request(key, d, spec, nullptr, ex, std::move(done));
+  cond_slices_.fetch_add(1, std::memory_order_relaxed);
+  part_request(key, d, spec, std::make_shared<const PartCond>(cond), ex, std::move(done));
+}
+
+void HbmBackend::part_request(const std::string& key, const Digest& d, const SliceSpec& spec,
+                              std::shared_ptr<const PartCond> cond, Executor* ex,
+                              PartCallback done) {
   slices_.fetch_add(1, std::memory_order_relaxed);
   const int k = route_get(d);
   if (k < 0) {  // every shard ejected
@@ -292,6 +305,7 @@ void HbmBackend::get_part(const std::string& key, const Digest& d, const SliceSp
   r.d = d;
   r.key = key;
   r.spec = spec;
+  r.cond = std::move(cond);
   r.ex = ex;
   r.pcb = std::move(done);
   enqueue(k, std::move(r));  // (the batcher only: the edge server does not cut)
@@ -685,6 +699,7 @@ void HbmBackend::stats(StatList* out) {
   out->emplace_back("hbm_tag_purges", by_tag);
   out->emplace_back("hbm_lists", lists_.load());
   out->emplace_back("hbm_slices", slices_.load());
+  out->emplace_back("hbm_cond_slices", cond_slices_.load());
   out->emplace_back("hbm_tag_purged_objects", sum(&Dev::tag_purged_objects));
   out->emplace_back("hbm_tag_softened_objects", sum(&Dev::tag_softened_objects));
   out->emplace_back("hbm_glob_purges", by_glob);

@@ -75,7 +75,17 @@ PYBIND11_MODULE(_shellac_core, m) {
   m.attr("SLICE_OK") = (int)kSliceOk;
   m.attr("SLICE_UNSAT") = (int)kSliceUnsat;
   m.attr("SLICE_WHOLE_OBJ") = (int)kSliceWholeObj;
+  m.attr("SLICE_NOT_MODIFIED") = (int)kSliceNotModified;
   m.attr("SLICE_HEAD_MAX") = (int)kSliceHeadMax;
+  m.attr("SLICE_COND_BYTES") = (int)sizeof(SliceCond);
+  m.attr("COND_NONE") = (int)kCondNone;
+  m.attr("COND_NONE_MATCH") = (int)kCondNoneMatch;
+  m.attr("COND_MODIFIED_SINCE") = (int)kCondModifiedSince;
+  m.attr("COND_IF_RANGE_ETAG") = (int)kCondIfRangeEtag;
+  m.attr("COND_IF_RANGE_DATE") = (int)kCondIfRangeDate;
+  m.attr("COND_LINE_MAX") = (int)kCondLineMax;
+  m.attr("COND_VALUE_MAX") = (int)kCondValueMax;
+  m.attr("COND_MAX_CANDIDATES") = (int)kCondMaxCandidates;
   m.attr("SLICE_ROW_BYTES") = (int)sizeof(SliceRow);
   m.attr("SLICE_SPEC_BYTES") = (int)sizeof(SliceSpec);
 
@@ -146,6 +156,33 @@ PYBIND11_MODULE(_shellac_core, m) {
       return py::none();
     return py::make_tuple(ho, bo);
   }, "(head_off, body_off) of a sliceable keyed value, else None (slice.h)");
+  m.def("cond_matches", [](py::bytes value, uint32_t kind, uint32_t ncand, py::bytes records) {
+    const std::string v = value, r = records;
+    uint32_t ho = 0, bo = 0;
+    if (!slice_layout(reinterpret_cast<const uint8_t*>(v.data()), v.size(), &ho, &bo)) return false;
+    const SliceCond c{kind, ncand, 0, (uint32_t)r.size()};
+    return cond_matches(reinterpret_cast<const uint8_t*>(v.data()), ho, bo, c,
+                        reinterpret_cast<const uint8_t*>(r.data()));
+  }, "whether a condition (kind, ncand, candidate records) holds for a keyed value (conditional.h)");
+  const auto cond_tuple = [](bool ok, const CondRequest& c) -> py::object {
+    if (!ok) return py::none();
+    return py::make_tuple(c.kind, c.ncand, py::bytes(c.records));
+  };
+  m.def("parse_if_none_match", [cond_tuple](py::bytes value) {
+    const std::string v = value;
+    CondRequest c;
+    return cond_tuple(parse_if_none_match(v.data(), v.size(), &c), c);
+  }, "(kind, ncand, records) of an If-None-Match value, None: the header is ignored");
+  m.def("parse_if_range", [cond_tuple](py::bytes value) {
+    const std::string v = value;
+    CondRequest c;
+    return cond_tuple(parse_if_range(v.data(), v.size(), &c), c);
+  }, "(kind, 1, record) of an If-Range value, None: it can never match (ask for the whole object)");
+  m.def("parse_if_modified_since", [cond_tuple](py::bytes value) {
+    const std::string v = value;
+    CondRequest c;
+    return cond_tuple(parse_if_modified_since(v.data(), v.size(), &c), c);
+  }, "(kind, 1, record) of an If-Modified-Since value, None: the header is ignored");
   m.def("bucket_pair", [](uint64_t lo, uint64_t hi, uint64_t nbuckets) {
     const Digest d{lo, hi};
     return std::vector<uint64_t>{bucket1(d, nbuckets - 1), bucket2(d, nbuckets - 1)};
@@ -358,15 +395,17 @@ PYBIND11_MODULE(_shellac_core, m) {
       .def("get_keyed_slices", [](HbmCache& c, uintptr_t keys, uintptr_t key_bytes,
                                   uintptr_t key_offs, uintptr_t spec, int64_t n, uintptr_t rows,
                                   uintptr_t out, uint64_t out_cap, uintptr_t res, uint32_t now,
-                                  uintptr_t s, uint64_t reserve) {
+                                  uintptr_t s, uint64_t reserve, uintptr_t cond,
+                                  uintptr_t cond_bytes) {
         py::gil_scoped_release nogil;
         c.get_keyed_slices(P<const Digest>(keys), P<const uint8_t>(key_bytes),
                            P<const int64_t>(key_offs), P<const SliceSpec>(spec), n,
                            P<SliceRow>(rows), P<uint8_t>(out), out_cap, P<uint64_t>(res), now, S(s),
-                           reserve);
+                           reserve, P<const SliceCond>(cond), P<const uint8_t>(cond_bytes));
       }, py::arg("keys"), py::arg("key_bytes"), py::arg("key_offs"), py::arg("spec"), py::arg("n"),
          py::arg("rows"), py::arg("out"), py::arg("out_cap"), py::arg("res"), py::arg("now"),
-         py::arg("stream"), py::arg("reserve") = 0)
+         py::arg("stream"), py::arg("reserve") = 0, py::arg("cond") = 0,
+         py::arg("cond_bytes") = 0)
       // flags / key_bytes + key_offs: 0 = none; asynchronous on the stream
       .def("touch", [](HbmCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
@@ -634,15 +673,15 @@ PYBIND11_MODULE(_shellac_core, m) {
       .def("get_keyed_slices", [](HostCache& c, uintptr_t keys, uintptr_t key_bytes,
                                   uintptr_t key_offs, uintptr_t spec, int64_t n, uintptr_t rows,
                                   uintptr_t out, uint64_t out_cap, uintptr_t res, uint32_t now,
-                                  uint64_t reserve) {
+                                  uint64_t reserve, uintptr_t cond, uintptr_t cond_bytes) {
         py::gil_scoped_release nogil;
         c.get_keyed_slices(P<const Digest>(keys), P<const uint8_t>(key_bytes),
                            P<const int64_t>(key_offs), P<const SliceSpec>(spec), n,
                            P<SliceRow>(rows), P<uint8_t>(out), out_cap, P<uint64_t>(res), now,
-                           reserve);
+                           reserve, P<const SliceCond>(cond), P<const uint8_t>(cond_bytes));
       }, py::arg("keys"), py::arg("key_bytes"), py::arg("key_offs"), py::arg("spec"), py::arg("n"),
          py::arg("rows"), py::arg("out"), py::arg("out_cap"), py::arg("res"), py::arg("now"),
-         py::arg("reserve") = 0)
+         py::arg("reserve") = 0, py::arg("cond") = 0, py::arg("cond_bytes") = 0)
       .def("touch", [](HostCache& c, uintptr_t keys, uintptr_t expire, uintptr_t flags,
                        uintptr_t key_bytes, uintptr_t key_offs, int64_t n, uintptr_t hit,
                        uint32_t now) {

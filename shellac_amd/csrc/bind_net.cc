@@ -456,12 +456,26 @@ void bind_net(py::module_& m) {
       // sliced GETs (CacheBackend::get_part), every one issued at once, then waited for.
       // specs: (kind, a, b) tuples with kind a SLICE_* number; one dict per key: {status (a
       // SLICE_* status number), head, window, body_len, first, flags, ttl}. `digest_of`: look
-      // every key up under that key's digest (a forged collision)
+      // every key up under that key's digest (a forged collision). `conds`: None, or one
+      // entry per key, None or (kind, ncand, records) with kind a COND_* number and records the
+      // [u8 len | bytes] candidates: the key is asked with CacheBackend::get_part_if
       .def("get_parts", [](BackendHandle& h, std::vector<std::string> keys,
                            std::vector<std::tuple<uint32_t, uint64_t, uint64_t>> specs,
-                           py::object digest_of) {
+                           py::object digest_of, py::object conds) {
         const size_t n = keys.size();
         if (specs.size() != n) throw py::value_error("one window spec per key");
+        std::vector<PartCond> pc(n);
+        if (!conds.is_none()) {
+          const py::list cl = conds.cast<py::list>();
+          if (cl.size() != n) throw py::value_error("one condition (or None) per key");
+          for (size_t i = 0; i < n; ++i) {
+            if (cl[i].is_none()) continue;
+            const py::tuple t = cl[i].cast<py::tuple>();
+            pc[i].kind = t[0].cast<uint32_t>();
+            pc[i].ncand = t[1].cast<uint32_t>();
+            pc[i].records = t[2].cast<std::string>();
+          }
+        }
         const bool forged = !digest_of.is_none();
         const std::string o = forged ? digest_of.cast<std::string>() : std::string();
         std::vector<PartValue> vals(n);
@@ -477,11 +491,15 @@ void bind_net(py::module_& m) {
             sp.kind = std::get<0>(specs[i]);
             sp.a = std::get<1>(specs[i]);
             sp.b = std::get<2>(specs[i]);
-            h.be->get_part(keys[i], d, sp, &g_inline, [&, i](PartValue v) {
+            const auto done = [&, i](PartValue v) {
               std::lock_guard<std::mutex> lk(mu);
               vals[i] = std::move(v);
               if (--left == 0) cv.notify_all();
-            });
+            };
+            if (pc[i].kind != kCondNone)
+              h.be->get_part_if(keys[i], d, sp, pc[i], &g_inline, done);
+            else
+              h.be->get_part(keys[i], d, sp, &g_inline, done);
           }
           std::unique_lock<std::mutex> lk(mu);
           cv.wait(lk, [&] { return left == 0; });
@@ -499,7 +517,8 @@ void bind_net(py::module_& m) {
           out.append(d);
         }
         return out;
-      }, py::arg("keys"), py::arg("specs"), py::arg("digest_of") = py::none())
+      }, py::arg("keys"), py::arg("specs"), py::arg("digest_of") = py::none(),
+         py::arg("conds") = py::none())
       .def("flush", [](BackendHandle& h) { h.be->flush(); })
       .def("stats", [](BackendHandle& h) {
         StatList st;
@@ -632,8 +651,9 @@ void bind_net(py::module_& m) {
                        std::vector<int> cpus, int spin_us, int gzip_gpu, int gzip_batch_us,
                        uint64_t max_inflate_bytes, int gzip_workers, const std::string& purge,
                        uint32_t grace, const std::string& tag_header,
-                       const std::string& inspect, bool partial_hits) {
+                       const std::string& inspect, bool partial_hits, bool conditional_hits) {
              ProxyConfig c;
+             c.conditional_hits = conditional_hits;
              c.grace = grace;
              c.tag_header = tag_header;
              c.inspect = inspect;
@@ -692,7 +712,8 @@ void bind_net(py::module_& m) {
            py::arg("gzip_gpu") = -1, py::arg("gzip_batch_us") = 200,
            py::arg("max_inflate_bytes") = 64ull << 20, py::arg("gzip_workers") = 2,
            py::arg("purge") = "off", py::arg("grace") = 0, py::arg("tag_header") = "",
-           py::arg("inspect") = "off", py::arg("partial_hits") = false)
+           py::arg("inspect") = "off", py::arg("partial_hits") = false,
+           py::arg("conditional_hits") = false)
       .def("start", &Proxy::start)
       .def("wait", &Proxy::wait, py::call_guard<py::gil_scoped_release>())
       .def("stop", &Proxy::stop)

@@ -238,6 +238,10 @@ struct Flight {
   Mapped slice_buf;
   size_t slice_offs_off = 0, slice_spec_off = 0, slice_rows_off = 0, slice_res_off = 0,
          slice_kb_off = 0;
+  // where some slice of the flight carries a condition: [SliceCond per row | candidate bytes]
+  // behind the key bytes
+  bool slice_conds = false;
+  size_t slice_cond_off = 0, slice_cb_off = 0;
   std::shared_ptr<ArenaPool::Arena> slice_arena;
   void release_mapped() {
     for (Mapped* m : {&keys, &offs, &set_keys, &set_vals, &set_voff, &set_meta, &del_keys,

@@ -286,12 +286,31 @@ void HbmBackend::Dev::launch_slices(Flight& f) {
   f.slice_rows_off = f.slice_spec_off + align_up(n * sizeof(SliceSpec), 16);
   f.slice_res_off = f.slice_rows_off + n * sizeof(SliceRow);
   f.slice_kb_off = f.slice_res_off + 16;
-  f.slice_buf.ensure(f.slice_kb_off + p.kbytes.size() + 16);
+  // conditions travel only where some row has one; the launch is the plain one otherwise
+  size_t cond_bytes = 0;
+  f.slice_conds = false;
+  for (uint32_t i : f.slices)
+    if (f.reqs[i].cond) {
+      f.slice_conds = true;
+      cond_bytes += f.reqs[i].cond->records.size();
+    }
+  f.slice_cond_off = align_up(f.slice_kb_off + p.kbytes.size(), 16);
+  f.slice_cb_off = f.slice_cond_off + (f.slice_conds ? n * sizeof(SliceCond) : 0);
+  f.slice_buf.ensure(f.slice_cb_off + cond_bytes + 16);
   uint8_t* const hb = f.slice_buf.host<uint8_t>();
+  size_t cb_at = 0;
   for (size_t j = 0; j < n; ++j) {
     const Req& r = f.reqs[f.slices[j]];
     reinterpret_cast<Digest*>(hb)[j] = r.d;
     reinterpret_cast<SliceSpec*>(hb + f.slice_spec_off)[j] = r.spec;
+    if (!f.slice_conds) continue;
+    SliceCond c{};
+    if (r.cond) {
+      c = SliceCond{r.cond->kind, r.cond->ncand, (uint32_t)cb_at, (uint32_t)r.cond->records.size()};
+      std::memcpy(hb + f.slice_cb_off + cb_at, r.cond->records.data(), r.cond->records.size());
+      cb_at += r.cond->records.size();
+    }
+    reinterpret_cast<SliceCond*>(hb + f.slice_cond_off)[j] = c;
   }
   std::memcpy(hb + f.slice_offs_off, p.offs.data(), (n + 1) * 8);
   std::memcpy(hb + f.slice_kb_off, p.kbytes.data(), p.kbytes.size());
@@ -309,7 +328,10 @@ void HbmBackend::Dev::run_slices(Flight& f) {
                           (int64_t)f.slices.size(),
                           reinterpret_cast<SliceRow*>(db + f.slice_rows_off), f.slice_arena->d,
                           f.slice_arena->cap, reinterpret_cast<uint64_t*>(db + f.slice_res_off),
-                          f.tnow, stream);
+                          f.tnow, stream, 0,
+                          f.slice_conds ? reinterpret_cast<const SliceCond*>(db + f.slice_cond_off)
+                                        : nullptr,
+                          f.slice_conds ? db + f.slice_cb_off : nullptr);
 }
 
 // SET: [klen | key | payload] values packed into mapped staging the SET kernels read

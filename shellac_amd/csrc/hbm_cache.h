@@ -21,6 +21,7 @@
 
 #include "keyed.h"
 #include "layout.h"
+#include "conditional.h"
 #include "slice.h"
 
 namespace shellac {
@@ -338,10 +339,16 @@ class HbmCache {
   // before waits, on the device, for that one's event, so calls on several streams are safe
   // and run one after the other. See k_slice_plan for what holds beside a SET chain on
   // another stream.
+  // `cond` (nullable; device or mapped pinned memory, as `cond_bytes`): one SliceCond per row
+  // (conditional.h), decided on the GPU against the stored head by k_slice_plan: a matched
+  // none_match / modified_since row returns the head alone under kSliceNotModified, an
+  // unmatched if_range_* row the whole value. Without it the call launches
+  // the kernel instance without condition arguments, exactly what it launched before.
   void get_keyed_slices(const Digest* keys, const uint8_t* key_bytes, const int64_t* key_offs,
                         const SliceSpec* spec, int64_t n, SliceRow* rows, uint8_t* out,
                         uint64_t out_cap, uint64_t* res, uint32_t now, hipStream_t s,
-                        uint64_t reserve = 0);
+                        uint64_t reserve = 0, const SliceCond* cond = nullptr,
+                        const uint8_t* cond_bytes = nullptr);
   // TOUCH a batch: row i's live entry gets the absolute expiry expire[i] (0 = never) and,
   // with `flags` (nullable), the flags flags[i] — in place, in the index entry and in the
   // record's ItemHeader (the CLOCK hand and the backends read the header); no value byte

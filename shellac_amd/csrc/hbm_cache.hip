@@ -4047,8 +4047,149 @@ __global__ __launch_bounds__(kBlock) void k_records_to_set(
 // between the plan and the copy comes back torn, as after lookup + gather; such a row's
 // fields still describe the object that was planned. It writes the index only by the atomicOr
 // of kRefBit (a GET's), and the log not at all.
+//
+// Conditions (conditional.h). The kernel is a template over a pack of trailing arguments:
+// k_slice_plan<> has none and is the kernel as it was before conditions, argument for argument
+// and instruction for instruction; k_slice_plan<const SliceCond*, const uint8_t*> reads one
+// SliceCond per row, looks for the head of every row that carries one, whatever its window
+// kind, and lets slice_cond_matches decide it between steps 6 and 7. The evaluation keeps the
+// contract above: it reads aligned granules below body_off, bytes inside [head_off, body_off),
+// and candidate bytes inside the row's cond_bytes[off, off + len) only; every loop is bounded
+// by offsets computed before it, never by a byte read in it, so a record that is overwritten
+// meanwhile cannot lead it out. A conditional row's get_bytes is the final row's payload.
 constexpr int kSliceWaves = kBlock / 64;
 
+// The bytes 'A'..'Z' of a word in lower case, every other byte as it is.
+__device__ __forceinline__ uint32_t cond_lower4(uint32_t x) {
+  const uint32_t h = x & 0x7f7f7f7fu;
+  const uint32_t ge_a = h + 0x3f3f3f3fu;  // bit 7 of a byte: its low 7 bits >= 'A'
+  const uint32_t gt_z = h + 0x25252525u;  //                  its low 7 bits >  'Z'
+  return x | ((ge_a & ~gt_z & ~x & 0x80808080u) >> 2);
+}
+
+// Whether condition c holds for the sliceable value `val` (16-B aligned, the head at
+// [head_off, body_off)), decided by one wave; the result and every branch are wave-uniform.
+//   1. The first line of the field's name: per pass each lane loads one 16-B granule (1 KiB
+//      per wave), takes the granule before's last dword and the granule after's four from its
+//      neighbour lanes (lane 0 and lane 63 load theirs), lowers the letters, and tests CR LF
+//      and the name with its colon at its 16 start positions; a ballot finds the lowest match.
+//   2. The value's extent: the first CR LF within kCondLineMax bytes behind the colon, then the
+//      first and the last byte that is no blank, 64 bytes per step.
+//   3. cond_stored_validator's shape test, then the candidates one after the other, each
+//      compared 64 bytes per step.
+__device__ __forceinline__ bool slice_cond_matches(const uint8_t* __restrict__ val,
+                                                   uint32_t head_off, uint32_t body_off,
+                                                   const SliceCond c,
+                                                   const uint8_t* __restrict__ cond_bytes,
+                                                   int lane) {
+  if (!cond_kind_valid(c.kind) || (c.ncand && !cond_bytes)) return false;
+  const uint8_t* const cb = cond_bytes ? cond_bytes + c.off : nullptr;
+  if (!cond_records_ok(c.ncand, cb, c.len)) return false;
+  if (c.ncand == 0) return c.kind == kCondNoneMatch;  // "*"
+  const bool etag = cond_kind_etag(c.kind);
+  const uint32_t nl = cond_name_len(etag);
+  const uint32_t e = body_off - 4;  // the head's CR LF CR LF
+  const uint4* const vg = reinterpret_cast<const uint4*>(val);
+  const uint32_t ngr = (body_off + 15) >> 4;  // the granules that hold the head
+  // a line start at value offset p needs head_off + 2 <= p and p + nl <= e
+  uint32_t start = 0;
+  for (uint32_t g0 = (head_off + 2) >> 4; g0 * 16 + nl <= e; g0 += 64) {
+    const uint32_t g = g0 + lane;
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (g < ngr) w = vg[g];
+    uint32_t pw = __shfl_up(w.w, 1);
+    if (lane == 0) pw = g > 0 ? vg[g - 1].w : 0u;
+    uint4 nx = make_uint4(__shfl_down(w.x, 1), __shfl_down(w.y, 1), __shfl_down(w.z, 1),
+                          __shfl_down(w.w, 1));
+    if (lane == 63) nx = g + 1 < ngr ? vg[g + 1] : make_uint4(0u, 0u, 0u, 0u);
+    // ww[1..4] is the lane's granule: position j's byte k is byte 4 + j + k of ww
+    const uint32_t ww[9] = {cond_lower4(pw),   cond_lower4(w.x),  cond_lower4(w.y),
+                            cond_lower4(w.z),  cond_lower4(w.w),  cond_lower4(nx.x),
+                            cond_lower4(nx.y), cond_lower4(nx.z), cond_lower4(nx.w)};
+    uint32_t hit = 16;
+#pragma unroll
+    for (int j = 15; j >= 0; --j) {
+      const int q = (4 + j) >> 2, sh = 8 * (j & 3);
+      const int qc = (2 + j) >> 2, shc = 8 * ((2 + j) & 3);
+      const uint32_t crlf = __funnelshift_r(ww[qc], ww[qc + 1], shc) & 0xffffu;
+      const uint32_t n0 = __funnelshift_r(ww[q], ww[q + 1], sh);
+      const uint32_t n1 = __funnelshift_r(ww[q + 1], ww[q + 2], sh);
+      const uint32_t n2 = __funnelshift_r(ww[q + 2], ww[q + 3], sh);
+      const uint32_t n3 = __funnelshift_r(ww[q + 3], ww[q + 4], sh);
+      const bool name = etag ? (n0 == 0x67617465u && (n1 & 0xffu) == 0x3au)  // "etag" ":"
+                             : (n0 == 0x7473616cu && n1 == 0x646f6d2du &&    // "last" "-mod"
+                                n2 == 0x65696669u && (n3 & 0xffffu) == 0x3a64u);  // "ifie" "d:"
+      const uint32_t p = g * 16 + j;
+      if (crlf == 0x0a0du && name && p >= head_off + 2 && p + nl <= e) hit = j;
+    }
+    const unsigned long long m = __ballot(hit < 16);
+    if (m) {
+      const int src = __ffsll((long long)m) - 1;
+      start = (g0 + (uint32_t)src) * 16 + (uint32_t)__shfl((int)hit, src);
+      break;
+    }
+  }
+  if (start == 0) return false;  // no such field
+  // the raw value [c0, q): q is the first CR LF at or behind the colon (one stands at e)
+  const uint32_t c0 = start + nl;
+  const uint32_t qlim = min(c0 + kCondLineMax, e);
+  uint32_t q = ~0u;
+  for (uint32_t b0 = c0; b0 <= qlim; b0 += 64) {
+    const uint32_t x = b0 + lane;
+    const bool is = x <= qlim && val[x] == '\r' && val[x + 1] == '\n';
+    const unsigned long long m = __ballot(is);
+    if (m) {
+      q = b0 + (uint32_t)__ffsll((long long)m) - 1;
+      break;
+    }
+  }
+  if (q == ~0u) return false;  // longer than kCondLineMax: absent
+  uint32_t vs = q, vend = q;   // the trimmed value [vs, vend)
+  for (uint32_t b0 = c0; b0 < q; b0 += 64) {
+    const uint32_t x = b0 + lane;
+    const unsigned long long m = __ballot(x < q && !cond_blank(val[x]));
+    if (m) {
+      vs = b0 + (uint32_t)__ffsll((long long)m) - 1;
+      break;
+    }
+  }
+  for (uint32_t b0 = q; b0 > vs; b0 -= 64) {  // lane l looks at byte b0 - 1 - l
+    const bool in = (uint32_t)lane < b0 - vs;
+    const unsigned long long m = __ballot(in && !cond_blank(val[in ? b0 - 1 - lane : vs]));
+    if (m) {
+      vend = b0 - (uint32_t)__ffsll((long long)m) + 1;
+      break;
+    }
+    if (b0 - vs <= 64) return false;  // (val[vs] was no blank: a record overwritten meanwhile)
+  }
+  bool weak;
+  uint32_t o, len;
+  if (!cond_stored_validator(etag, val + vs, vend - vs, &weak, &o, &len)) return false;
+  if (weak && c.kind == kCondIfRangeEtag) return false;
+  const uint8_t* const sv = val + vs + o;
+  uint32_t p = 0;
+  for (uint32_t k = 0; k < c.ncand; ++k) {
+    const uint32_t cl = cb[p];
+    if (cl == len) {
+      bool eq = true;
+      for (uint32_t t = lane; t < len; t += 64) eq = eq && sv[t] == cb[p + 1 + t];
+      if (__ballot(!eq) == 0) return true;
+    }
+    p += 1 + cl;
+  }
+  return false;
+}
+
+// The two trailing arguments of the kernel's conditional instance.
+__device__ __forceinline__ const SliceCond* slice_cond_rows(const SliceCond* c, const uint8_t*) {
+  return c;
+}
+__device__ __forceinline__ const uint8_t* slice_cond_bytes(const SliceCond*, const uint8_t* b) {
+  return b;
+}
+
+// Cond...: nothing, or (const SliceCond* cond, const uint8_t* cond_bytes).
+template <class... Cond>
 __global__ __launch_bounds__(kBlock) void k_slice_plan(
     const Digest* __restrict__ keys, const uint8_t* __restrict__ kbytes,
     const int64_t* __restrict__ koffs, const SliceSpec* __restrict__ spec, int64_t n,
@@ -4056,7 +4197,8 @@ __global__ __launch_bounds__(kBlock) void k_slice_plan(
     const uint64_t* __restrict__ head_ptr, const uint64_t* __restrict__ claim_ptr,
     uint64_t reserve, uint64_t cap, uint32_t max_item, uint32_t now, SliceRow* __restrict__ rows,
     uint64_t* __restrict__ seg_src, uint64_t* __restrict__ seg_len,
-    CacheCounters* __restrict__ ctr) {
+    CacheCounters* __restrict__ ctr, Cond... cond_args) {
+  constexpr bool kCond = sizeof...(Cond) != 0;
   const int lane = threadIdx.x & 63;
   const int l16 = lane & 15;
   const int gbase = lane & 48;
@@ -4128,7 +4270,13 @@ __global__ __launch_bounds__(kBlock) void k_slice_plan(
       const SliceSpec sp = spec[i];
       uint32_t head_off = (uint32_t)kKeyedPrefix + klen, body_off = 0;
       bool sliceable = false;
-      if (sp.kind < kSliceWhole) {
+      SliceCond ck = SliceCond{};
+      bool find_head = sp.kind < kSliceWhole;
+      if constexpr (kCond) {
+        ck = slice_cond_rows(cond_args...)[i];
+        find_head = find_head || ck.kind != kCondNone;  // (a condition needs the head)
+      }
+      if (find_head) {
         const uint32_t o = head_off;
         if (o + 2 <= vlen && val[o] == kTagMarker) {
           const uint32_t nt = val[o + 1];
@@ -4170,8 +4318,15 @@ __global__ __launch_bounds__(kBlock) void k_slice_plan(
           }
         }
       }
-      slice_make_row(&r, sp.kind, sp.a, sp.b, vlen, hb.y, (uint32_t)(ve >> 32), sliceable,
-                     head_off, body_off);
+      if constexpr (kCond) {
+        const bool matched = sliceable && ck.kind != kCondNone &&
+                             slice_cond_matches(val, head_off, body_off, ck, slice_cond_bytes(cond_args...), lane);
+        slice_make_row_if(&r, sp.kind, sp.a, sp.b, vlen, hb.y, (uint32_t)(ve >> 32), sliceable,
+                          head_off, body_off, ck.kind, matched);
+      } else {
+        slice_make_row(&r, sp.kind, sp.a, sp.b, vlen, hb.y, (uint32_t)(ve >> 32), sliceable,
+                       head_off, body_off);
+      }
       src0 = recoff + kItemHeaderBytes;
       src1 = src0 + ((r.body_off + r.win_first) & ~15u);
     } while (false);
@@ -5428,7 +5583,8 @@ void HbmCache::list_keyed(uint32_t mode, const uint8_t* image, uint32_t plen, bo
 void HbmCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
                                 const int64_t* key_offs, const SliceSpec* spec, int64_t n,
                                 SliceRow* rows, uint8_t* out, uint64_t out_cap, uint64_t* res,
-                                uint32_t now, hipStream_t s, uint64_t reserve) {
+                                uint32_t now, hipStream_t s, uint64_t reserve,
+                                const SliceCond* cond, const uint8_t* cond_bytes) {
   TraceRange tr("hbm.slices");
   SH_CHECK(n >= 0 && n <= kSmallGetMax, "sliced GET batch too large");
   SH_CHECK(res, "sliced GET needs result words");
@@ -5458,10 +5614,17 @@ void HbmCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
   if (n > 0) {
     // (the scan reads 2n + 1 lengths: the last one is its zero)
     HIP_OK(hipMemsetAsync(seg_len + 2 * n, 0, sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_slice_plan, dim3(grid_for(n, kSliceWaves, kMaxGrid)), dim3(kBlock), 0, s,
-                       keys, key_bytes, key_offs, spec, n, index_, cfg_.nbuckets - 1, log_,
-                       cur_head(), claim_ptr(), reserve, cfg_.log_bytes, cfg_.max_item, now, rows,
-                       seg_src, seg_len, ctr_);
+    if (cond)
+      hipLaunchKernelGGL((k_slice_plan<const SliceCond*, const uint8_t*>),
+                         dim3(grid_for(n, kSliceWaves, kMaxGrid)), dim3(kBlock), 0,
+                         s, keys, key_bytes, key_offs, spec, n, index_, cfg_.nbuckets - 1, log_,
+                         cur_head(), claim_ptr(), reserve, cfg_.log_bytes, cfg_.max_item, now,
+                         rows, seg_src, seg_len, ctr_, cond, cond_bytes);
+    else
+      hipLaunchKernelGGL(k_slice_plan<>, dim3(grid_for(n, kSliceWaves, kMaxGrid)), dim3(kBlock), 0, s,
+                         keys, key_bytes, key_offs, spec, n, index_, cfg_.nbuckets - 1, log_,
+                         cur_head(), claim_ptr(), reserve, cfg_.log_bytes, cfg_.max_item, now, rows,
+                         seg_src, seg_len, ctr_);
     HIP_OK(hipGetLastError());
     device_exclusive_scan(seg_len, dst_off, 2 * n, tmp, slice_tmp_bytes_, s);
     hipLaunchKernelGGL(k_slice_offsets, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), 0, s,

@@ -633,7 +633,8 @@ void HostCache::touch(const Digest* keys, const uint32_t* expire, const uint32_t
 void HostCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
                                  const int64_t* key_offs, const SliceSpec* spec, int64_t n,
                                  SliceRow* rows, uint8_t* out, uint64_t out_cap,
-                                 uint64_t res[kSliceWords], uint32_t now, uint64_t reserve) {
+                                 uint64_t res[kSliceWords], uint32_t now, uint64_t reserve,
+                                 const SliceCond* cond, const uint8_t* cond_bytes) {
   SH_CHECK(n >= 0 && res, "sliced GET needs result words");
   SH_CHECK(n == 0 || (keys && key_bytes && key_offs && spec && rows),
            "sliced GET needs digests, key bytes with their offsets, window specs and rows");
@@ -670,7 +671,8 @@ void HostCache::get_keyed_slices(const Digest* keys, const uint8_t* key_bytes,
     if (kl != klen || (klen && std::memcmp(v + kKeyedPrefix, key_bytes + key_offs[i], (size_t)klen)))
       continue;  // another key's record: a miss
     e->vlen |= kRefBit;
-    slice_value_row(&r, spec[i], v, vlen, h.flags, e->expire);
+    slice_value_row_if(&r, spec[i], cond ? &cond[i] : nullptr, cond_bytes, v, vlen, h.flags,
+                       e->expire);
     r.out_off = total;  // (slice_value_row starts from an empty row)
     total += slice_row_bytes(r);
     vals[(size_t)i] = v;

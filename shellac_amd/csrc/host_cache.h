@@ -12,6 +12,7 @@
 
 #include "keyed.h"
 #include "layout.h"
+#include "conditional.h"
 #include "slice.h"
 
 namespace shellac {
@@ -74,11 +75,13 @@ class HostCache {
              uint32_t now);
   // Sliced GET (HbmCache::get_keyed_slices, whose semantic reference this is): the same rows,
   // the same bytes in `out` (nothing when the total exceeds out_cap), the same result words,
-  // reference bit and counters. Built on slice.h.
+  // reference bit and counters, under the same conditions (nullable). Built on slice.h and
+  // conditional.h.
   void get_keyed_slices(const Digest* keys, const uint8_t* key_bytes, const int64_t* key_offs,
                         const SliceSpec* spec, int64_t n, SliceRow* rows, uint8_t* out,
                         uint64_t out_cap, uint64_t res[kSliceWords], uint32_t now,
-                        uint64_t reserve = 0);
+                        uint64_t reserve = 0, const SliceCond* cond = nullptr,
+                        const uint8_t* cond_bytes = nullptr);
   void flush();
   // Tests: see HbmCache::debug_bucket / debug_set_entry.
   std::vector<uint64_t> debug_bucket(uint64_t b);

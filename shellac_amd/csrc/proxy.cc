@@ -229,6 +229,10 @@ struct Slot {
   // (a Range GET, or a HEAD under policy rfc, which has lookup == false)
   bool part = false;
   SliceSpec spec{};
+  // --conditional-hits: the client's validators the tier compares with the stored ones
+  // (kCondNone: the request is not conditional); `ranged`: it carries a usable Range
+  PartCond cond;
+  bool ranged = false;
   // request headers, kept for the miss path when a response may Vary (policy rfc)
   std::shared_ptr<const std::vector<Header>> req_headers;
   Bytes vary_marker;  // --grace: the URL's marker a variant lookup went through
@@ -317,6 +321,10 @@ class Reactor : public Executor {
   // answered from the cache, and requests answered from a whole GET after all
   std::atomic<uint64_t> range_requests{0}, range_206{0}, range_416{0}, head_hits{0},
       partial_fallbacks{0};
+  // --conditional-hits: requests asked of the cache under a condition, their 304 answers, and
+  // how If-Range validators compared
+  std::atomic<uint64_t> conditional_requests{0}, not_modified_304{0}, if_range_matched{0},
+      if_range_failed{0};
   // --grace: stale hits served, background revalidations started, their 304s, the objects
   // those extended in place / stored again, and revalidations the origin failed
   std::atomic<uint64_t> stale_served{0}, revalidations{0}, revalidated_304{0},
@@ -354,6 +362,8 @@ class Reactor : public Executor {
   void ask_part(Slot* s, uint64_t cid);
   void on_part(uint64_t cid, uint64_t seq, PartValue p);
   bool answer_part(Client* c, Slot* s, const PartValue& p);
+  bool not_modified_exact(const Slot* s, std::string_view hv) const;
+  void answer_not_modified(Client* c, Slot* s, std::string_view hv);
   void forward(Client* c, Slot* s);
   static std::string upstream_request(HttpParser& q);
   std::unique_ptr<HttpParser> take_parser();
@@ -746,21 +756,55 @@ void Reactor::on_request(Client* c) {
   s->d = digest_bytes(reinterpret_cast<const uint8_t*>(s->key.data()), s->key.size());
   s->lookup = px_->cfg_.cache_enabled &&
               (cfg_.policy == "reference" || method == "GET") && !q.header("authorization");
+  const bool cached_get = s->lookup && method == "GET";
   if (cfg_.partial_hits && px_->cfg_.cache_enabled && !q.header("authorization")) {
-    if (s->lookup && method == "GET") {
+    if (cached_get) {
       const std::string* rg = q.header("range");
-      s->part = rg && !q.header("if-range") && parse_single_range(rg->data(), rg->size(), &s->spec);
+      s->part = rg && (cfg_.conditional_hits || !q.header("if-range")) &&
+                parse_single_range(rg->data(), rg->size(), &s->spec);
+      s->ranged = s->part;
     } else if (!s->lookup && s->head && cfg_.policy == "rfc") {
       s->spec = SliceSpec{};
       s->spec.kind = kSliceHead;
       s->part = true;
     }
   }
+  // --conditional-hits (RFC 9110 13.2.2, reduced): If-None-Match is the condition, else
+  // If-Modified-Since; a request with If-Match or If-Unmodified-Since is not conditional here.
+  // If-Range counts only beside a usable Range, and a row carries one condition: with a
+  // 304-condition as well the row asks for the whole object ("If-Range means 200 in full").
+  if (cfg_.conditional_hits && px_->cfg_.cache_enabled && !q.header("authorization") &&
+      (cached_get || s->part) && !q.header("if-match") && !q.header("if-unmodified-since")) {
+    PartCond pc;
+    if (const std::string* inm = q.header("if-none-match")) {
+      if (parse_if_none_match(inm->data(), inm->size(), &pc)) s->cond = std::move(pc);
+    } else if (const std::string* ims = q.header("if-modified-since")) {
+      if (parse_if_modified_since(ims->data(), ims->size(), &pc)) s->cond = std::move(pc);
+    }
+    const std::string* ifr = s->ranged ? q.header("if-range") : nullptr;
+    if (ifr && s->cond.kind == kCondNone && parse_if_range(ifr->data(), ifr->size(), &pc)) {
+      s->cond = std::move(pc);
+    } else if (ifr) {  // beside a 304-condition, or a validator that can never match
+      if (s->cond.kind == kCondNone) if_range_failed++;
+      s->ranged = false;
+      s->part = s->cond.kind != kCondNone;
+    }
+    if (s->cond.kind != kCondNone) {
+      conditional_requests++;
+      if (!s->ranged && cached_get) {  // no usable Range: the whole object, or a 304
+        s->spec = SliceSpec{};
+        s->spec.kind = kSliceWhole;
+        s->part = true;
+      }
+    }
+  } else if (s->ranged && q.header("if-range")) {  // (If-Match beside it: as without the option)
+    s->ranged = s->part = false;
+  }
   if (s->lookup || s->part) s->req = std::move(c->req);  // serialized only if the cache misses
   else s->fwd = upstream_request(q);
   c->slots.push_back(std::move(s));
   if (sp->part) {
-    if (!sp->head) range_requests++;
+    if (sp->ranged) range_requests++;
     ask_part(sp, c->id);
   } else if (sp->lookup) {
     const uint64_t cid = c->id, seq = sp->seq;
@@ -1233,11 +1277,28 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
   if (hit && v.data) {
     hits++;
     if (s->vary_probe) vary_hits++;
+    // --conditional-hits with the whole object here (a tier's whole answer, a fallback, a
+    // stale object): the same decision with the same functions, so every path answers alike
+    bool not_modified = false;
+    size_t head_len = 0;
+    if ((s->cond.kind == kCondNoneMatch || s->cond.kind == kCondModifiedSince) &&
+        slice_find_head_end(reinterpret_cast<const uint8_t*>(v.data->data()), v.data->size(),
+                            &head_len)) {
+      const SliceCond sc{s->cond.kind, s->cond.ncand, 0, (uint32_t)s->cond.records.size()};
+      not_modified =
+          cond_matches(reinterpret_cast<const uint8_t*>(v.data->data()), 0, (uint32_t)head_len, sc,
+                       reinterpret_cast<const uint8_t*>(s->cond.records.data())) &&
+          not_modified_exact(s, v.data->view().substr(0, head_len));
+    }
     // --grace: past its freshness time (the flags word) the object is served stale, and
     // revalidated in the background (before deliver(): that gives the parsed request back)
     if (cfg_.grace && v.flags && unix_now() >= v.flags) {
       stale_served++;
       revalidate(s, v.data, raw);
+    }
+    if (not_modified) {
+      answer_not_modified(c, s, v.data->view().substr(0, head_len));
+      return;
     }
     deliver(c, s, v.data);
     return;
@@ -1256,9 +1317,43 @@ void Reactor::on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v) {
 // ---- partial hits (ProxyConfig::partial_hits) -------------------------------------------
 void Reactor::ask_part(Slot* s, uint64_t cid) {
   const uint64_t seq = s->seq;
-  px_->backend_->get_part(s->key, s->d, s->spec, this, [this, cid, seq](PartValue p) {
-    on_part(cid, seq, std::move(p));
-  });
+  const auto done = [this, cid, seq](PartValue p) { on_part(cid, seq, std::move(p)); };
+  if (s->cond.kind != kCondNone)
+    px_->backend_->get_part_if(s->key, s->d, s->spec, s->cond, this, done);
+  else
+    px_->backend_->get_part(s->key, s->d, s->spec, this, done);
+}
+
+// Whether a 304 is the exact answer to the slot's matched condition for the stored head: the
+// stored status is 200, and the object is not gzip-coded for a client without gzip under rfc.
+bool Reactor::not_modified_exact(const Slot* s, std::string_view hv) const {
+  const size_t sp = hv.find(' ');
+  if (sp == std::string_view::npos || hv.substr(sp + 1, 3) != "200" ||
+      (hv.size() > sp + 4 && hv[sp + 4] != ' ' && hv[sp + 4] != '\r'))
+    return false;
+  return s->client_gzip || cfg_.policy != "rfc" || !object_is_gzip(hv);
+}
+
+// 304 Not Modified from the stored head: the header lines a 304 carries (RFC 9110 15.4.5), no
+// body and no Content-Length. It counts as a hit.
+void Reactor::answer_not_modified(Client* c, Slot* s, std::string_view hv) {
+  std::string out = "HTTP/1.1 304 Not Modified\r\nServer: " + cfg_.server_name + "\r\n";
+  size_t pos = hv.find("\r\n");
+  while (pos != std::string_view::npos && pos + 2 < hv.size()) {
+    const size_t ls = pos + 2, le = hv.find("\r\n", ls);
+    if (le == std::string_view::npos || le == ls) break;  // the blank line
+    const std::string_view line = hv.substr(ls, le - ls);
+    const std::string low = to_lower(std::string(line.substr(0, line.find(':'))));
+    if (low == "cache-control" || low == "content-location" || low == "date" || low == "etag" ||
+        low == "expires" || low == "last-modified" || low == "vary") {
+      out.append(line);
+      out += "\r\n";
+    }
+    pos = le;
+  }
+  out += "Connection: keep-alive\r\n\r\n";
+  not_modified_304++;
+  complete_slot(c, s, std::make_shared<const std::string>(std::move(out)));
 }
 
 // The tier's answer to a Range GET or a HEAD. Answered here: 206, 416, a HEAD's stored head.
@@ -1287,8 +1382,22 @@ void Reactor::on_part(uint64_t cid, uint64_t seq, PartValue p) {
       return;
     }
   }
-  if ((p.status == kSliceOk || p.status == kSliceUnsat) && answer_part(c, s, p)) return;
-  if (p.status != kSliceMiss) partial_fallbacks++;
+  const bool if_range = s->cond.kind == kCondIfRangeEtag || s->cond.kind == kCondIfRangeDate;
+  if (if_range && p.status != kSliceMiss)
+    (p.status == kSliceWholeObj ? if_range_failed : if_range_matched)++;
+  if (p.status == kSliceNotModified && p.head && not_modified_exact(s, p.head->view()) &&
+      !(cfg_.grace && p.flags && unix_now() >= p.flags)) {  // (stale: on_cache revalidates)
+    hits++;
+    if (s->vary_probe) vary_hits++;
+    answer_not_modified(c, s, p.head->view());
+    return;
+  }
+  if ((p.status == kSliceOk || p.status == kSliceUnsat) && (s->ranged || head_only) &&
+      answer_part(c, s, p))
+    return;
+  // (a conditional request whose whole object came back was answered as it asked)
+  if (p.status != kSliceMiss && !(p.status == kSliceWholeObj && s->cond.kind != kCondNone))
+    partial_fallbacks++;
   if (head_only) {  // forwarded, as every HEAD is without the option
     s->key = s->base_key;
     forward(c, s);
@@ -2529,6 +2638,7 @@ std::string Proxy::stats_json() {
            lslow = 0, idd = 0, vst = 0, vh = 0, prq = 0, pob = 0, pdn = 0, fpg = 0, spr = 0,
            sob = 0, tpr = 0, tpo = 0, tso = 0, tgf = 0, insp = 0, pdr = 0, pgr = 0;
   uint64_t ph[5] = {};  // --partial-hits
+  uint64_t ch[4] = {};  // --conditional-hits
   uint64_t pmax[5] = {}, crst = 0;
   uint64_t gr[6] = {};  // --grace: stale hits, revalidations and their outcomes
   uint64_t h[kHistBuckets] = {};
@@ -2553,6 +2663,8 @@ std::string Proxy::stats_json() {
     pgr += r->purge_glob_requests;
     ph[0] += r->range_requests; ph[1] += r->range_206; ph[2] += r->range_416;
     ph[3] += r->head_hits; ph[4] += r->partial_fallbacks;
+    ch[0] += r->conditional_requests; ch[1] += r->not_modified_304;
+    ch[2] += r->if_range_matched; ch[3] += r->if_range_failed;
     gr[0] += r->stale_served; gr[1] += r->revalidations; gr[2] += r->revalidated_304;
     gr[3] += r->revalidate_touched; gr[4] += r->revalidate_restored;
     gr[5] += r->revalidate_errors;
@@ -2591,6 +2703,8 @@ std::string Proxy::stats_json() {
     << ",\"range_requests\":" << ph[0] << ",\"range_206\":" << ph[1]
     << ",\"range_416\":" << ph[2] << ",\"head_hits\":" << ph[3]
     << ",\"partial_fallbacks\":" << ph[4]
+    << ",\"conditional_requests\":" << ch[0] << ",\"not_modified_304\":" << ch[1]
+    << ",\"if_range_matched\":" << ch[2] << ",\"if_range_failed\":" << ch[3]
     << ",\"stale_served\":" << gr[0] << ",\"revalidations\":" << gr[1]
     << ",\"revalidated_304\":" << gr[2] << ",\"revalidate_touched\":" << gr[3]
     << ",\"revalidate_restored\":" << gr[4] << ",\"revalidate_errors\":" << gr[5]

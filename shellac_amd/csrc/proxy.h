@@ -98,6 +98,17 @@ struct ProxyConfig {
   // (`partial_fallbacks`). A HEAD miss is forwarded and its response not cached, as without
   // it. Fills keep the origin's Accept-Ranges header instead of dropping it.
   bool partial_hits = false;
+  // Answer a client's own validators from the cache (default off: every request is answered
+  // as without it). A cacheable GET without Authorization, and a HEAD that partial_hits serves,
+  // with If-None-Match (else If-Modified-Since; neither beside If-Match or
+  // If-Unmodified-Since) asks the tier with CacheBackend::get_part_if, which compares the
+  // stored ETag / Last-Modified where the object lies (on the GPU for the HBM tier): a match
+  // whose stored status is 200 is answered 304 Not Modified from the stored head (counted in
+  // `not_modified_304`, and as a hit), anything else as without the header. With partial_hits,
+  // `Range` + `If-Range` is one trip too: 206 if the validator matches (strong tag, or the
+  // Last-Modified value byte for byte), the whole object in a 200 if not. If-Modified-Since
+  // matches only the exact Last-Modified value; stored headers are not updated from a 304.
+  bool conditional_hits = false;
   // cache key = Host + URL (ref: URL only). The Python/CLI layer defaults it on for
   // policy rfc (vhosts must not share entries) and off for policy reference.
   bool key_host = false;

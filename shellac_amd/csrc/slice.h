@@ -48,13 +48,14 @@ enum : uint32_t {
   kSliceOk = 1,
   kSliceUnsat = 2,     // the head is returned, the window is empty
   kSliceWholeObj = 3,  // kSliceWhole, or the value is not sliceable: the whole value is returned
+  kSliceNotModified = 4,  // the row's condition holds (conditional.h): the head, an empty window
 };
 
 // One result row. Its bytes in `out`: segment 0 at out_off, the value's first head_bytes
 // bytes; segment 1 at out_off + head_bytes, the 16-byte granules of the value that cover the
 // window (slice_window_bytes()), the window's first byte at + skew. A miss occupies nothing.
 // For kSliceMiss every other field but out_off is 0; for kSliceWholeObj the head and window
-// fields are 0.
+// fields are 0; a kSliceNotModified row is a kSliceOk row of kind kSliceHead (win_len = 0).
 struct alignas(16) SliceRow {
   uint32_t status;
   uint32_t vlen;    // stored value bytes (the keyed image)

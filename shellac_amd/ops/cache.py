@@ -149,7 +149,10 @@ def unpack_records(out: torch.Tensor, off: torch.Tensor, size: torch.Tensor) -> 
 
 
 SLICE_KINDS = {"head": 0, "range": 1, "from": 2, "suffix": 3, "whole": 4}  # slice.h kSlice*
-SLICE_STATUS = ("miss", "ok", "unsat", "whole")  # slice.h kSliceMiss ..
+SLICE_STATUS = ("miss", "ok", "unsat", "whole", "not_modified")  # slice.h kSliceMiss ..
+# conditional.h kCond*
+COND_KINDS = {"none": 0, "none_match": 1, "modified_since": 2, "if_range_etag": 3,
+              "if_range_date": 4}
 # u32 words of a SliceRow (slice.h); out_off is the u64 at bytes 48..55
 _SLICE_WORDS = ("status", "vlen", "flags", "expire", "head_off", "body_off", "body_len", "skew",
                 "win_first", "win_len", "head_bytes")
@@ -165,6 +168,41 @@ def pack_slice_specs(specs) -> np.ndarray:
         kind = SLICE_KINDS[s[0]] if isinstance(s[0], str) else int(s[0])
         arr[i] = (kind, int(s[1]) if len(s) > 1 else 0, int(s[2]) if len(s) > 2 else 0)
     return arr.view(np.uint8).reshape(len(specs), 24)
+
+
+def pack_slice_conds(conds):
+    """Row conditions -> ``(uint8 [n, 16] rows of SliceCond {u32 kind, ncand, off, len}, uint8
+    candidate bytes)`` (``csrc/conditional.h``). ``conds[i]`` is ``None``, ``("none_match",
+    [tag, ...])`` (entity-tags as the client sent them; a ``W/`` is stripped, which gives the
+    weak comparison), ``("none_match", "*")``, ``("modified_since", date)``,
+    ``("if_range_etag", tag)`` (a weak tag never matches) or ``("if_range_date", date)``. A
+    candidate is sent as one ``[u8 len | bytes]`` record and holds at most 255 bytes; a list at
+    most 16 tags."""
+    rows = np.zeros((len(conds), 4), dtype=np.uint32)
+    blob = bytearray()
+    for i, c in enumerate(conds):
+        if c is None:
+            continue
+        kind, arg = c
+        kind = COND_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if kind == COND_KINDS["none_match"]:
+            if isinstance(arg, (bytes, bytearray)):
+                arg = [arg]
+            cands = [] if isinstance(arg, str) and arg == "*" else \
+                [bytes(t)[2:] if bytes(t)[:2] == b"W/" else bytes(t) for t in arg]
+            if not isinstance(arg, str) and not cands:
+                raise ValueError("none_match needs '*' or at least one entity-tag")
+        elif kind == COND_KINDS["if_range_etag"]:
+            cands = [] if bytes(arg)[:2] == b"W/" else [bytes(arg)]
+        else:
+            cands = [bytes(arg)]
+        if len(cands) > 16 or any(len(t) > 255 for t in cands):
+            raise ValueError("a condition holds at most 16 candidates of at most 255 bytes")
+        off = len(blob)
+        for t in cands:
+            blob += bytes([len(t)]) + t
+        rows[i] = (kind, len(cands), off, len(blob) - off)
+    return rows.view(np.uint8).reshape(len(conds), 16), np.frombuffer(bytes(blob), dtype=np.uint8)
 
 
 def slice_rows(rows: torch.Tensor) -> list:
@@ -747,7 +785,8 @@ class CacheShard:
 
     # -- sliced GET -----------------------------------------------------------------
     def get_keyed_slices(self, keys: torch.Tensor, key_bytes, specs: torch.Tensor,
-                         out: torch.Tensor, now: Optional[int] = None, reserve_bytes: int = 0):
+                         out: torch.Tensor, now: Optional[int] = None, reserve_bytes: int = 0,
+                         conds=None):
         """Sliced GET (``csrc/slice.h``; ``k_slice_plan`` on a GPU shard): row i asks for the
         window ``specs[i]`` of the keyed value stored under ``keys[i]`` (int64 [n, 2]) with
         exactly the key ``key_bytes`` names (``(uint8 buffer, int64 offsets[n + 1])``, as
@@ -758,7 +797,14 @@ class CacheShard:
         When the total exceeds ``out.numel()`` nothing is written to ``out``; rows and totals
         are complete. ``n`` <= SMALL_GET_MAX. Asynchronous on the current stream; a shard's
         sliced GETs share one workspace, so calls on different streams run one after the other
-        (the later one waits for the earlier one's event on the device)."""
+        (the later one waits for the earlier one's event on the device).
+        ``conds``: ``None``, or ``(uint8 [n, SLICE_COND_BYTES], uint8 candidate bytes)`` on the
+        shard's device, from ``pack_slice_conds``: one condition per row, decided by the shard
+        against the stored ``ETag`` / ``Last-Modified`` (``k_slice_plan`` on a GPU shard). A
+        matched ``none_match`` / ``modified_since`` row returns the head alone with status
+        ``SLICE_NOT_MODIFIED``; an unmatched ``if_range_*`` row the whole value. Every row's
+        ``[off, off + len)`` must lie inside the candidate bytes (the shard reads nothing of a
+        row's candidates outside that range; records that overrun it never match)."""
         c = core()
         self._check(keys, "keys")
         self._check(specs, "specs")
@@ -780,14 +826,24 @@ class CacheShard:
         now = self.now() if now is None else now
         args = (keys.data_ptr(), buf.data_ptr(), offs.data_ptr(), specs.data_ptr(), n,
                 rows.data_ptr(), out.data_ptr(), out.numel(), res.data_ptr(), now)
+        cp = (0, 0)
+        if conds is not None:
+            crow, cbytes = conds
+            self._check(crow, "conds")
+            self._check(cbytes, "candidate bytes")
+            if crow.dtype != torch.uint8 or crow.numel() != n * c.SLICE_COND_BYTES or \
+                    cbytes.dtype != torch.uint8:
+                raise TypeError("conds must be (uint8 [n, SLICE_COND_BYTES], uint8 bytes) "
+                                "from pack_slice_conds")
+            cp =(crow.data_ptr(), cbytes.data_ptr() if cbytes.numel() else 0)
         if self.is_gpu:
-            self._impl.get_keyed_slices(*args, self._s(), int(reserve_bytes))
+            self._impl.get_keyed_slices(*args, self._s(), int(reserve_bytes), *cp)
         else:
-            self._impl.get_keyed_slices(*args, int(reserve_bytes))
+            self._impl.get_keyed_slices(*args, int(reserve_bytes), *cp)
         return rows, res
 
     def get_slices(self, keys: Sequence[bytes], specs, now: Optional[int] = None,
-                   reserve_bytes: int = 0, out_cap: Optional[int] = None) -> list:
+                   reserve_bytes: int = 0, out_cap: Optional[int] = None, conds=None) -> list:
         """Sliced GET for byte-string keys: the HTTP head and one byte window of each stored
         response, cut by the shard (the rest of the object is not moved). ``specs[i]`` is
         ``("head",)``, ``("range", a, b)`` (body bytes a..b inclusive, b clamped),
@@ -799,12 +855,20 @@ class CacheShard:
         from ``HTTP/`` through the blank line. Works on GPU and CPU shards. Synchronises.
         ``out_cap``: the response buffer's bytes; by default it grows until the batch fits (a
         batch that did not fit is asked again, and counted again); an explicit one that is too
-        small raises ``ValueError``."""
+        small raises ``ValueError``.
+        ``conds``: one condition per row (``pack_slice_conds``' forms, ``None``: none), the
+        client's validators, which the shard compares with the stored ``ETag`` /
+        ``Last-Modified``: a ``none_match`` / ``modified_since`` row that matches answers
+        ``"not_modified"`` (``head`` set, ``window`` empty, whatever its spec: a 304), one that
+        does not answers its spec; an ``if_range_*`` row that matches answers its spec (a
+        206), one that does not answers ``"whole"`` (a 200)."""
         c = core()
         keys = [bytes(k) for k in keys]
         n = len(keys)
         if len(specs) != n:
             raise ValueError("one window spec per key")
+        if conds is not None and len(conds) != n:
+            raise ValueError("one condition (or None) per key")
         if n == 0:
             return []
         d = digest_strings(keys, self.device)
@@ -812,10 +876,15 @@ class CacheShard:
         buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, np.uint8)
         kb = (torch.from_numpy(buf.copy()).to(self.device), torch.from_numpy(offs).to(self.device))
         sp = torch.from_numpy(pack_slice_specs(specs)).to(self.device)
+        cd = None
+        if conds is not None:
+            crow, cbytes = pack_slice_conds(conds)
+            cd = (torch.from_numpy(crow.copy()).to(self.device),
+                  torch.from_numpy(cbytes.copy()).to(self.device))
         cap = (1 << 20) if out_cap is None else int(out_cap)
         while True:
             out = torch.zeros(max(cap, 16), dtype=torch.uint8, device=self.device)[:cap]
-            rows, res = self.get_keyed_slices(d, kb, sp, out, now, reserve_bytes)
+            rows, res = self.get_keyed_slices(d, kb, sp, out, now, reserve_bytes, conds=cd)
             total = int(res.tolist()[1])  # (waits for the stream)
             if total <= cap:
                 break

@@ -157,7 +157,7 @@ class Server:
                  gzip_batch_us: int = 200, gzip_workers: int = 2,
                  max_inflate_bytes: int = 64 << 20, purge: str = "off", grace: int = 0,
                  tag_header: str = "", inspect: str = "off", partial_hits: bool = False,
-                 **backend_opts):
+                 conditional_hits: bool = False, **backend_opts):
         """``grace`` (seconds, 0 = off): keep cached objects that long past their TTL; a hit
         in that window is served stale at once while one background request per key
         revalidates it upstream (``If-None-Match`` / ``If-Modified-Since``) — a 304 extends
@@ -200,7 +200,21 @@ class Server:
         status other than 200, ``Transfer-Encoding``, a gzip-coded object for a client without
         ``Accept-Encoding: gzip``, an object already stale under ``grace``) is answered from a
         whole GET and counted as ``partial_fallbacks``. Fills keep the origin's
-        ``Accept-Ranges`` header."""
+        ``Accept-Ranges`` header.
+
+        ``conditional_hits`` (default off: every request is answered as without it): a
+        cacheable ``GET`` (and a ``HEAD`` that ``partial_hits`` serves) with ``If-None-Match``,
+        else ``If-Modified-Since``, and without ``If-Match`` / ``If-Unmodified-Since``, asks the
+        tier with the client's validators; the tier compares them with the stored ``ETag`` /
+        ``Last-Modified`` (``k_slice_plan`` on the HBM tier, so a 304 moves only the head
+        across PCIe). A match on an object stored with status 200 is ``304 Not Modified`` with
+        the stored ``Cache-Control``, ``Content-Location``, ``Date``, ``ETag``, ``Expires``,
+        ``Last-Modified`` and ``Vary`` lines; anything else is answered as without the header.
+        ``If-None-Match`` uses the weak comparison; ``If-Modified-Since`` matches the exact
+        ``Last-Modified`` value only. With ``partial_hits``, ``Range`` + ``If-Range`` gets
+        ``206`` if the validator matches (a strong tag, or the date byte for byte) and the
+        whole object if not. Counted in ``conditional_requests``, ``not_modified_304``,
+        ``if_range_matched``, ``if_range_failed`` (and ``hbm_cond_slices``)."""
         if purge not in ("off", "loopback", "any"):
             raise ValueError("purge must be 'off', 'loopback' or 'any'")
         if inspect not in ("off", "loopback", "any"):
@@ -225,7 +239,8 @@ class Server:
             gzip_gpu=int(gzip_gpu), gzip_batch_us=int(gzip_batch_us),
             max_inflate_bytes=int(max_inflate_bytes), gzip_workers=int(gzip_workers),
             purge=purge, grace=int(grace), tag_header=str(tag_header or ""),
-            inspect=inspect, partial_hits=bool(partial_hits))
+            inspect=inspect, partial_hits=bool(partial_hits),
+            conditional_hits=bool(conditional_hits))
         self._started = False
 
     @property
@@ -347,6 +362,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
                         "to page). "
                         "'PURGE' with 'X-Purge-Dry-Run: 1' answers what a purge would hit. "
                         "Default: off (the URL is forwarded like any other)")
+    p.add_argument("--conditional-hits", action="store_true",
+                   help="answer a client's own validators from the cache: 'If-None-Match' (else "
+                        "'If-Modified-Since', compared with the exact Last-Modified value) on a "
+                        "cached object gets '304 Not Modified' built from the stored head, and "
+                        "with --partial-hits 'Range' + 'If-Range' gets 206 or the whole object in "
+                        "one trip to the cache tier, which compares the validators where the "
+                        "object lies (on the GPU for --cache hbm). Default: off")
     p.add_argument("--partial-hits", action="store_true",
                    help="answer Range requests (one 'bytes=' range, no If-Range) and, under "
                         "--policy rfc, HEAD requests from the cache: 206 with Content-Range, 416, "
@@ -412,7 +434,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                  gzip_gpu=args.gzip_gpu, gzip_batch_us=args.gzip_batch_us,
                  max_inflate_bytes=args.max_inflate_mb << 20, purge=args.purge,
                  grace=args.grace, tag_header=args.tag_header, inspect=args.inspect,
-                 partial_hits=args.partial_hits,
+                 partial_hits=args.partial_hits, conditional_hits=args.conditional_hits,
                  **({"fault": args.fault} if args.fault else {}),
                  **({"dram_mb": args.dram_mb} if kind == "dram" else {}),
                  **({"gpus": gpus, "hbm_gb": args.hbm_gb, "batch_us": args.batch_us,
