@@ -92,50 +92,13 @@ void DramBackend::del(const std::string& key, const Digest& d, Executor*, DelCal
   if (done) done(found);
 }
 
-void DramBackend::purge_prefix(const std::string& prefix, Executor*, PurgeCallback done) {
-  // (an empty prefix is flush(), not a purge: refused, as by every tier)
-  const int64_t n = prefix.empty() ? -1 : (int64_t)cache_.purge_prefix(prefix, now());
-  if (done) done(n);
-}
-
-void DramBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                                uint32_t keep_s, Executor*, PurgeCallback done) {
+void DramBackend::purge(const KeyedSelector& what, const PurgeAction& how, Executor*,
+                        PurgeCallback done) {
   const uint32_t n = now();
-  const int64_t c = pattern.empty() ? -1
-                                    : (int64_t)cache_.soften_prefix(pattern, exact, stale_at,
-                                                                    keep_s ? n + keep_s : 0, n);
-  if (done) done(c);
-}
-
-void DramBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor*, PurgeCallback done) {
-  const bool ok = !hashes.empty() && hashes.size() <= kMaxPurgeTags;
-  const int64_t n = ok ? (int64_t)cache_.purge_tags(hashes, now()) : -1;
-  if (done) done(n);
-}
-
-void DramBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
-                              uint32_t keep_s, Executor*, PurgeCallback done) {
-  const uint32_t n = now();
-  const bool ok = !hashes.empty() && hashes.size() <= kMaxPurgeTags;
-  const int64_t c = ok ? (int64_t)cache_.soften_tags(hashes, stale_at, keep_s ? n + keep_s : 0, n)
-                       : -1;
-  if (done) done(c);
-}
-
-void DramBackend::purge_glob(const std::string& pattern, Executor*, PurgeCallback done) {
-  KeyedGlob g;
-  const int64_t n = compile_keyed_glob(pattern, &g, nullptr) ? (int64_t)cache_.purge_glob(g, now())
-                                                             : -1;
-  if (done) done(n);
-}
-
-void DramBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
-                              Executor*, PurgeCallback done) {
-  const uint32_t n = now();
-  KeyedGlob g;
-  const int64_t c = compile_keyed_glob(pattern, &g, nullptr)
-                        ? (int64_t)cache_.soften_glob(g, stale_at, keep_s ? n + keep_s : 0, n)
-                        : -1;
+  const int64_t c = purge_refused(what, how)
+                        ? -1
+                        : (int64_t)cache_.purge(what, how.soft, how.stale_at,
+                                                how.keep_s ? n + how.keep_s : 0, n);
   if (done) done(c);
 }
 
@@ -298,7 +261,7 @@ void TieredBackend::set(const std::string& key, const Digest& d, Bytes value, ui
   l1_->set(key, d, std::move(value), flags, ttl_s);
 }
 
-// L2 first, then L1, with the purge epoch moved in between (as purge_prefix): a GET that hit
+// L2 first, then L1, with the purge epoch moved in between (as purge()): a GET that hit
 // the object in L2 before it was deleted there cannot promote it into L1 after the L1 delete.
 void TieredBackend::del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) {
   l2_->del(key, d, ex, [this, key, d, ex, done](bool f2) {
@@ -326,28 +289,15 @@ void TieredBackend::move_purge_epoch() {
   purge_epoch_.fetch_add(1, std::memory_order_acq_rel);
 }
 
-void TieredBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
+void TieredBackend::purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+                          PurgeCallback done) {
   purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->purge_prefix(prefix, ex, [this, prefix, ex, done = std::move(done)](int64_t n2) {
-    // L2 holds none of the objects now: a GET that starts after this move finds nothing
-    // there, and one that hit earlier has its promotion dropped, or landed it in L1 before
-    // the pass below
+  l2_->purge(what, how, ex, [this, what, how, ex, done = std::move(done)](int64_t n2) {
+    // L2 holds none of the objects now (soft: only stale copies): a GET that starts after
+    // this move finds nothing fresh there, and one that hit earlier has its promotion
+    // dropped, or landed it in L1 before the pass below
     move_purge_epoch();
-    l1_->purge_prefix(prefix, ex, [done, n2](int64_t n1) {
-      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
-    });
-  });
-}
-
-void TieredBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                                  uint32_t keep_s, Executor* ex, PurgeCallback done) {
-  purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->soften_prefix(pattern, exact, stale_at, keep_s, ex,
-                     [this, pattern, exact, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
-    // L2's copies are stale now: a GET that hit a fresh one earlier has its promotion
-    // dropped, or landed it in L1 before the pass below, which softens it
-    move_purge_epoch();
-    l1_->soften_prefix(pattern, exact, stale_at, keep_s, ex, [done, n2](int64_t n1) {
+    l1_->purge(what, how, ex, [done, n2](int64_t n1) {
       if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
     });
   });
@@ -356,53 +306,6 @@ void TieredBackend::soften_prefix(const std::string& pattern, bool exact, uint32
 // Fills write both levels, so L2 holds the superset: the listing is L2's.
 void TieredBackend::list_objects(const ListQuery& q, Executor* ex, ListCallback done) {
   l2_->list_objects(q, ex, std::move(done));
-}
-
-void TieredBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor* ex,
-                               PurgeCallback done) {
-  purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->purge_tags(hashes, ex, [this, hashes, ex, done = std::move(done)](int64_t n2) {
-    // as purge_prefix: L2 is clean from here on, promotions read before it are dropped
-    move_purge_epoch();
-    l1_->purge_tags(hashes, ex, [done, n2](int64_t n1) {
-      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
-    });
-  });
-}
-
-void TieredBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
-                                uint32_t keep_s, Executor* ex, PurgeCallback done) {
-  purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->soften_tags(hashes, stale_at, keep_s, ex,
-                   [this, hashes, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
-    move_purge_epoch();
-    l1_->soften_tags(hashes, stale_at, keep_s, ex, [done, n2](int64_t n1) {
-      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
-    });
-  });
-}
-
-void TieredBackend::purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
-  purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->purge_glob(pattern, ex, [this, pattern, ex, done = std::move(done)](int64_t n2) {
-    // as purge_prefix: L2 is clean from here on, promotions read before it are dropped
-    move_purge_epoch();
-    l1_->purge_glob(pattern, ex, [done, n2](int64_t n1) {
-      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
-    });
-  });
-}
-
-void TieredBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
-                                Executor* ex, PurgeCallback done) {
-  purges_.fetch_add(1, std::memory_order_relaxed);
-  l2_->soften_glob(pattern, stale_at, keep_s, ex,
-                   [this, pattern, stale_at, keep_s, ex, done = std::move(done)](int64_t n2) {
-    move_purge_epoch();
-    l1_->soften_glob(pattern, stale_at, keep_s, ex, [done, n2](int64_t n1) {
-      if (done) done(n1 < 0 || n2 < 0 ? -1 : n1 + n2);
-    });
-  });
 }
 
 void TieredBackend::flush() {

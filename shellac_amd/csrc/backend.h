@@ -87,7 +87,7 @@ using PartCond = CondRequest;
 // unmatched if_range_* the whole value.
 PartValue slice_cache_value_if(bool hit, CacheValue v, const SliceSpec& spec, const PartCond& cond);
 using DelCallback = std::function<void(bool found)>;
-// Prefix purge: objects removed, or -1 if the tier cannot scan its keys.
+// Purge: objects removed or softened, or -1 if the tier cannot scan its keys.
 using PurgeCallback = std::function<void(int64_t removed)>;
 // In-place touch: 1 touched, 0 not found, -1 the tier cannot do it.
 using TouchCallback = std::function<void(int status)>;
@@ -142,78 +142,23 @@ class CacheBackend {
   virtual void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
                    uint32_t ttl_s) = 0;
   virtual void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) = 0;
-  // Invalidation: remove every object whose key starts with `prefix`. `done` runs once, on
-  // `ex`'s thread (inline for synchronous backends), with the number of objects removed, or
-  // -1 where the tier cannot do it (the default: a tier that cannot enumerate its keys, e.g.
-  // memcached) and for an empty prefix, which every tier refuses (that is flush()). Objects stored before the call are gone
-  // when `done` runs; GETs racing the purge may still hit until then.
-  virtual void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
-    (void)prefix;
+  // Invalidation (selector.h): carry out `how` on every live object `what` selects: remove it,
+  // or (soft) keep it and make it stale. `done` runs once, on `ex`'s thread (inline for
+  // synchronous backends), with the number of objects removed, or of live matching objects
+  // softened (whether or not their words changed), or -1 where the tier cannot do it (the
+  // default: a tier that cannot enumerate its keys, e.g. memcached) and for what every tier
+  // refuses (purge_refused: a refused selector, everything, the removal of one key). Objects
+  // stored before the call are gone, or stale, when `done` runs; GETs racing the purge may
+  // still hit until then.
+  virtual void purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+                     PurgeCallback done) {
+    (void)what;
+    (void)how;
     if (!done) return;
     if (ex) ex->post([done] { done(-1); });
     else done(-1);
   }
-  // Soft purge: end the freshness of every live object whose key starts with `pattern`
-  // (`exact`: equals it) and keep the object: its flags word (the proxy's freshness time)
-  // becomes `stale_at`, and with keep_s != 0 an object that never expires or expires later
-  // than keep_s seconds from now expires then — a life is only shortened; keep_s == 0 leaves
-  // expiries alone. `done` as for purge_prefix: the number of live matching objects (whether
-  // or not their words changed), or -1 where the tier cannot do it (the default) and for an
-  // empty pattern.
-  virtual void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                             uint32_t keep_s, Executor* ex, PurgeCallback done) {
-    (void)pattern;
-    (void)exact;
-    (void)stale_at;
-    (void)keep_s;
-    if (!done) return;
-    if (ex) ex->post([done] { done(-1); });
-    else done(-1);
-  }
-  // Purge by surrogate key: drop every live object whose stored value carries a tag block
-  // (keyed.h) holding one of `hashes` (tag_hash of each tag; at most kMaxPurgeTags), or the
-  // overflow block. Ordered and answered as purge_prefix: the objects removed, or -1 where
-  // the tier cannot do it (the default), for an empty list and for one that is too long.
-  virtual void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) {
-    (void)hashes;
-    if (!done) return;
-    if (ex) ex->post([done] { done(-1); });
-    else done(-1);
-  }
-  // Soft purge by surrogate key: purge_tags' matcher, soften_prefix's action and answer.
-  virtual void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
-                           uint32_t keep_s, Executor* ex, PurgeCallback done) {
-    (void)hashes;
-    (void)stale_at;
-    (void)keep_s;
-    if (!done) return;
-    if (ex) ex->post([done] { done(-1); });
-    else done(-1);
-  }
-  // Purge by glob: drop every live object whose stored key, up to its first 0x1f byte (a Vary
-  // variant goes with its base key), matches `pattern` (keyed.h: '*' is any run of bytes, '\\'
-  // makes the next byte literal, anchored at both ends). Ordered and answered as purge_prefix:
-  // the objects removed, or -1 where the tier cannot do it (the default) and for a pattern
-  // compile_keyed_glob refuses (empty, stars only, a dangling '\\', over a limit).
-  virtual void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
-    (void)pattern;
-    if (!done) return;
-    if (ex) ex->post([done] { done(-1); });
-    else done(-1);
-  }
-  // Soft purge by glob: purge_glob's matcher, soften_prefix's action and answer.
-  virtual void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
-                           Executor* ex, PurgeCallback done) {
-    (void)pattern;
-    (void)stale_at;
-    (void)keep_s;
-    if (!done) return;
-    if (ex) ex->post([done] { done(-1); });
-    else done(-1);
-  }
-  // Inspection, read-only: the live objects whose stored key starts with (exact: equals)
-  // q.pattern, or that carry one of q.tags, or whose key matches the glob q.pattern
-  // (kListGlob), or all of them; how many they are and their bytes
+  // Inspection, read-only: the live objects q.what selects; how many they are and their bytes
   // (per stored copy, as a purge's count), and up to q.limit of them after the cursor q.after,
   // in an order of the tier's own that a cursor pages through exactly (`next`; empty: the
   // end). `done` runs once, on `ex`'s thread (inline for synchronous backends). ok == false:
@@ -288,16 +233,9 @@ class DramBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
-  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
-  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
-                     Executor* ex, PurgeCallback done) override;
-  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  void purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+             PurgeCallback done) override;
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
-  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
-                   Executor* ex, PurgeCallback done) override;
-  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
-  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
-                   PurgeCallback done) override;
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override;
   void flush() override;
@@ -424,24 +362,14 @@ class HbmBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
-  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
-  // To this tier a soft purge is a purge: the same ReqKind::Purge request carrying the soft
-  // fields, so it is queued to every shard in service behind the writes queued before it, hot
-  // replicas and refresh fills included, and marks shards out of service purge_dirty.
-  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
-                     Executor* ex, PurgeCallback done) override;
-  // The same ReqKind::Purge request carrying a tag list instead of a pattern: ordering,
-  // fan-out, hot replicas, refresh fills and purge_dirty are purge_prefix's.
-  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  // Every shard scans its own index (a selector has no owner, and the hot replicas live on
+  // all of them): one ReqKind::Purge request per shard in service carrying the selector and
+  // the action, queued behind the writes queued before it, hot replicas and refresh fills
+  // included. To this tier a soft purge is a purge: only the launch differs. A shard out of
+  // service is marked purge_dirty.
+  void purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+             PurgeCallback done) override;
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
-  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
-                   Executor* ex, PurgeCallback done) override;
-  // The same ReqKind::Purge request carrying the compiled glob (compiled once per call, shared
-  // by the shards' requests): ordering, fan-out, hot replicas, refresh fills and purge_dirty
-  // are purge_prefix's.
-  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
-  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
-                   PurgeCallback done) override;
   // Routed like del(): to the owner, and for a hot object written through to every shard in
   // service (the answer is the owner's). Queued on the shard's stream behind the writes
   // queued before it; a flight's touches are one key-exact HbmCache::touch launch.
@@ -459,13 +387,14 @@ class HbmBackend : public CacheBackend {
 
   struct HotFill;
   struct HotRefresh;  // one refresh's state and its steps (hbm_hot.cc)
-  // One purge_prefix call fanned out over the shards: each shard's Purge request adds what
+  // One purge() call fanned out over the shards: each shard's Purge request adds what
   // its scan removed when its flight is reaped; the last one to finish (or fail) answers.
   struct Purge {
     std::atomic<int> left{0};
     std::atomic<int64_t> removed{0};
     Executor* ex = nullptr;
     PurgeCallback cb;
+    KeyedSelector what;  // the call's copy: the shards' requests point into it
   };
   // One list_objects call walking the shards in order (backend_hbm.cc list_step): every shard
   // in service scans (the totals cover them all), the shards from the cursor's on are asked
@@ -488,13 +417,9 @@ class HbmBackend : public CacheBackend {
     Bytes value;
     uint32_t flags = 0, ttl = 0;
     bool has_flags = false;  // Touch: `flags` replaces the object's (else they stay)
-    // Purge: a soft one (soften_prefix) keeps the objects; `flags` holds stale_at and `ttl`
-    // keep_s; `exact`: the key must equal the pattern
-    bool soft = false, exact = false;
-    // Purge by tag (purge_tags / soften_tags): the hash list; `key` is empty then
-    std::shared_ptr<const std::vector<uint64_t>> tags;
-    // Purge by glob (purge_glob / soften_glob): the compiled pattern; `key` is empty then
-    std::shared_ptr<const KeyedGlob> glob;
+    // Purge: what is selected (Purge::what of `purge`, which it keeps alive) and what is done
+    std::shared_ptr<const KeyedSelector> what;
+    PurgeAction how;
     Executor* ex = nullptr;
     GetCallback gcb;
     DelCallback dcb;
@@ -506,7 +431,7 @@ class HbmBackend : public CacheBackend {
     // finished on the GPU (ok) or was failed
     std::function<void(bool ok)> ccb;
     std::shared_ptr<HotFill> fill;
-    std::shared_ptr<Purge> purge;  // Purge (`key` holds the pattern)
+    std::shared_ptr<Purge> purge;  // Purge: the call it belongs to
     std::shared_ptr<ListWalk> list;  // List: the walk it belongs to; `flags` holds the rows
     uint64_t list_start = 0;         // asked of this shard, list_start the start slot
   };
@@ -568,20 +493,15 @@ class HbmBackend : public CacheBackend {
   std::atomic<uint64_t> up_mask_{0};  // bit i: shard i serves requests
   double epoch_;
   std::atomic<uint64_t> no_shard_misses_{0};
-  // purge_prefix calls begun / answered: a warm restore that overlapped one may have copied
+  // purge() calls begun / answered: a warm restore that overlapped one may have copied
   // objects a peer had not purged yet, and flushes the restored shard again
   std::atomic<uint64_t> purge_started_{0}, purge_done_{0};
   std::atomic<uint64_t> soft_purges_{0};
-  // purge_tags and soften_tags calls taken (they count in purge_started_ / purge_done_ for
-  // the restore's overlap check, and are taken out of the `hbm_purges` figure)
+  // purges by tag taken, hard and soft (they count in purge_started_ / purge_done_ for the
+  // restore's overlap check, and are taken out of the `hbm_purges` figure)
   std::atomic<uint64_t> tag_purges_{0};
-  std::atomic<uint64_t> glob_purges_{0};  // purge_glob and soften_glob calls, counted likewise
+  std::atomic<uint64_t> glob_purges_{0};  // purges by glob, counted likewise
   void purge_finish(const std::shared_ptr<Purge>& p);
-  // purge_prefix and soften_prefix: `proto` (kind Purge, the pattern and the soft fields) goes
-  // to every shard in service
-  void purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done);
-  void soften_or_purge_glob(const std::string& pattern, bool soft, uint32_t stale_at,
-                            uint32_t keep_s, Executor* ex, PurgeCallback done);
   // list_objects' walk: asks the next shard in service, or answers
   void list_step(std::shared_ptr<ListWalk> w);
   std::atomic<uint64_t> lists_{0};
@@ -642,23 +562,13 @@ class TieredBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
-  // L2 first, then L1; the sum, or -1 if either level cannot purge. A GET that hit L2 before
-  // the purge does not promote its object into L1 after L1 was purged (purge_epoch_; del()
-  // does the same for one key).
-  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override;
-  // L2 first, then L1, with the purge epoch moved in between, exactly as purge_prefix: a
-  // promotion read before the soft purge would put a fresh copy into L1. The sum, or -1 if
-  // either level cannot.
-  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
-                     Executor* ex, PurgeCallback done) override;
-  // L2 then L1 with the purge epoch moved in between, as the prefix forms.
-  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override;
+  // L2 first, then L1, with the purge epoch moved in between; the sum, or -1 if either level
+  // cannot. A GET that hit L2 before the purge does not promote its object into L1 after L1
+  // was purged or softened (purge_epoch_; del() does the same for one key): the promotion
+  // would bring back a removed object, or a fresh copy of a softened one.
+  void purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+             PurgeCallback done) override;
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override;
-  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
-                   Executor* ex, PurgeCallback done) override;
-  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override;
-  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
-                   PurgeCallback done) override;
   // L2 first, then L1; the answer is L2's (on 0 or -1 the caller re-stores the object, which
   // writes both levels). A promotion that straddles the touch is dropped, as for del(): it
   // would carry the pre-touch TTL and flags into L1.
@@ -719,29 +629,12 @@ class FaultBackend : public CacheBackend {
   void set(const std::string& key, const Digest& d, Bytes value, uint32_t flags,
            uint32_t ttl_s) override;
   void del(const std::string& key, const Digest& d, Executor* ex, DelCallback done) override;
-  void purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) override {
-    inner_->purge_prefix(prefix, ex, std::move(done));
-  }
-  void soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at, uint32_t keep_s,
-                     Executor* ex, PurgeCallback done) override {
-    inner_->soften_prefix(pattern, exact, stale_at, keep_s, ex, std::move(done));
-  }
-  void purge_tags(const std::vector<uint64_t>& hashes, Executor* ex, PurgeCallback done) override {
-    inner_->purge_tags(hashes, ex, std::move(done));
+  void purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+             PurgeCallback done) override {
+    inner_->purge(what, how, ex, std::move(done));
   }
   void list_objects(const ListQuery& q, Executor* ex, ListCallback done) override {
     inner_->list_objects(q, ex, std::move(done));
-  }
-  void soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t keep_s,
-                   Executor* ex, PurgeCallback done) override {
-    inner_->soften_tags(hashes, stale_at, keep_s, ex, std::move(done));
-  }
-  void purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) override {
-    inner_->purge_glob(pattern, ex, std::move(done));
-  }
-  void soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s, Executor* ex,
-                   PurgeCallback done) override {
-    inner_->soften_glob(pattern, stale_at, keep_s, ex, std::move(done));
   }
   void touch(const std::string& key, const Digest& d, uint32_t ttl_s, const uint32_t* flags,
              Executor* ex, TouchCallback done) override {

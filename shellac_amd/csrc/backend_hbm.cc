@@ -4,7 +4,7 @@
 // Replaces the reference's blocking memcached round trip inside the reactor
 // (src/python/shellac/server/Server.py:335 get, :432 set). This file is what the reactors
 // call: construction, routing (owners, hot replicas), the request API (get / set / del /
-// touch / purge_prefix / flush), drills and stats. A request ends up on its shard's queue,
+// touch / purge / flush), drills and stats. A request ends up on its shard's queue,
 // served by that GPU's batcher thread (hbm_batcher.cc), or for a small GET batch with the
 // calling reactor itself (hbm_direct.cc); hbm_hot.cc keeps the replicated hot set current.
 // hbm_backend_impl.h has the types they share, hbm_flight_plan.h the host-only decisions.
@@ -409,98 +409,34 @@ void HbmBackend::purge_finish(const std::shared_ptr<Purge>& p) {
   PostGroups::answer_now(p->ex, [cb = std::move(p->cb), n]() { cb(n); });
 }
 
-// Every shard scans its own index (a prefix has no owner, and the hot replicas live on all
+// Every shard scans its own index (a selector has no owner, and the hot replicas live on all
 // of them): a Purge request per shard in service, launched by its batcher on the shard's
-// stream behind the writes queued before it. A shard that is out of service, or fails the
-// purge, is marked so that its restore flushes it.
-void HbmBackend::purge_prefix(const std::string& prefix, Executor* ex, PurgeCallback done) {
-  Req proto;
-  proto.kind = ReqKind::Purge;
-  proto.d = Digest{0, 0};
-  proto.key = prefix;
-  purge_fan_out(proto, ex, std::move(done));
-}
-
-// A soft purge is a purge to this tier: the same request, fan-out, ordering, hot-replica and
-// restore handling; only the launch differs (Dev::launch_purges).
-void HbmBackend::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                               uint32_t keep_s, Executor* ex, PurgeCallback done) {
-  Req proto;
-  proto.kind = ReqKind::Purge;
-  proto.d = Digest{0, 0};
-  proto.key = pattern;
-  proto.soft = true;
-  proto.exact = exact;
-  proto.flags = stale_at;
-  proto.ttl = keep_s;
-  if (!pattern.empty() && pattern.size() <= kMaxKeyedKey)
+// stream behind the writes queued before it. A soft purge is the same request, fan-out,
+// ordering, hot-replica and restore handling; only the launch differs (Dev::launch_purges). A
+// shard that is out of service, or fails the purge, is marked so that its restore flushes it.
+void HbmBackend::purge(const KeyedSelector& what, const PurgeAction& how, Executor* ex,
+                       PurgeCallback done) {
+  using Kind = KeyedSelector::Kind;
+  if (purge_refused(what, how)) {
+    if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
+    return;
+  }
+  if (how.soft && (what.kind == Kind::Prefix || what.kind == Kind::Exact))
     soft_purges_.fetch_add(1, std::memory_order_relaxed);
-  purge_fan_out(proto, ex, std::move(done));
-}
-
-// A tag purge is the same request with a hash list in place of the pattern.
-void HbmBackend::purge_tags(const std::vector<uint64_t>& hashes, Executor* ex,
-                            PurgeCallback done) {
-  Req proto;
-  proto.kind = ReqKind::Purge;
-  proto.d = Digest{0, 0};
-  proto.tags = std::make_shared<const std::vector<uint64_t>>(hashes);
-  purge_fan_out(proto, ex, std::move(done));
-}
-
-void HbmBackend::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
-                             uint32_t keep_s, Executor* ex, PurgeCallback done) {
-  Req proto;
-  proto.kind = ReqKind::Purge;
-  proto.d = Digest{0, 0};
-  proto.tags = std::make_shared<const std::vector<uint64_t>>(hashes);
-  proto.soft = true;
-  proto.flags = stale_at;
-  proto.ttl = keep_s;
-  purge_fan_out(proto, ex, std::move(done));
-}
-
-// A glob purge is the same request with the compiled pattern: compiled here, once per call.
-void HbmBackend::purge_glob(const std::string& pattern, Executor* ex, PurgeCallback done) {
-  soften_or_purge_glob(pattern, false, 0, 0, ex, std::move(done));
-}
-
-void HbmBackend::soften_glob(const std::string& pattern, uint32_t stale_at, uint32_t keep_s,
-                             Executor* ex, PurgeCallback done) {
-  soften_or_purge_glob(pattern, true, stale_at, keep_s, ex, std::move(done));
-}
-
-void HbmBackend::soften_or_purge_glob(const std::string& pattern, bool soft, uint32_t stale_at,
-                                      uint32_t keep_s, Executor* ex, PurgeCallback done) {
-  auto g = std::make_shared<KeyedGlob>();
-  if (!compile_keyed_glob(pattern, g.get(), nullptr)) {
-    if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
-    return;
-  }
-  Req proto;
-  proto.kind = ReqKind::Purge;
-  proto.d = Digest{0, 0};
-  proto.glob = std::move(g);
-  proto.soft = soft;
-  proto.flags = stale_at;
-  proto.ttl = keep_s;
-  purge_fan_out(proto, ex, std::move(done));
-}
-
-void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback done) {
-  if (proto.glob ? false
-      : proto.tags ? proto.tags->empty() || proto.tags->size() > kMaxPurgeTags
-                   : proto.key.empty() || proto.key.size() > kMaxKeyedKey) {
-    if (done) PostGroups::answer_now(ex, [done]() { done(-1); });
-    return;
-  }
-  if (proto.tags) tag_purges_.fetch_add(1, std::memory_order_acq_rel);  // (before started)
-  if (proto.glob) glob_purges_.fetch_add(1, std::memory_order_acq_rel);
+  if (what.kind == Kind::Tags) tag_purges_.fetch_add(1, std::memory_order_acq_rel);  // (before
+  if (what.kind == Kind::Glob) glob_purges_.fetch_add(1, std::memory_order_acq_rel);  // started)
   purge_started_.fetch_add(1, std::memory_order_acq_rel);
   auto p = std::make_shared<Purge>();
   p->ex = ex;
   p->cb = std::move(done);
   p->left.store((int)devs_.size() + 1, std::memory_order_release);  // + this call's own hold
+  Req proto;
+  proto.kind = ReqKind::Purge;
+  proto.d = Digest{0, 0};
+  p->what = what;
+  proto.what = std::shared_ptr<const KeyedSelector>(p, &p->what);
+  proto.how = how;
+  proto.purge = p;
   const uint64_t up = up_mask_.load(std::memory_order_acquire);
   for (size_t k = 0; k < devs_.size(); ++k) {
     Dev* dv = devs_[k].get();
@@ -515,7 +451,6 @@ void HbmBackend::purge_fan_out(const Req& proto, Executor* ex, PurgeCallback don
       }
     }
     Req r = proto;
-    r.purge = p;
     r.ccb = [this, p, dv](bool ok) {
       if (!ok) dv->purge_dirty.store(true, std::memory_order_release);
       purge_finish(p);

@@ -97,14 +97,15 @@ std::shared_ptr<TouchWait> start_touch(CacheBackend* be, const std::string& key,
   return w;
 }
 
-// `call(cb)`: one purge_prefix / soften_prefix call answering through cb
-int64_t blocking_purge(const std::function<void(PurgeCallback)>& call) {
+// One CacheBackend::purge call, waited for: the Python methods purge_prefix, soften_prefix,
+// purge_tags, soften_tags, purge_glob and soften_glob are each a selector and an action here.
+int64_t blocking_purge(BackendHandle& h, const KeyedSelector& what, const PurgeAction& how) {
   std::mutex mu;
   std::condition_variable cv;
   bool done = false;
   int64_t removed = -1;
   py::gil_scoped_release nogil;
-  call([&](int64_t n) {
+  h.be->purge(what, how, &g_inline, [&](int64_t n) {
     std::lock_guard<std::mutex> lk(mu);
     removed = n;
     done = true;
@@ -113,6 +114,12 @@ int64_t blocking_purge(const std::function<void(PurgeCallback)>& call) {
   std::unique_lock<std::mutex> lk(mu);
   cv.wait(lk, [&] { return done; });
   return removed;
+}
+
+KeyedSelector tag_selector(const std::vector<std::string>& tags) {
+  std::vector<uint64_t> hs;
+  for (const std::string& t : tags) hs.push_back(tag_hash(t));
+  return KeyedSelector::tags(std::move(hs));
 }
 
 // Tests: one hot-set refresh with `call(hb, cb)` (a purge or a soft purge) queued in its
@@ -257,76 +264,47 @@ void bind_net(py::module_& m) {
       }, py::arg("key"), py::arg("value"), py::arg("flags") = 0, py::arg("ttl") = 0,
          py::arg("digest_of") = py::none())
       .def("delete", [](BackendHandle& h, py::bytes key) { return blocking_del(h.be.get(), key); })
-      // objects whose key starts with `prefix` removed (blocking); -1: the tier cannot scan
+      // objects removed (blocking); -1: the tier cannot scan, or refuses the pattern or the tags
       .def("purge_prefix", [](BackendHandle& h, py::bytes prefix) {
-        const std::string pre = prefix;
-        CacheBackend* be = h.be.get();
-        return blocking_purge(
-            [&](PurgeCallback cb) { be->purge_prefix(pre, &g_inline, std::move(cb)); });
+        return blocking_purge(h, KeyedSelector::prefix(prefix), PurgeAction::remove());
       }, py::arg("prefix"))
+      .def("purge_tags", [](BackendHandle& h, const std::vector<std::string>& tags) {
+        return blocking_purge(h, tag_selector(tags), PurgeAction::remove());
+      }, py::arg("tags"))
+      .def("purge_glob", [](BackendHandle& h, py::bytes pattern) {
+        return blocking_purge(h, KeyedSelector::glob(pattern), PurgeAction::remove());
+      }, py::arg("pattern"))
       // soft purge (blocking): live matching objects made stale at `stale_at` and, with keep_s,
-      // expiring at most keep_s seconds from now; -1: the tier cannot
+      // expiring at most keep_s seconds from now; -1 as above
       .def("soften_prefix", [](BackendHandle& h, py::bytes pattern, uint32_t stale_at,
                                uint32_t keep_s, bool exact) {
-        const std::string pat = pattern;
-        CacheBackend* be = h.be.get();
-        return blocking_purge([&](PurgeCallback cb) {
-          be->soften_prefix(pat, exact, stale_at, keep_s, &g_inline, std::move(cb));
-        });
+        return blocking_purge(h, exact ? KeyedSelector::exact(pattern)
+                                       : KeyedSelector::prefix(pattern),
+                              PurgeAction::soften(stale_at, keep_s));
       }, py::arg("pattern"), py::arg("stale_at"), py::arg("keep_s") = 0, py::arg("exact") = false)
-      // purge / soft purge by surrogate key (blocking): `tags` are the tag byte strings
-      .def("purge_tags", [](BackendHandle& h, const std::vector<std::string>& tags) {
-        std::vector<uint64_t> hs;
-        for (const std::string& t : tags) hs.push_back(tag_hash(t));
-        CacheBackend* be = h.be.get();
-        return blocking_purge(
-            [&](PurgeCallback cb) { be->purge_tags(hs, &g_inline, std::move(cb)); });
-      }, py::arg("tags"))
       .def("soften_tags", [](BackendHandle& h, const std::vector<std::string>& tags,
                              uint32_t stale_at, uint32_t keep_s) {
-        std::vector<uint64_t> hs;
-        for (const std::string& t : tags) hs.push_back(tag_hash(t));
-        CacheBackend* be = h.be.get();
-        return blocking_purge([&](PurgeCallback cb) {
-          be->soften_tags(hs, stale_at, keep_s, &g_inline, std::move(cb));
-        });
+        return blocking_purge(h, tag_selector(tags), PurgeAction::soften(stale_at, keep_s));
       }, py::arg("tags"), py::arg("stale_at"), py::arg("keep_s") = 0)
-      // purge / soft purge by glob (blocking): `pattern` as keyed.h's glob ('*' wildcards);
-      // -1: the tier cannot, or the pattern is refused
-      .def("purge_glob", [](BackendHandle& h, py::bytes pattern) {
-        const std::string pat = pattern;
-        CacheBackend* be = h.be.get();
-        return blocking_purge(
-            [&](PurgeCallback cb) { be->purge_glob(pat, &g_inline, std::move(cb)); });
-      }, py::arg("pattern"))
       .def("soften_glob", [](BackendHandle& h, py::bytes pattern, uint32_t stale_at,
                              uint32_t keep_s) {
-        const std::string pat = pattern;
-        CacheBackend* be = h.be.get();
-        return blocking_purge([&](PurgeCallback cb) {
-          be->soften_glob(pat, stale_at, keep_s, &g_inline, std::move(cb));
-        });
+        return blocking_purge(h, KeyedSelector::glob(pattern), PurgeAction::soften(stale_at, keep_s));
       }, py::arg("pattern"), py::arg("stale_at"), py::arg("keep_s") = 0)
       // inspection (blocking): prefix, key (exact), tags or glob, none of them: everything. None:
       // the tier cannot scan or refused the query; else a dict (next: None at the end)
       .def("list_objects", [](BackendHandle& h, py::object prefix, py::object key, py::object tags,
                               uint32_t limit, const std::string& after,
                               py::object glob) -> py::object {
-        ListQuery q;
-        q.limit = limit;
-        q.after = after;
-        if (!glob.is_none()) {
-          q.mode = kListGlob;
-          q.pattern = glob.cast<std::string>();
-          q.exact = !prefix.is_none() || !key.is_none() || !tags.is_none();  // (refused with them)
-        } else if (!prefix.is_none() || !key.is_none()) {
-          q.mode = kListPrefix;
-          q.exact = prefix.is_none();
-          q.pattern = (q.exact ? key : prefix).cast<std::string>();
+        ListQuery q{KeyedSelector(), limit, after};
+        if (!glob.is_none()) {  // (refused beside another selector)
+          if (!prefix.is_none() || !key.is_none() || !tags.is_none()) return py::none();
+          q.what = KeyedSelector::glob(glob.cast<std::string>());
+        } else if (!prefix.is_none()) {
+          q.what = KeyedSelector::prefix(prefix.cast<std::string>());
+        } else if (!key.is_none()) {
+          q.what = KeyedSelector::exact(key.cast<std::string>());
         } else if (!tags.is_none()) {
-          q.mode = kListTags;
-          for (const std::string& t : tags.cast<std::vector<std::string>>())
-            q.tags.push_back(tag_hash(t));
+          q.what = tag_selector(tags.cast<std::vector<std::string>>());
         }
         CacheBackend* be = h.be.get();
         ListResult res;
@@ -612,16 +590,16 @@ void bind_net(py::module_& m) {
   // Tests: hot_refresh_with a prefix purge / a soft prefix purge; returns (the refresh's
   // counts, objects the purge removed / softened).
   m.def("hot_refresh_purging", [](BackendHandle& h, py::bytes prefix) {
-    const std::string pre = prefix;
-    return hot_refresh_with(h, [pre](HbmBackend* hb, PurgeCallback cb) {
-      hb->purge_prefix(pre, nullptr, std::move(cb));
+    const KeyedSelector what = KeyedSelector::prefix(prefix);
+    return hot_refresh_with(h, [what](HbmBackend* hb, PurgeCallback cb) {
+      hb->purge(what, PurgeAction::remove(), nullptr, std::move(cb));
     });
   }, py::arg("backend"), py::arg("prefix"));
   m.def("hot_refresh_softening", [](BackendHandle& h, py::bytes prefix, uint32_t stale_at,
                                     uint32_t keep_s) {
-    const std::string pre = prefix;
-    return hot_refresh_with(h, [pre, stale_at, keep_s](HbmBackend* hb, PurgeCallback cb) {
-      hb->soften_prefix(pre, false, stale_at, keep_s, nullptr, std::move(cb));
+    const KeyedSelector what = KeyedSelector::prefix(prefix);
+    return hot_refresh_with(h, [what, stale_at, keep_s](HbmBackend* hb, PurgeCallback cb) {
+      hb->purge(what, PurgeAction::soften(stale_at, keep_s), nullptr, std::move(cb));
     });
   }, py::arg("backend"), py::arg("prefix"), py::arg("stale_at"), py::arg("keep_s") = 0);
   m.def("inject_shard_down", [](BackendHandle& h, int shard, bool down) {

@@ -450,21 +450,22 @@ void HbmBackend::Dev::launch_fills(Flight& f) {
   }
 }
 
-// Prefix purges: after the SETs and DELETEs queued before them (a purge is its flight's last
-// request); pattern image and result words in mapped memory
+// A selector's device image (selector.h) staged at byte `off` of the mapped buffer `m`; the
+// device address of what was written.
+static const uint8_t* stage_image(const KeyedSelector& what, Mapped& m, size_t off) {
+  what.write_image(m.host<uint8_t>() + off);
+  return m.dev<uint8_t>() + off;
+}
+
+// Purges: after the SETs and DELETEs queued before them (a purge is its flight's last
+// request); selector images and result words in mapped memory
 void HbmBackend::Dev::launch_purges(Flight& f) {
-  // a request's bytes in purge_img: the pattern image, the compiled glob's bytes in use, or
-  // the tag list (kept 16-B aligned)
-  const auto img_size = [](const Req& r) {
-    return r.glob ? (size_t)keyed_glob_used_bytes(*r.glob)
-           : r.tags ? (r.tags->size() * sizeof(uint64_t) + 15) & ~(size_t)15
-                    : keyed_prefix_image_bytes(r.key.size());
-  };
+  using Kind = KeyedSelector::Kind;
   size_t np = 0, img_bytes = 0;
   for (uint32_t i : f.ctls)
     if (f.reqs[i].kind == ReqKind::Purge) {
       ++np;
-      img_bytes += img_size(f.reqs[i]);
+      img_bytes += f.reqs[i].what->image_bytes();
     }
   if (!np) return;
   f.purge_img.ensure(img_bytes);
@@ -473,72 +474,67 @@ void HbmBackend::Dev::launch_purges(Flight& f) {
   for (uint32_t i : f.ctls) {
     const Req& r = f.reqs[i];
     if (r.kind != ReqKind::Purge) continue;
+    const KeyedSelector& w = *r.what;
+    const PurgeAction& a = r.how;
     uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * j;
     res[0] = res[1] = 0;
     uint64_t* const out = f.purge_out.dev<uint64_t>() + 2 * j;
-    const uint32_t cap = r.ttl ? f.tnow + r.ttl : 0;  // (soft: flags is stale_at, ttl keep_s)
-    if (r.glob) {
-      const uint32_t nb = keyed_glob_used_bytes(*r.glob);
-      std::memcpy(f.purge_img.host<uint8_t>() + off, r.glob.get(), nb);
-      const uint8_t* const img = f.purge_img.dev<uint8_t>() + off;
-      if (r.soft) cache->soften_keyed_glob(img, nb, r.flags, cap, f.tnow, out, stream);
-      else cache->remove_keyed_glob(img, nb, f.tnow, out, stream);
-    } else if (r.tags) {
-      const uint32_t nt = (uint32_t)r.tags->size();
-      std::memcpy(f.purge_img.host<uint8_t>() + off, r.tags->data(), nt * sizeof(uint64_t));
-      const uint64_t* const list =
-          reinterpret_cast<const uint64_t*>(f.purge_img.dev<uint8_t>() + off);
-      if (r.soft) cache->soften_keyed_tags(list, nt, r.flags, cap, f.tnow, out, stream);
-      else cache->remove_keyed_tags(list, nt, f.tnow, out, stream);
-    } else {
-      write_keyed_prefix_image(f.purge_img.host<uint8_t>() + off,
-                               reinterpret_cast<const uint8_t*>(r.key.data()), r.key.size());
-      if (r.soft)  // (the flight's SET chains are whole ones)
-        cache->soften_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
-                                   r.exact, r.flags, cap, f.tnow, out, stream);
-      else
-        cache->remove_keyed_prefix(f.purge_img.dev<uint8_t>() + off, (uint32_t)r.key.size(),
-                                   f.tnow, out, stream);
+    const uint32_t cap = a.keep_s ? f.tnow + a.keep_s : 0;
+    const uint8_t* const img = stage_image(w, f.purge_img, off);
+    const uint32_t nb = (uint32_t)w.image_bytes(), plen = (uint32_t)w.pattern.size();
+    switch (w.kind) {
+      case Kind::Glob:
+        if (a.soft) cache->soften_keyed_glob(img, nb, a.stale_at, cap, f.tnow, out, stream);
+        else cache->remove_keyed_glob(img, nb, f.tnow, out, stream);
+        break;
+      case Kind::Tags: {
+        const uint64_t* const list = reinterpret_cast<const uint64_t*>(img);
+        const uint32_t nt = (uint32_t)w.hashes.size();
+        if (a.soft) cache->soften_keyed_tags(list, nt, a.stale_at, cap, f.tnow, out, stream);
+        else cache->remove_keyed_tags(list, nt, f.tnow, out, stream);
+        break;
+      }
+      default:  // Prefix, and a soft Exact (purge_refused: no other kind gets here)
+        if (a.soft)  // (the flight's SET chains are whole ones)
+          cache->soften_keyed_prefix(img, plen, w.kind == Kind::Exact, a.stale_at, cap, f.tnow,
+                                     out, stream);
+        else cache->remove_keyed_prefix(img, plen, f.tnow, out, stream);
     }
-    off += img_size(r);
+    off += nb;
     ++j;
   }
 }
 
-// A list (HbmBackend::list_step): after the flight's writes, as a purge; the query's image or
-// tag list, the result words, the rows and the key areas in one mapped buffer. It writes
+// A list (HbmBackend::list_step): after the flight's writes, as a purge; the selector's image,
+// the result words, the rows and the key areas in one mapped buffer. It writes
 // nothing in the cache, so neither the filter nor `touched` nor purge_dirty hears of it.
 constexpr uint32_t kListBackendKeyCap = 256;  // keys up to 254 bytes come back whole
 
 void HbmBackend::Dev::launch_lists(Flight& f) {
+  using Kind = KeyedSelector::Kind;
   for (uint32_t i : f.ctls) {
     const Req& r = f.reqs[i];
     if (r.kind != ReqKind::List) continue;
-    const ListQuery& q = r.list->q;
+    const KeyedSelector& w = r.list->q.what;
     const uint32_t limit = r.flags;
-    KeyedGlob glob;
-    if (q.mode == kListGlob) compile_keyed_glob(q.pattern, &glob, nullptr);  // (valid: list_objects)
-    const size_t img = q.mode == kListPrefix ? keyed_prefix_image_bytes(q.pattern.size())
-                       : q.mode == kListGlob ? (size_t)keyed_glob_used_bytes(glob)
-                                             : (q.tags.size() * sizeof(uint64_t) + 15) & ~(size_t)15;
+    const size_t img = w.image_bytes();
     f.list_out_off = img;
     f.list_rows_off = img + 32;
     f.list_keys_off = f.list_rows_off + (size_t)limit * sizeof(ListRow);
     f.list_buf.ensure(f.list_keys_off + (size_t)limit * kListBackendKeyCap + 16);
     uint8_t* const h = f.list_buf.host<uint8_t>();
     uint8_t* const d = f.list_buf.dev<uint8_t>();
-    if (q.mode == kListPrefix)
-      write_keyed_prefix_image(h, reinterpret_cast<const uint8_t*>(q.pattern.data()),
-                               q.pattern.size());
-    else if (q.mode == kListTags)
-      std::memcpy(h, q.tags.data(), q.tags.size() * sizeof(uint64_t));
-    else if (q.mode == kListGlob)
-      std::memcpy(h, &glob, img);
+    stage_image(w, f.list_buf, 0);
     std::memset(h + f.list_out_off, 0, 32);
-    cache->list_keyed(q.mode, d, q.mode == kListGlob ? (uint32_t)img : (uint32_t)q.pattern.size(),
-                      q.exact,
-                      reinterpret_cast<const uint64_t*>(d), (uint32_t)q.tags.size(), r.list_start,
-                      limit, kListBackendKeyCap, f.tnow,
+    uint32_t plen = 0;  // the engine's `plen`: the pattern's bytes, or the glob image's in use
+    switch (w.kind) {
+      case Kind::Glob: plen = (uint32_t)img; break;
+      case Kind::Prefix: case Kind::Exact: plen = (uint32_t)w.pattern.size(); break;
+      default: break;
+    }
+    cache->list_keyed(w.list_mode(), d, plen, w.kind == Kind::Exact,
+                      reinterpret_cast<const uint64_t*>(d), (uint32_t)w.hashes.size(),
+                      r.list_start, limit, kListBackendKeyCap, f.tnow,
                       reinterpret_cast<ListRow*>(d + f.list_rows_off), d + f.list_keys_off,
                       reinterpret_cast<uint64_t*>(d + f.list_out_off), stream);
     return;
@@ -653,15 +649,21 @@ void HbmBackend::Dev::finish_ctls(Flight& f) {
     Req& r = f.reqs[i];
     if (r.kind == ReqKind::Purge) {
       const uint64_t* const res = f.purge_out.host<uint64_t>() + 2 * pj++;
-      if (r.glob) {
-        (r.soft ? glob_softened_objects : glob_purged_objects) += res[0];
-      } else if (r.tags) {
-        (r.soft ? tag_softened_objects : tag_purged_objects) += res[0];
-      } else if (r.soft) {
-        softened_objects += res[0];
-      } else {
-        purged_objects += res[0];
-        purged_bytes += res[1];
+      const bool soft = r.how.soft;
+      switch (r.what->kind) {
+        case KeyedSelector::Kind::Glob:
+          (soft ? glob_softened_objects : glob_purged_objects) += res[0];
+          break;
+        case KeyedSelector::Kind::Tags:
+          (soft ? tag_softened_objects : tag_purged_objects) += res[0];
+          break;
+        default:
+          if (soft) {
+            softened_objects += res[0];
+          } else {
+            purged_objects += res[0];
+            purged_bytes += res[1];
+          }
       }
       if (r.purge) r.purge->removed.fetch_add((int64_t)res[0], std::memory_order_relaxed);
     }

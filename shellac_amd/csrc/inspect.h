@@ -12,18 +12,18 @@
 #include <vector>
 
 #include "keyed.h"
+#include "selector.h"
 
 namespace shellac {
 
 struct ListQuery {
-  uint32_t mode = kListAll;    // kListPrefix (pattern, exact), kListTags (tags), kListGlob
-                               // (pattern: a glob, keyed.h) or kListAll
-  std::string pattern;
-  bool exact = false;
-  std::vector<uint64_t> tags;  // tag hashes, 1..kMaxPurgeTags
-  uint32_t limit = 100;        // objects wanted, <= kMaxListRows; 0: count only
-  std::string after;           // the `next` of the page before; empty: from the start
+  KeyedSelector what;     // which objects (selector.h); the default: all of them
+  uint32_t limit = 100;   // objects wanted, <= kMaxListRows; 0: count only
+  std::string after;      // the `next` of the page before; empty: from the start
 };
+inline bool list_query_valid(const ListQuery& q) {
+  return q.what.valid() && q.limit <= kMaxListRows;
+}
 
 struct ListedObject {
   std::string key;
@@ -44,33 +44,6 @@ struct ListResult {
   std::string next;         // empty: nothing follows
   uint32_t shards_skipped = 0;
 };
-
-// Whether a stored keyed value [u16 klen | key | payload] matches the query (the matcher of
-// HostCache::list_keyed, for tiers that hold whole values). kListGlob: `glob` is q.pattern
-// compiled (once per walk, by the caller); without it nothing matches.
-inline bool keyed_value_listed(const uint8_t* v, size_t n, const ListQuery& q,
-                               const KeyedGlob* glob = nullptr) {
-  if (n < kKeyedPrefix) return false;
-  uint16_t kl;
-  std::memcpy(&kl, v, kKeyedPrefix);
-  if (kKeyedPrefix + kl > n) return false;
-  if (q.mode == kListGlob) return glob && keyed_glob_matches(*glob, v + kKeyedPrefix, kl);
-  if (q.mode == kListTags) return keyed_tags_match(v, n, q.tags.data(), q.tags.size());
-  if (q.mode == kListAll) return kl != 0;
-  if (q.exact ? kl != q.pattern.size() : kl < q.pattern.size()) return false;
-  return std::memcmp(v + kKeyedPrefix, q.pattern.data(), q.pattern.size()) == 0;
-}
-
-inline bool list_query_valid(const ListQuery& q) {
-  if (q.limit > kMaxListRows) return false;
-  if (q.mode == kListPrefix) return !q.pattern.empty() && q.pattern.size() <= kMaxKeyedKey;
-  if (q.mode == kListTags) return !q.tags.empty() && q.tags.size() <= kMaxPurgeTags;
-  if (q.mode == kListGlob) {  // (the pattern is checked by compiling it)
-    KeyedGlob g;
-    return !q.exact && compile_keyed_glob(q.pattern, &g, nullptr);
-  }
-  return q.mode == kListAll;
-}
 
 // ---- the HTTP surface ---------------------------------------------------------------------
 // Percent-decodes once ("%2F" -> "/", "%252F" -> "%2F"; '+' stays '+'). False on a '%' that

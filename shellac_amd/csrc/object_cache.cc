@@ -219,85 +219,62 @@ bool ObjectCache::touch(const std::string& key, const Digest& d, uint32_t expire
   return true;
 }
 
-uint64_t ObjectCache::purge_prefix(const std::string& prefix, uint32_t now) {
-  uint64_t removed = 0;
+template <typename Visit>
+void ObjectCache::for_each_selected(const KeyedSelector& what, uint32_t now, Visit&& visit) {
   for (auto& sp : stripes_) {
     Stripe& s = *sp;
     std::vector<std::shared_ptr<const std::string>> dead;  // freed outside the stripe lock
     std::lock_guard<std::mutex> lk(s.mu);
     for (size_t id = 0; id < s.slots.size(); ++id) {
-      const Obj& o = s.slots[id];
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      if (v.size() < kKeyedPrefix + prefix.size()) continue;
-      uint16_t kl;
-      std::memcpy(&kl, v.data(), kKeyedPrefix);
-      if (kl < prefix.size() || v.size() < kKeyedPrefix + kl) continue;
-      if (std::memcmp(v.data() + kKeyedPrefix, prefix.data(), prefix.size()) != 0) continue;
-      if (int32_t* pos = find(s, o.d)) {
-        erase_slot(s, pos, &dead);
-        ++removed;
-      }
-    }
-  }
-  return removed;
-}
-
-uint64_t ObjectCache::soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                                    uint32_t expire_cap, uint32_t now) {
-  uint64_t softened = 0;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (size_t id = 0; id < s.slots.size(); ++id) {
       Obj& o = s.slots[id];
       if (!o.data || (o.expire && o.expire <= now)) continue;
       const std::string& v = *o.data;
-      if (v.size() < kKeyedPrefix + pattern.size()) continue;
-      uint16_t kl;
-      std::memcpy(&kl, v.data(), kKeyedPrefix);
-      if ((exact ? kl != pattern.size() : kl < pattern.size()) || v.size() < kKeyedPrefix + kl)
-        continue;
-      if (std::memcmp(v.data() + kKeyedPrefix, pattern.data(), pattern.size()) != 0) continue;
-      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
-      o.flags = stale_at;
-      ++softened;
+      if (what.matches_value(reinterpret_cast<const uint8_t*>(v.data()), v.size()))
+        visit(s, o, &dead);
     }
   }
-  return softened;
+}
+
+uint64_t ObjectCache::purge(const KeyedSelector& what, bool soft, uint32_t stale_at,
+                            uint32_t expire_cap, uint32_t now) {
+  uint64_t n = 0;
+  for_each_selected(what, now, [&](Stripe& s, Obj& o, auto* dead) {
+    if (soft) {
+      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
+      o.flags = stale_at;
+    } else {
+      int32_t* pos = find(s, o.d);
+      if (!pos) return;
+      erase_slot(s, pos, dead);
+    }
+    ++n;
+  });
+  return n;
 }
 
 ListResult ObjectCache::list(const ListQuery& q, uint32_t now) {
   ListResult res;
   if (!list_query_valid(q)) return res;
-  KeyedGlob glob;
-  if (q.mode == kListGlob) compile_keyed_glob(q.pattern, &glob, nullptr);
   res.ok = true;
   std::vector<ListedObject> all;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (const Obj& o : s.slots) {
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data());
-      if (!keyed_value_listed(b, v.size(), q, &glob)) continue;
-      ++res.matched;
-      res.bytes += v.size();
-      uint16_t kl;
-      std::memcpy(&kl, b, kKeyedPrefix);
-      ListedObject lo;
-      lo.key.assign(v.data() + kKeyedPrefix, kl);
-      if (!q.limit || (!q.after.empty() && lo.key <= q.after)) continue;
-      lo.size = (uint32_t)v.size();
-      lo.ttl = o.expire ? (int64_t)o.expire - now : -1;
-      lo.flags = o.flags;
-      const uint32_t nt = keyed_ntags(b, v.size());
-      lo.ntags = nt == kTagOverflow ? -1 : (int)nt;
-      lo.referenced = o.ref;
-      all.push_back(std::move(lo));
-    }
-  }
+  for_each_selected(q.what, now, [&](Stripe&, Obj& o, auto*) {
+    const std::string& v = *o.data;
+    const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data());
+    ++res.matched;
+    res.bytes += v.size();
+    uint16_t kl;
+    std::memcpy(&kl, b, kKeyedPrefix);
+    ListedObject lo;
+    lo.key.assign(v.data() + kKeyedPrefix, kl);
+    if (!q.limit || (!q.after.empty() && lo.key <= q.after)) return;
+    lo.size = (uint32_t)v.size();
+    lo.ttl = o.expire ? (int64_t)o.expire - now : -1;
+    lo.flags = o.flags;
+    const uint32_t nt = keyed_ntags(b, v.size());
+    lo.ntags = nt == kTagOverflow ? -1 : (int)nt;
+    lo.referenced = o.ref;
+    all.push_back(std::move(lo));
+  });
   std::sort(all.begin(), all.end(),
             [](const ListedObject& a, const ListedObject& b) { return a.key < b.key; });
   if (all.size() > q.limit) {
@@ -306,90 +283,6 @@ ListResult ObjectCache::list(const ListQuery& q, uint32_t now) {
   }
   res.objects = std::move(all);
   return res;
-}
-
-uint64_t ObjectCache::purge_tags(const std::vector<uint64_t>& hashes, uint32_t now) {
-  uint64_t removed = 0;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::vector<std::shared_ptr<const std::string>> dead;  // freed outside the stripe lock
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (size_t id = 0; id < s.slots.size(); ++id) {
-      const Obj& o = s.slots[id];
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      if (!keyed_tags_match(reinterpret_cast<const uint8_t*>(v.data()), v.size(), hashes.data(),
-                            hashes.size()))
-        continue;
-      if (int32_t* pos = find(s, o.d)) {
-        erase_slot(s, pos, &dead);
-        ++removed;
-      }
-    }
-  }
-  return removed;
-}
-
-uint64_t ObjectCache::soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at,
-                                  uint32_t expire_cap, uint32_t now) {
-  uint64_t softened = 0;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (size_t id = 0; id < s.slots.size(); ++id) {
-      Obj& o = s.slots[id];
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      if (!keyed_tags_match(reinterpret_cast<const uint8_t*>(v.data()), v.size(), hashes.data(),
-                            hashes.size()))
-        continue;
-      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
-      o.flags = stale_at;
-      ++softened;
-    }
-  }
-  return softened;
-}
-
-uint64_t ObjectCache::purge_glob(const KeyedGlob& g, uint32_t now) {
-  uint64_t removed = 0;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::vector<std::shared_ptr<const std::string>> dead;  // freed outside the stripe lock
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (size_t id = 0; id < s.slots.size(); ++id) {
-      const Obj& o = s.slots[id];
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      if (!keyed_value_glob_matches(g, reinterpret_cast<const uint8_t*>(v.data()), v.size()))
-        continue;
-      if (int32_t* pos = find(s, o.d)) {
-        erase_slot(s, pos, &dead);
-        ++removed;
-      }
-    }
-  }
-  return removed;
-}
-
-uint64_t ObjectCache::soften_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap,
-                                  uint32_t now) {
-  uint64_t softened = 0;
-  for (auto& sp : stripes_) {
-    Stripe& s = *sp;
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (size_t id = 0; id < s.slots.size(); ++id) {
-      Obj& o = s.slots[id];
-      if (!o.data || (o.expire && o.expire <= now)) continue;
-      const std::string& v = *o.data;
-      if (!keyed_value_glob_matches(g, reinterpret_cast<const uint8_t*>(v.data()), v.size()))
-        continue;
-      if (expire_cap && (o.expire == 0 || o.expire > expire_cap)) o.expire = expire_cap;
-      o.flags = stale_at;
-      ++softened;
-    }
-  }
-  return softened;
 }
 
 void ObjectCache::clear() {

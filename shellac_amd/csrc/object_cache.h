@@ -48,24 +48,13 @@ class ObjectCache {
   // (absent, expired, or another key's object under a colliding digest: left alone).
   bool touch(const std::string& key, const Digest& d, uint32_t expire, const uint32_t* flags,
              uint32_t now);
-  // Drops every live object whose stored key starts with `prefix` (a walk of every stripe
-  // under its lock); returns how many.
-  uint64_t purge_prefix(const std::string& prefix, uint32_t now);
-  // Soft purge, in place under each stripe's lock (as touch): every live object whose stored
-  // key starts with `pattern` (`exact`: equals it) gets flags = stale_at and, where
-  // expire_cap != 0 and the object never expires or expires after it, expire = expire_cap.
-  // Returns the live matching objects, whether or not their words changed.
-  uint64_t soften_prefix(const std::string& pattern, bool exact, uint32_t stale_at,
-                         uint32_t expire_cap, uint32_t now);
-  // Purge / soft purge by surrogate key: the same walks with the tag matcher of keyed.h
-  // (keyed_tags_match) on the stored value; `hashes` holds 1..kMaxPurgeTags tag hashes.
-  uint64_t purge_tags(const std::vector<uint64_t>& hashes, uint32_t now);
-  uint64_t soften_tags(const std::vector<uint64_t>& hashes, uint32_t stale_at, uint32_t expire_cap,
-                       uint32_t now);
-  // Purge / soft purge by glob: the same walks with keyed_value_glob_matches on the compiled
-  // pattern (keyed.h: the key up to its first 0x1f, '*' wildcards, anchored at both ends).
-  uint64_t purge_glob(const KeyedGlob& g, uint32_t now);
-  uint64_t soften_glob(const KeyedGlob& g, uint32_t stale_at, uint32_t expire_cap, uint32_t now);
+  // Invalidation (selector.h): a walk of every stripe under its lock over the live objects
+  // `what` selects; returns how many. Hard: they are dropped (their bytes freed outside the
+  // lock). Soft, in place as touch(): flags = stale_at and, where expire_cap != 0 and the
+  // object never expires or expires after it, expire = expire_cap; the count is of the live
+  // matches, whether or not their words changed. `what` must be valid().
+  uint64_t purge(const KeyedSelector& what, bool soft, uint32_t stale_at, uint32_t expire_cap,
+                 uint32_t now);
   // Inspection (CacheBackend::list_objects): the live objects the query matches are collected
   // under each stripe's lock and sorted by key bytes; the cursor is "after this key" (q.after:
   // the last key of the page before; a truncated key is never handed out). ttl is left from
@@ -97,6 +86,10 @@ class ObjectCache {
   static void rehash(Stripe& s, size_t cap);
   void erase_slot(Stripe& s, int32_t* pos, std::vector<std::shared_ptr<const std::string>>* dead);
   void evict(Stripe& s, std::vector<std::shared_ptr<const std::string>>* dead);
+  // The one walk of purge() and list(): visit(stripe, object) for every live object `what`
+  // selects, under the stripe's lock; what `visit` puts into `dead` is freed outside it.
+  template <typename Visit>
+  void for_each_selected(const KeyedSelector& what, uint32_t now, Visit&& visit);
 
   uint64_t cap_per_stripe_;
   uint32_t max_item_;

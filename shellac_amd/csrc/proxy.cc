@@ -295,6 +295,85 @@ struct Upstream : Conn {
   bool stream_chunked = false;  // ... re-framed as chunked (unknown length)
 };
 
+// The distinct tags of a tag header's value: split on space, tab and comma, empty tokens
+// dropped, duplicates collapsed; as hashes (keyed.h tag_hash), in order of first appearance.
+static std::vector<uint64_t> tag_hashes_of(const std::string& value) {
+  std::vector<uint64_t> out;
+  size_t pos = 0;
+  while (pos < value.size()) {
+    const size_t e = std::min(value.find_first_of(" \t,", pos), value.size());
+    if (e > pos) {
+      const uint64_t h = tag_hash(value.data() + pos, e - pos);
+      if (std::find(out.begin(), out.end(), h) == out.end()) out.push_back(h);
+    }
+    pos = e + 1;
+  }
+  return out;
+}
+
+// The 400 body of a tag list no selector can be made of.
+static std::string bad_tags(bool no_header, const KeyedSelector& what) {
+  return std::string("{\"mode\":\"tag\",\"error\":\"") +
+         (no_header              ? "no tag header is configured"
+          : what.hashes.empty() ? "the request names no tags"
+                                : "more than 64 tags") + "\"}";
+}
+static std::string bad_glob(const std::string& why) {
+  return "{\"mode\":\"glob\",\"error\":\"" + why + "\"}";
+}
+
+// What a PURGE asks. X-Purge-Mode (any case) names the mode: none or an unknown one is exact.
+//   exact : the object of the request's key, then `variants`, its Vary variants;
+//   prefix: every object whose key starts with the request's key;
+//   tag   : every object that carries one of the 1..64 tags in the request's header named by
+//           ProxyConfig::tag_header (the URL is ignored);
+//   glob  : the request's key (Host + URL with key_host, else the URL) is the pattern, '*' the
+//           wildcard: every '\\' is escaped before compiling, so every other byte of the URL is
+//           literal, a '?' before a query string included. An object is selected when its
+//           key, up to the first '\x1f', matches (keyed.h), a Vary marker with its variants.
+struct PurgeRequest {
+  KeyedSelector what, variants;
+  bool soft = false, dry_run = false;  // (a dry run ignores `soft`: nothing changes either way)
+  bool exact() const { return what.kind == KeyedSelector::Kind::Exact; }
+  bool by_tag() const { return what.kind == KeyedSelector::Kind::Tags; }
+  // how an answer begins, and its "tags" field (tag mode only)
+  std::string head() const {
+    using Kind = KeyedSelector::Kind;
+    return std::string("{\"mode\":\"") + (what.kind == Kind::Prefix ? "prefix" : by_tag() ? "tag"
+                                          : what.kind == Kind::Glob ? "glob" : "exact") + "\",";
+  }
+  std::string tags_field() const {
+    return by_tag() ? "\"tags\":" + std::to_string(what.hashes.size()) + "," : std::string();
+  }
+};
+
+// The request's headers and key into *rq; *bad: not empty: the request is a 400 with this body
+// (a tag list or a glob no selector can be made of). An empty key makes a refused prefix or exact
+// selector that goes on to the tier, which answers "cannot".
+static void parse_purge(const HttpParser& q, const std::string& key, const ProxyConfig& cfg,
+                        PurgeRequest* rq, std::string* bad) {
+  const std::string* h = q.header("x-purge-mode");
+  const std::string mode = h ? to_lower(*h) : std::string();
+  h = q.header("x-purge-soft");
+  rq->soft = h && *h == "1";
+  h = q.header("x-purge-dry-run");
+  rq->dry_run = h && *h == "1";
+  if (mode == "tag") {
+    const std::string* list = cfg.tag_header.empty() ? nullptr : q.header(cfg.tag_header);
+    rq->what = KeyedSelector::tags(list ? tag_hashes_of(*list) : std::vector<uint64_t>());
+    if (!rq->what.valid()) *bad = bad_tags(cfg.tag_header.empty(), rq->what);
+  } else if (mode == "glob") {
+    std::string why;
+    rq->what = KeyedSelector::glob(keyed_glob_escape(key, true), &why);
+    if (!rq->what.valid()) *bad = bad_glob(why);
+  } else if (mode == "prefix") {
+    rq->what = KeyedSelector::prefix(key);
+  } else {
+    rq->what = KeyedSelector::exact(key);
+    rq->variants = KeyedSelector::prefix(key + '\x1f');
+  }
+}
+
 class Reactor : public Executor {
  public:
   Reactor(Proxy* px, int id, int listen_fd);
@@ -346,18 +425,14 @@ class Reactor : public Executor {
   void on_client(Client* c, uint32_t ev);
   void on_upstream(Upstream* u, uint32_t ev);
   void on_request(Client* c);
-  void on_purge(Client* c, Slot* s, const std::string& key, bool prefix, bool soft);
-  void hard_purge(uint64_t cid, uint64_t seq, const std::string& key, bool prefix,
-                  bool soft_asked);
-  void on_purge_tags(Client* c, Slot* s, const std::string* list, bool soft);
-  void hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes, bool soft_asked);
-  void on_purge_glob(Client* c, Slot* s, const std::string& key, bool soft);
-  void hard_purge_glob(uint64_t cid, uint64_t seq, const std::string& pattern, bool soft_asked);
+  void on_purge(Client* c, Slot* s, const HttpParser& q, const std::string& key);
+  using PurgeRef = std::shared_ptr<const PurgeRequest>;
+  void hard_purge(uint64_t cid, uint64_t seq, const PurgeRef& rq, bool soft_asked);
+  void soft_purge(uint64_t cid, uint64_t seq, const PurgeRef& rq);
+  void dry_purge(uint64_t cid, uint64_t seq, const PurgeRef& rq);
   void answer_purge(uint64_t cid, uint64_t seq, int code, const char* reason,
                     const std::string& body);
   void on_inspect(Client* c, Slot* s, const std::string& qs);
-  void on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
-                        const std::string* list);
   void on_cache(uint64_t cid, uint64_t seq, bool hit, CacheValue v);
   void ask_part(Slot* s, uint64_t cid);
   void on_part(uint64_t cid, uint64_t seq, PartValue p);
@@ -724,28 +799,8 @@ void Reactor::on_request(Client* c) {
   if (method == "PURGE" && cfg_.purge != "off") {
     const std::string* host = q.header("host");
     const std::string key = cfg_.key_host && host ? *host + url : url;  // as a GET's
-    const std::string* mode = q.header("x-purge-mode");
-    const bool prefix = mode && to_lower(*mode) == "prefix";
-    const std::string* soft = q.header("x-purge-soft");
-    const std::string* dry = q.header("x-purge-dry-run");
     c->slots.push_back(std::move(s));
-    const bool glob = mode && to_lower(*mode) == "glob";
-    if (dry && *dry == "1") {  // (X-Purge-Soft is ignored: nothing is changed either way)
-      const bool tag = mode && to_lower(*mode) == "tag";
-      on_purge_dry_run(c, sp, key, glob ? 3 : tag ? 2 : prefix ? 1 : 0,
-                       tag && !cfg_.tag_header.empty() ? q.header(cfg_.tag_header) : nullptr);
-      return;
-    }
-    if (mode && to_lower(*mode) == "tag") {
-      const std::string* list = cfg_.tag_header.empty() ? nullptr : q.header(cfg_.tag_header);
-      on_purge_tags(c, sp, list, soft && *soft == "1");
-      return;
-    }
-    if (glob) {
-      on_purge_glob(c, sp, key, soft && *soft == "1");
-      return;
-    }
-    on_purge(c, sp, key, prefix, soft && *soft == "1");
+    on_purge(c, sp, q, key);
     return;
   }
   s->head = method == "HEAD";
@@ -817,314 +872,132 @@ void Reactor::on_request(Client* c) {
 }
 
 // PURGE (ProxyConfig::purge): the request holds its slot like any other (pipelined order is
-// kept) and is answered when the backend's callbacks arrive.
-//   exact : the URL's object (for a URL whose responses Vary, the marker) and every variant
-//           — the variants live under vary_key(base, ...) = base + '\x1f' + ..., and
-//           deleting only the marker would make them reachable again once a new marker is
-//           stored;
-//   prefix: every object whose key starts with the URL's key.
-// X-Purge-Soft: 1 (with --grace): the same objects are kept and made stale now
-// (CacheBackend::soften_prefix: freshness time = now, life capped at now + grace), so the next
-// request is answered from the stale copy and revalidated in the background. note_purge is
-// called all the same: a fill or a revalidation that left before the soft purge must not make
-// the object fresh again (purged_since drops it; the object stays stale and the next hit
-// revalidates). Exact mode is two scans, the key itself and its variants; a Vary marker at
-// the base key is softened like any object (a marker's freshness is never tested). Without
-// --grace, or where the tier answers -1, the request is carried out as a hard purge and
-// answered with "soft":false.
-void Reactor::on_purge(Client* c, Slot* s, const std::string& key, bool prefix, bool soft) {
+// kept) and is answered when the backend's callbacks arrive. One pipeline for every mode
+// (PurgeRequest): the loopback rule (403), the request counters, what parse_purge refused
+// (400), "no cache" (501), then
+//   dry run (X-Purge-Dry-Run: 1): what the purge would hit, from the count-only list
+//           (CacheBackend::list_objects with limit 0); nothing is removed or softened and
+//           note_purge is not called, so a fill in flight is still stored;
+//   soft    (X-Purge-Soft: 1 with --grace): the objects are kept and made stale now
+//           (PurgeAction::soften: freshness time = now, life capped at now + grace), so the
+//           next request is answered from the stale copy and revalidated in the background;
+//   hard    otherwise, and where the tier answers a soft purge with -1: the objects are
+//           removed, and a request that asked for a soft purge is told "soft":false.
+// note_purge is called before the tier is touched, for a soft purge too: a fill or a
+// revalidation that left before it must not store the object, or make it fresh again
+// (purged_since drops it; a softened object stays stale and the next hit revalidates).
+// Exact mode is two steps: the URL's object (for a URL whose responses Vary, the marker: a
+// delete, or a soft scan), then its variants, which live under vary_key(base, ...) = base +
+// '\x1f' + ...; deleting only the marker would make them reachable again once a new marker is
+// stored. A tier that cannot scan answers 501, exact mode `"variants":-1`.
+void Reactor::on_purge(Client* c, Slot* s, const HttpParser& q, const std::string& key) {
   const uint64_t cid = c->id, seq = s->seq;
   if (!purge_allowed(cfg_.purge, c->loopback)) {
     purge_denied++;
     answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
     return;
   }
-  purge_requests++;
-  CacheBackend* be = px_->backend_.get();
-  if (!be || !px_->cfg_.cache_enabled) {
+  PurgeRequest rq;
+  std::string bad;
+  parse_purge(q, key, cfg_, &rq, &bad);
+  if (!rq.dry_run) purge_requests++;
+  if (!bad.empty()) {
+    answer_purge(cid, seq, 400, "Bad Request", bad);
+    return;
+  }
+  if (!px_->backend_ || !px_->cfg_.cache_enabled) {
     answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
     return;
   }
-  px_->note_purge(key, prefix);  // before the tier is touched: fills in flight are refused
-  if (!soft || !cfg_.grace) {  // (without --grace staleness has no meaning)
-    hard_purge(cid, seq, key, prefix, soft);
+  const PurgeRef r = std::make_shared<const PurgeRequest>(std::move(rq));
+  if (r->dry_run) {
+    purge_dry_runs++;
+    dry_purge(cid, seq, r);
     return;
   }
-  const uint32_t stale_at = unix_now(), keep = cfg_.grace;
-  if (prefix) {
-    be->soften_prefix(key, false, stale_at, keep, this, [this, cid, seq, key](int64_t n) {
-      if (n < 0) {
-        hard_purge(cid, seq, key, true, true);
-        return;
+  if (r->what.kind == KeyedSelector::Kind::Tags) tag_purge_requests++;
+  if (r->what.kind == KeyedSelector::Kind::Glob) purge_glob_requests++;
+  px_->note_purge(r->what);  // before the tier is touched: fills in flight are refused
+  if (r->soft && cfg_.grace) soft_purge(cid, seq, r);  // (without --grace staleness has no meaning)
+  else hard_purge(cid, seq, r, r->soft);
+}
+
+static const char* const kCannotScan = "\"error\":\"the cache tier cannot scan its keys\"}";
+
+void Reactor::soft_purge(uint64_t cid, uint64_t seq, const PurgeRef& r) {
+  CacheBackend* be = px_->backend_.get();
+  const PurgeAction how = PurgeAction::soften(unix_now(), cfg_.grace);
+  be->purge(r->what, how, this, [this, be, cid, seq, r, how](int64_t n) {
+    if (n < 0) {  // the tier cannot: a hard purge that says so
+      hard_purge(cid, seq, r, true);
+      return;
+    }
+    const auto answer = [this, cid, seq, r, n](const int64_t* variants) {
+      const uint64_t all = (uint64_t)n + (uint64_t)(variants && *variants > 0 ? *variants : 0);
+      if (r->by_tag()) {
+        tag_softened_objects += all;
+      } else {
+        soft_purge_requests++;
+        softened_objects += all;
       }
-      soft_purge_requests++;
-      softened_objects += (uint64_t)n;
       answer_purge(cid, seq, 200, "OK",
-                   "{\"mode\":\"prefix\",\"soft\":true,\"softened\":" + std::to_string(n) + "}");
-    });
-    return;
-  }
-  be->soften_prefix(key, true, stale_at, keep, this,
-                    [this, be, key, cid, seq, stale_at, keep](int64_t n) {
-    if (n < 0) {
-      hard_purge(cid, seq, key, false, true);
+                   r->head() + "\"soft\":true," + r->tags_field() + "\"softened\":" +
+                       std::to_string(n) +
+                       (variants ? ",\"variants\":" + std::to_string(*variants < 0 ? -1 : *variants)
+                                 : std::string()) + "}");
+    };
+    if (!r->exact()) {
+      answer(nullptr);
       return;
     }
-    be->soften_prefix(key + '\x1f', false, stale_at, keep, this, [this, cid, seq, n](int64_t m) {
-      soft_purge_requests++;
-      softened_objects += (uint64_t)n + (uint64_t)(m > 0 ? m : 0);
-      answer_purge(cid, seq, 200, "OK",
-                   "{\"mode\":\"exact\",\"soft\":true,\"softened\":" + std::to_string(n) +
-                       ",\"variants\":" + std::to_string(m < 0 ? -1 : m) + "}");
-    });
+    be->purge(r->variants, how, this, [answer](int64_t m) { answer(&m); });
   });
 }
 
-// The hard purge; `soft_asked`: the request asked for a soft one that cannot be had, which the
-// answer says ("soft":false). Without it the answers are what they always were.
-void Reactor::hard_purge(uint64_t cid, uint64_t seq, const std::string& key, bool prefix,
-                         bool soft_asked) {
+// `soft_asked`: the request asked for a soft purge that cannot be had, which the answer says
+// ("soft":false). Without it the answers are what they always were.
+void Reactor::hard_purge(uint64_t cid, uint64_t seq, const PurgeRef& r, bool soft_asked) {
   CacheBackend* be = px_->backend_.get();
-  const std::string mode = std::string("{\"mode\":\"") + (prefix ? "prefix" : "exact") + "\"," +
-                           (soft_asked ? "\"soft\":false," : "");
-  if (prefix) {
-    be->purge_prefix(key, this, [this, cid, seq, mode](int64_t n) {
-      if (n < 0) {
-        answer_purge(cid, seq, 501, "Not Implemented",
-                     mode + "\"error\":\"the cache tier cannot scan its keys\"}");
-        return;
-      }
-      purged_objects += (uint64_t)n;
-      answer_purge(cid, seq, 200, "OK", mode + "\"purged\":" + std::to_string(n) + "}");
+  const std::string head = r->head() + (soft_asked ? "\"soft\":false," : "");
+  if (r->exact()) {
+    const std::string& key = r->what.pattern;
+    const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(key.data()), key.size());
+    be->del(key, d, this, [this, be, cid, seq, r, head](bool found) {
+      be->purge(r->variants, PurgeAction::remove(), this, [this, cid, seq, found, head](int64_t n) {
+        purged_objects += (found ? 1 : 0) + (uint64_t)(n > 0 ? n : 0);
+        answer_purge(cid, seq, 200, "OK",
+                     head + "\"found\":" + (found ? "true" : "false") +
+                         ",\"variants\":" + std::to_string(n < 0 ? -1 : n) + "}");
+      });
     });
     return;
   }
-  const Digest d = digest_bytes(reinterpret_cast<const uint8_t*>(key.data()), key.size());
-  be->del(key, d, this, [this, be, key, cid, seq, mode](bool found) {
-    be->purge_prefix(key + '\x1f', this, [this, cid, seq, found, mode](int64_t n) {
-      purged_objects += (found ? 1 : 0) + (uint64_t)(n > 0 ? n : 0);
-      answer_purge(cid, seq, 200, "OK",
-                   mode + "\"found\":" + (found ? "true" : "false") +
-                       ",\"variants\":" + std::to_string(n < 0 ? -1 : n) + "}");
-    });
-  });
-}
-
-// The distinct tags of a tag header's value: split on space, tab and comma, empty tokens
-// dropped, duplicates collapsed; as hashes (keyed.h tag_hash), in order of first appearance.
-static std::vector<uint64_t> tag_hashes_of(const std::string& value) {
-  std::vector<uint64_t> out;
-  size_t pos = 0;
-  while (pos < value.size()) {
-    const size_t e = std::min(value.find_first_of(" \t,", pos), value.size());
-    if (e > pos) {
-      const uint64_t h = tag_hash(value.data() + pos, e - pos);
-      if (std::find(out.begin(), out.end(), h) == out.end()) out.push_back(h);
-    }
-    pos = e + 1;
-  }
-  return out;
-}
-
-// PURGE with X-Purge-Mode: tag. The tags come from the request's header named by
-// ProxyConfig::tag_header (`list`; null: no such header, or the option is off); the URL is
-// ignored. Every object stored behind a tag block that names one of them goes (or, with
-// X-Purge-Soft: 1 and --grace, is made stale: CacheBackend::soften_tags), on the same terms
-// as a prefix purge: the loopback rule, note_purge before the tier is touched, the hard
-// fallback answered with "soft":false, 501 from a tier that cannot scan.
-void Reactor::on_purge_tags(Client* c, Slot* s, const std::string* list, bool soft) {
-  const uint64_t cid = c->id, seq = s->seq;
-  if (!purge_allowed(cfg_.purge, c->loopback)) {
-    purge_denied++;
-    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
-    return;
-  }
-  purge_requests++;
-  if (cfg_.tag_header.empty()) {
-    answer_purge(cid, seq, 400, "Bad Request",
-                 "{\"mode\":\"tag\",\"error\":\"no tag header is configured\"}");
-    return;
-  }
-  std::vector<uint64_t> hashes = list ? tag_hashes_of(*list) : std::vector<uint64_t>();
-  if (hashes.empty() || hashes.size() > kMaxPurgeTags) {
-    answer_purge(cid, seq, 400, "Bad Request",
-                 std::string("{\"mode\":\"tag\",\"error\":\"") +
-                     (hashes.empty() ? "the request names no tags" : "more than 64 tags") + "\"}");
-    return;
-  }
-  CacheBackend* be = px_->backend_.get();
-  if (!be || !px_->cfg_.cache_enabled) {
-    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
-    return;
-  }
-  tag_purge_requests++;
-  px_->note_purge_tags(hashes);  // before the tier is touched: fills in flight are refused
-  if (!soft || !cfg_.grace) {
-    hard_purge_tags(cid, seq, std::move(hashes), soft);
-    return;
-  }
-  be->soften_tags(hashes, unix_now(), cfg_.grace, this, [this, cid, seq, hashes](int64_t n) {
+  be->purge(r->what, PurgeAction::remove(), this, [this, cid, seq, r, head](int64_t n) {
     if (n < 0) {
-      hard_purge_tags(cid, seq, hashes, true);
+      answer_purge(cid, seq, 501, "Not Implemented", head + kCannotScan);
       return;
     }
-    tag_softened_objects += (uint64_t)n;
+    (r->by_tag() ? tag_purged_objects : purged_objects) += (uint64_t)n;
     answer_purge(cid, seq, 200, "OK",
-                 "{\"mode\":\"tag\",\"soft\":true,\"tags\":" + std::to_string(hashes.size()) +
-                     ",\"softened\":" + std::to_string(n) + "}");
+                 head + r->tags_field() + "\"purged\":" + std::to_string(n) + "}");
   });
 }
 
-void Reactor::hard_purge_tags(uint64_t cid, uint64_t seq, std::vector<uint64_t> hashes,
-                              bool soft_asked) {
-  const std::string mode =
-      std::string("{\"mode\":\"tag\",") + (soft_asked ? "\"soft\":false," : "");
-  const size_t nt = hashes.size();
-  px_->backend_->purge_tags(hashes, this, [this, cid, seq, mode, nt](int64_t n) {
-    if (n < 0) {
-      answer_purge(cid, seq, 501, "Not Implemented",
-                   mode + "\"error\":\"the cache tier cannot scan its keys\"}");
-      return;
-    }
-    tag_purged_objects += (uint64_t)n;
-    answer_purge(cid, seq, 200, "OK",
-                 mode + "\"tags\":" + std::to_string(nt) + ",\"purged\":" + std::to_string(n) +
-                     "}");
-  });
-}
-
-// PURGE with X-Purge-Mode: glob. The pattern is the request's key as formed for the other
-// modes (Host + URL with key_host, else the URL) with '*' as the wildcard: every '\\' is escaped
-// before compiling, so every other byte of the URL is literal, a '?' before a query string
-// included. An object goes when its key, up to the first '\x1f', matches (keyed.h), so a Vary
-// marker and its variants go together. A pattern the compiler refuses (stars only, more than
-// 8 stars or 1024 literal bytes) is a 400. Everything else is on a prefix purge's terms: the
-// loopback rule, note_purge before the tier is touched, X-Purge-Soft: 1 with --grace
-// (CacheBackend::soften_glob), the hard fallback answered with "soft":false, 501 from a tier
-// that cannot scan.
-void Reactor::on_purge_glob(Client* c, Slot* s, const std::string& key, bool soft) {
-  const uint64_t cid = c->id, seq = s->seq;
-  if (!purge_allowed(cfg_.purge, c->loopback)) {
-    purge_denied++;
-    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
-    return;
-  }
-  purge_requests++;
-  const std::string pattern = keyed_glob_escape(key, true);
-  auto g = std::make_shared<KeyedGlob>();
-  std::string why;
-  if (!compile_keyed_glob(pattern, g.get(), &why)) {
-    answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
-    return;
-  }
+void Reactor::dry_purge(uint64_t cid, uint64_t seq, const PurgeRef& r) {
   CacheBackend* be = px_->backend_.get();
-  if (!be || !px_->cfg_.cache_enabled) {
-    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
-    return;
-  }
-  purge_glob_requests++;
-  px_->note_purge_glob(std::move(g));  // before the tier is touched: fills in flight are refused
-  if (!soft || !cfg_.grace) {
-    hard_purge_glob(cid, seq, pattern, soft);
-    return;
-  }
-  be->soften_glob(pattern, unix_now(), cfg_.grace, this, [this, cid, seq, pattern](int64_t n) {
-    if (n < 0) {
-      hard_purge_glob(cid, seq, pattern, true);
+  const std::string head = r->head() + "\"dry_run\":true," + r->tags_field();
+  be->list_objects(ListQuery{r->what, 0, {}}, this, [this, be, cid, seq, r, head](ListResult l) {
+    if (!l.ok) {
+      answer_purge(cid, seq, 501, "Not Implemented", head + kCannotScan);
       return;
     }
-    soft_purge_requests++;
-    softened_objects += (uint64_t)n;
-    answer_purge(cid, seq, 200, "OK",
-                 "{\"mode\":\"glob\",\"soft\":true,\"softened\":" + std::to_string(n) + "}");
-  });
-}
-
-void Reactor::hard_purge_glob(uint64_t cid, uint64_t seq, const std::string& pattern,
-                              bool soft_asked) {
-  const std::string mode =
-      std::string("{\"mode\":\"glob\",") + (soft_asked ? "\"soft\":false," : "");
-  px_->backend_->purge_glob(pattern, this, [this, cid, seq, mode](int64_t n) {
-    if (n < 0) {
-      answer_purge(cid, seq, 501, "Not Implemented",
-                   mode + "\"error\":\"the cache tier cannot scan its keys\"}");
-      return;
-    }
-    purged_objects += (uint64_t)n;
-    answer_purge(cid, seq, 200, "OK", mode + "\"purged\":" + std::to_string(n) + "}");
-  });
-}
-
-// PURGE with X-Purge-Dry-Run: 1: what the purge would hit, answered from the count-only list
-// (CacheBackend::list_objects with limit 0). The --purge access rule holds; nothing is removed
-// or softened and note_purge is not called, so a fill in flight is still stored. mode: 0 exact
-// (a second scan counts the Vary variants under key + '\x1f'), 1 prefix, 2 tag, 3 glob (the
-// pattern formed and refused as on_purge_glob's).
-void Reactor::on_purge_dry_run(Client* c, Slot* s, const std::string& key, int mode,
-                               const std::string* list) {
-  const uint64_t cid = c->id, seq = s->seq;
-  if (!purge_allowed(cfg_.purge, c->loopback)) {
-    purge_denied++;
-    answer_purge(cid, seq, 403, "Forbidden", "{\"error\":\"purge is allowed from loopback only\"}");
-    return;
-  }
-  ListQuery q;
-  q.limit = 0;
-  std::string head;
-  if (mode == 2) {
-    if (cfg_.tag_header.empty()) {
-      answer_purge(cid, seq, 400, "Bad Request",
-                   "{\"mode\":\"tag\",\"error\":\"no tag header is configured\"}");
-      return;
-    }
-    q.mode = kListTags;
-    if (list) q.tags = tag_hashes_of(*list);
-    if (q.tags.empty() || q.tags.size() > kMaxPurgeTags) {
-      answer_purge(cid, seq, 400, "Bad Request",
-                   std::string("{\"mode\":\"tag\",\"error\":\"") +
-                       (q.tags.empty() ? "the request names no tags" : "more than 64 tags") + "\"}");
-      return;
-    }
-    head = "{\"mode\":\"tag\",\"dry_run\":true,\"tags\":" + std::to_string(q.tags.size()) + ",";
-  } else if (mode == 3) {
-    q.mode = kListGlob;
-    q.pattern = keyed_glob_escape(key, true);
-    KeyedGlob g;
-    std::string why;
-    if (!compile_keyed_glob(q.pattern, &g, &why)) {
-      answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
-      return;
-    }
-    head = "{\"mode\":\"glob\",\"dry_run\":true,";
-  } else {
-    q.mode = kListPrefix;
-    q.pattern = key;
-    q.exact = mode == 0;
-    head = std::string("{\"mode\":\"") + (mode ? "prefix" : "exact") + "\",\"dry_run\":true,";
-  }
-  CacheBackend* be = px_->backend_.get();
-  if (!be || !px_->cfg_.cache_enabled) {
-    answer_purge(cid, seq, 501, "Not Implemented", "{\"error\":\"no cache\"}");
-    return;
-  }
-  purge_dry_runs++;
-  be->list_objects(q, this, [this, be, cid, seq, head, key, mode](ListResult r) {
-    if (!r.ok) {
-      answer_purge(cid, seq, 501, "Not Implemented",
-                   head + "\"error\":\"the cache tier cannot scan its keys\"}");
-      return;
-    }
-    const std::string counts = head + "\"matched\":" + std::to_string(r.matched) +
-                               ",\"bytes\":" + std::to_string(r.bytes);
-    if (mode != 0) {
+    const std::string counts = head + "\"matched\":" + std::to_string(l.matched) +
+                               ",\"bytes\":" + std::to_string(l.bytes);
+    if (!r->exact()) {
       answer_purge(cid, seq, 200, "OK", counts + "}");
       return;
     }
-    ListQuery v;
-    v.mode = kListPrefix;
-    v.pattern = key + '\x1f';
-    v.limit = 0;
-    be->list_objects(v, this, [this, cid, seq, counts](ListResult m) {
+    be->list_objects(ListQuery{r->variants, 0, {}}, this, [this, cid, seq, counts](ListResult m) {
       answer_purge(cid, seq, 200, "OK",
                    counts + ",\"variants\":" + std::to_string(m.ok ? (int64_t)m.matched : -1) + "}");
     });
@@ -1149,41 +1022,27 @@ void Reactor::on_inspect(Client* c, Slot* s, const std::string& qs) {
     answer_purge(cid, seq, 400, "Bad Request", "{\"error\":\"bad query\"}");
     return;
   }
-  ListQuery q;
-  q.limit = p.limit;
-  q.after = p.after;
+  ListQuery q{KeyedSelector(), p.limit, p.after};
   const char* mode = "all";
+  std::string bad;
   if (p.which == 1 || p.which == 2) {
-    q.mode = kListPrefix;
-    q.pattern = p.value;
-    q.exact = p.which == 2;
-    mode = q.exact ? "key" : "prefix";
-    if (q.pattern.empty() || q.pattern.size() > kMaxKeyedKey) {
-      answer_purge(cid, seq, 400, "Bad Request", "{\"error\":\"empty or oversized pattern\"}");
-      return;
-    }
+    mode = p.which == 2 ? "key" : "prefix";
+    q.what = p.which == 2 ? KeyedSelector::exact(p.value) : KeyedSelector::prefix(p.value);
+    if (!q.what.valid()) bad = "{\"error\":\"empty or oversized pattern\"}";
   } else if (p.which == 3) {
     mode = "tag";
-    q.mode = kListTags;
-    if (!cfg_.tag_header.empty()) q.tags = tag_hashes_of(p.value);
-    if (q.tags.empty() || q.tags.size() > kMaxPurgeTags) {
-      answer_purge(cid, seq, 400, "Bad Request",
-                   std::string("{\"mode\":\"tag\",\"error\":\"") +
-                       (cfg_.tag_header.empty() ? "no tag header is configured"
-                        : q.tags.empty()        ? "the request names no tags"
-                                                : "more than 64 tags") + "\"}");
-      return;
-    }
+    q.what = KeyedSelector::tags(cfg_.tag_header.empty() ? std::vector<uint64_t>()
+                                                         : tag_hashes_of(p.value));
+    if (!q.what.valid()) bad = bad_tags(cfg_.tag_header.empty(), q.what);
   } else if (p.which == 4) {  // (the pattern as written: '*' the wildcard, '\\' escapes)
     mode = "glob";
-    q.mode = kListGlob;
-    q.pattern = p.value;
-    KeyedGlob g;
     std::string why;
-    if (!compile_keyed_glob(q.pattern, &g, &why)) {
-      answer_purge(cid, seq, 400, "Bad Request", "{\"mode\":\"glob\",\"error\":\"" + why + "\"}");
-      return;
-    }
+    q.what = KeyedSelector::glob(p.value, &why);
+    if (!q.what.valid()) bad = bad_glob(why);
+  }
+  if (!bad.empty()) {
+    answer_purge(cid, seq, 400, "Bad Request", bad);
+    return;
   }
   CacheBackend* be = px_->backend_.get();
   if (!be || !px_->cfg_.cache_enabled) {
@@ -2563,45 +2422,11 @@ std::string prometheus_text(const std::string& stats_json) {
   return o.str();
 }
 
-void Proxy::note_purge(const std::string& pattern, bool prefix) {
+void Proxy::note_purge(KeyedSelector what) {
   std::lock_guard<std::mutex> lk(purge_mu_);
   if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
   const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
-  PurgeRec& r = purge_ring_[gen % kPurgeRing];
-  r.gen = gen;
-  r.pattern = pattern;
-  r.prefix = prefix;
-  r.by_tag = false;
-  r.tags.clear();
-  r.glob.reset();
-  purge_gen_.store(gen, std::memory_order_release);
-}
-
-void Proxy::note_purge_glob(std::shared_ptr<const KeyedGlob> glob) {
-  std::lock_guard<std::mutex> lk(purge_mu_);
-  if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
-  const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
-  PurgeRec& r = purge_ring_[gen % kPurgeRing];
-  r.gen = gen;
-  r.pattern.clear();
-  r.prefix = false;
-  r.by_tag = false;
-  r.tags.clear();
-  r.glob = std::move(glob);
-  purge_gen_.store(gen, std::memory_order_release);
-}
-
-void Proxy::note_purge_tags(const std::vector<uint64_t>& hashes) {
-  std::lock_guard<std::mutex> lk(purge_mu_);
-  if (purge_ring_.empty()) purge_ring_.resize(kPurgeRing);
-  const uint64_t gen = purge_gen_.load(std::memory_order_relaxed) + 1;
-  PurgeRec& r = purge_ring_[gen % kPurgeRing];
-  r.gen = gen;
-  r.pattern.clear();
-  r.prefix = false;
-  r.by_tag = true;
-  r.tags = hashes;
-  r.glob.reset();
+  purge_ring_[gen % kPurgeRing] = PurgeRec{gen, std::move(what)};
   purge_gen_.store(gen, std::memory_order_release);
 }
 
@@ -2611,24 +2436,8 @@ bool Proxy::purged_since(uint64_t gen, const std::string& key, const std::string
   std::lock_guard<std::mutex> lk(purge_mu_);
   const uint64_t cur = purge_gen_.load(std::memory_order_relaxed);
   if (cur - gen > kPurgeRing) return true;  // the ring wrapped past this fetch: assume purged
-  for (uint64_t g = gen + 1; g <= cur; ++g) {
-    const PurgeRec& r = purge_ring_[g % kPurgeRing];
-    if (r.by_tag) {
-      if (!tags) continue;
-      if (overflow) return true;
-      for (uint64_t h : *tags)
-        if (std::find(r.tags.begin(), r.tags.end(), h) != r.tags.end()) return true;
-      continue;
-    }
-    if (r.glob) {  // (the subject of a variant's key is its base key)
-      if (keyed_glob_matches(*r.glob, reinterpret_cast<const uint8_t*>(base_key.data()),
-                             base_key.size()))
-        return true;
-      continue;
-    }
-    if (r.prefix ? key.compare(0, r.pattern.size(), r.pattern) == 0 : base_key == r.pattern)
-      return true;
-  }
+  for (uint64_t g = gen + 1; g <= cur; ++g)
+    if (purge_ring_[g % kPurgeRing].what.matches_fill(key, base_key, tags, overflow)) return true;
   return false;
 }
 

@@ -65,7 +65,7 @@ struct ProxyConfig {
   // `PURGE <url>` removes the URL's object and all its Vary variants; with the header
   // `X-Purge-Mode: prefix` every object whose key starts with the URL's key. With the header
   // `X-Purge-Soft: 1` and grace != 0 the same objects are kept and made stale now instead
-  // (CacheBackend::soften_prefix; their lives capped at now + grace, never extended);
+  // (PurgeAction::soften; their lives capped at now + grace, never extended);
   // without grace, or where the tier cannot, it is a hard purge answered with "soft":false.
   std::string purge = "off";
   // Purge by surrogate key (Varnish xkey, Fastly Surrogate-Key, Cloudflare Cache-Tag): the
@@ -170,15 +170,12 @@ class Proxy {
   // cached if a newer purge matches its key or the ring has wrapped past its generation.
   static constexpr size_t kPurgeRing = 64;
   uint64_t purge_generation() const { return purge_gen_.load(std::memory_order_acquire); }
-  void note_purge(const std::string& pattern, bool prefix);
-  void note_purge_tags(const std::vector<uint64_t>& hashes);
-  // a glob purge: a fetch whose base_key the compiled pattern matches is refused
-  void note_purge_glob(std::shared_ptr<const KeyedGlob> glob);
+  void note_purge(KeyedSelector what);
   // `key`: the key the object would be stored under; `base_key`: its URL key (an exact
   // purge of the URL covers every variant)
   // `tags`: the object's tag hashes (null: it has none), `overflow`: it named too many — a
   // tag purge since `gen` that names one of them, or any tag purge for an overflowing
-  // object, refuses the fill as a key purge does
+  // object, refuses the fill as a key purge does (KeyedSelector::matches_fill has the rules)
   bool purged_since(uint64_t gen, const std::string& key, const std::string& base_key,
                     const std::vector<uint64_t>* tags = nullptr, bool overflow = false);
 
@@ -201,11 +198,7 @@ class Proxy {
   std::atomic<int> rr_{0};
   struct PurgeRec {
     uint64_t gen = 0;
-    std::string pattern;
-    bool prefix = false;
-    bool by_tag = false;  // a tag purge: `tags` holds its hashes, the pattern is unused
-    std::vector<uint64_t> tags;
-    std::shared_ptr<const KeyedGlob> glob;  // a glob purge: the compiled pattern, else null
+    KeyedSelector what;
   };
   std::atomic<uint64_t> purge_gen_{0};
   std::mutex purge_mu_;

@@ -2,7 +2,7 @@
 // refused form and at the limits; keyed_glob_matches on the overlap table, on the subject rule
 // (the key ends at its first 0x1f) and on keys of 0, 1 and 65535 bytes, all on exact-size heap
 // copies; keyed_value_glob_matches on values whose klen points past their end; the glob
-// selector of inspect.h (query parsing, list_query_valid, keyed_value_listed); and
+// selector of inspect.h and selector.h (query parsing, list_query_valid, matches_value); and
 // HostCache::remove_keyed_glob, soften_keyed_glob and list_keyed(kListGlob) on a small shard.
 // Built with -fsanitize=address,undefined by tests/test_glob_purge.py, so a read past a key
 // or a value, or a write past a buffer, is reported.
@@ -146,27 +146,23 @@ static void inspect_helpers() {
   CHECK(!parse_inspect_query("glob=a*&prefix=a", &p) && !parse_inspect_query("glob=a&glob=b", &p));
   CHECK(!parse_inspect_query("tag=a&glob=b", &p) && !parse_inspect_query("glob=%", &p));
   ListQuery q;
-  q.mode = kListGlob;
+  q.what = KeyedSelector::glob("");
   CHECK(!list_query_valid(q));
   for (const std::string& bad : {std::string("*"), std::string("a\\"), stars(9, "a"),
                                  std::string(1025, 'a')}) {
-    q.pattern = bad;
-    CHECK(!list_query_valid(q));
+    std::string why;
+    q.what = KeyedSelector::glob(bad, &why);
+    CHECK(!list_query_valid(q) && !why.empty() && !q.what.compiled);
   }
-  q.pattern = "*/static/*";
-  CHECK(list_query_valid(q));
-  q.exact = true;
-  CHECK(!list_query_valid(q));
-  q.exact = false;
+  q.what = KeyedSelector::glob("*/static/*");
+  CHECK(list_query_valid(q) && q.what.list_mode() == kListGlob);
   q.limit = kMaxListRows + 1;
   CHECK(!list_query_valid(q));
   q.limit = 5;
-  KeyedGlob g;
-  CHECK(compile_keyed_glob(q.pattern, &g, nullptr));
   const std::string v = keyed_value("h/static/x", "p");
   const uint8_t* const b = reinterpret_cast<const uint8_t*>(v.data());
-  CHECK(keyed_value_listed(b, v.size(), q, &g) && !keyed_value_listed(b, v.size(), q));
-  CHECK(!keyed_value_listed(b, 5, q, &g));
+  CHECK(q.what.matches_value(b, v.size()) && !KeyedSelector::glob("*").matches_value(b, v.size()));
+  CHECK(!q.what.matches_value(b, 5));
 }
 
 struct Listing {

@@ -125,19 +125,19 @@ static void http_helpers() {
                           "0.18446744073709551616", "0.99999999999999999999999999999999"})
     CHECK(!hbm_cursor_parse(exact(bad), 4, &shard, &slot));
   ListQuery q;
-  CHECK(list_query_valid(q));
+  CHECK(list_query_valid(q) && q.what.list_mode() == kListAll);
   q.limit = kMaxListRows + 1;
   CHECK(!list_query_valid(q));
   q.limit = 1;
-  q.mode = kListPrefix;
-  CHECK(!list_query_valid(q));
-  q.pattern = "a";
+  q.what = KeyedSelector::prefix("");
+  CHECK(!list_query_valid(q) && q.what.list_mode() == kListPrefix);
+  q.what = KeyedSelector::prefix("a");
   CHECK(list_query_valid(q));
-  q.mode = kListTags;
+  q.what = KeyedSelector::tags({});
+  CHECK(!list_query_valid(q) && q.what.list_mode() == kListTags);
+  q.what = KeyedSelector::tags(std::vector<uint64_t>(kMaxPurgeTags + 1, 1));
   CHECK(!list_query_valid(q));
-  q.tags.assign(kMaxPurgeTags + 1, 1);
-  CHECK(!list_query_valid(q));
-  q.tags.resize(kMaxPurgeTags);
+  q.what = KeyedSelector::tags(std::vector<uint64_t>(kMaxPurgeTags, 1));
   CHECK(list_query_valid(q));
 }
 
